@@ -8,11 +8,15 @@ One step = reset z, y -> one gpad_run over the local shard -> RCCL gather of (z*
 rank 0.  ``value`` = GPAD iterations/s (instance-iterations actually executed, summed over all
 ranks) / max-over-ranks step time.
 
-Also reported on rank 0: QP-solves/s, the C2 single-instance iteration rate, the roofline of
-the dominant kernel (HIP events on the solve stream) and the reference's own CPU GPAD timed on
-this host (cpu_baseline).
+A plain run does only what the headline needs: set up, W warm-up steps, K timed steps, the result
+line (QP-solves/s, ``ms_per_step``, batching and the roofline of the dominant kernel from the
+timed steps' own HIP events beside ``value``).  ``--full`` adds, on rank 0 after the timed steps,
+everything that takes runs of its own: the repeated-input rate, the C1/C2 single-instance rates,
+the side legs (``legs``), the multi-device gather and gpad_group legs and the reference's own CPU
+GPAD timed on this host (cpu_baseline).  ``--dump-outputs DIR`` writes what the last timed step
+returned (z*, y*, per-instance iteration counts) as DIR/<name>.npy.
 
-Usage:  python bench.py [--gpus N] [--steps K] [--warmup W]
+Usage:  python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
         torchrun --nproc-per-node N bench.py --gpus N ...
 """
 from __future__ import annotations
@@ -31,6 +35,8 @@ sys.path.insert(0, os.path.join(ROOT, "gpu-dualgradient-mpc_amd"))
 FP32_PEAK_TFLOPS = 157.3   # MI355X dense fp32 (VALU = f32 MFMA rate), MI355X_MICROARCH.md
 FP64_MFMA_PEAK_TFLOPS = 78.6  # MI355X f64 matrix (spec; measured 70 TF/s back-to-back, profiles/r04_mfma_f64.txt)
 HBM_PEAK_GBS = 8000.0
+FRESH_POOL = 32  # distinct fresh-input draws kept in HBM; longer runs cycle through them (main)
+DUMP_BYTES = 64 * 10**6  # --dump-outputs: at most this much in all
 
 
 def flops_per_iter(n, m):
@@ -205,7 +211,8 @@ def traffic_from_profile(kernel_name):
     bench command (tools/profile.sh -> the newest profiles/rNN_bench_summary.json; FETCH_SIZE x2 +
     WRITE_SIZE, MI355X_MICROARCH.md §HBM): the kernel's bytes summed over every launch of the
     profiled run / the C4 solves that run made (2 x (--warmup + --steps): the fresh-input and the
-    repeated-input loops; the side legs launch other kernel instantiations).  ``kernel_name`` is
+    repeated-input loops of a --full run, which tools/profile.sh asks for; the side legs launch
+    other kernel instantiations).  ``kernel_name`` is
     a prefix: every instantiation of that kernel family and tile count is summed (the T = 13 pairs
     are compiled per last-block length, gpad_panel2_kernel<13, KQ>).  None when absent."""
     import glob
@@ -802,6 +809,24 @@ def make_stream(n, m, batch, count, rank, seed=0):
     return out
 
 
+def dump_outputs(path, arrays):
+    """--dump-outputs: write {name: array} as path/<name>.npy, float32 as it is and everything
+    else as float64.  The arrays share their first axis (the instances); were they more than
+    DUMP_BYTES in all, the same fixed seeded sample of rows is written of each, and the rows'
+    indices as sample_rows.npy."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.asarray(a, np.float32 if a.dtype == np.float32 else np.float64) for k, a in arrays.items()}
+    rows = next(iter(arrays.values())).shape[0]
+    per_row = 8 + sum(a.nbytes // max(rows, 1) for a in arrays.values())  # 8: the row's index
+    keep = (DUMP_BYTES - 1024 * (len(arrays) + 1)) // per_row  # 1024: room for each file's header
+    if keep < rows:
+        idx = np.sort(np.random.default_rng(0).choice(rows, size=keep, replace=False))
+        arrays = {k: a[idx] for k, a in arrays.items()}
+        arrays["sample_rows"] = idx.astype(np.float64)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), np.ascontiguousarray(a))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -816,13 +841,18 @@ def main():
     ap.add_argument("--tol", type=float, default=1e-4)
     ap.add_argument("--max-iters", type=int, default=5000)
     ap.add_argument("--kernel", default="auto", choices=["auto", "stream", "resident", "panel"])
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the C2/C5 side legs")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure what takes runs of its own: the other input mode, "
+                         "single instances, side legs, CPU baselines, the multi-device gather and group legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's z*, y* and iteration counts (rank 0's view) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the CPU baselines")
+    ap.add_argument("--no-extra", action="store_true", help="--full: skip the C2/C5 side legs")
     ap.add_argument("--repeat-inputs", action="store_true",
                     help="headline on the SAME inputs every step (the planner then sees its own future); "
-                         "default: fresh inputs per step, the repeated-input rate reported beside it")
+                         "default: fresh inputs per step (--full reports the other mode's rate beside it)")
     ap.add_argument("--no-sharded", action="store_true",
-                    help="N > 1: skip rank 0's gpad_group leg over devices 0..N-1 after the timed region")
+                    help="--full, N > 1: skip rank 0's gpad_group leg over devices 0..N-1 after the timed region")
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
                     help="nccl (= RCCL) for real runs; gloo to rehearse ranks sharing one GPU")
     args = ap.parse_args()
@@ -862,11 +892,18 @@ def main():
     stream = torch.cuda.current_stream(dev)
 
     n, m, B = args.nu * args.horizon, args.m, args.batch
-    ML, G, L, M, g = make_shard(n, m, B, rank * B)
+    # which input modes run: the headline's, with --full both (fresh, then repeated)
+    run_fresh = args.full or not args.repeat_inputs
+    run_repeat = args.full or args.repeat_inputs
+    # the shard's own q/b draws feed the repeated-input steps and --full's C2 and CPU legs
+    ML, G, L, M, g = make_shard(n, m, B if run_repeat else 1, rank * B)
     f32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.float32)).to(dev)  # noqa: E731
     dML, dG, dM, dg = f32(ML), f32(G), f32(M), f32(g)
-    # fresh problems for every warm-up and timed step, resident in HBM before timing
-    fresh = [(f32(a), f32(b)) for a, b in make_stream(n, m, B, args.warmup + args.steps, rank)]
+    # fresh problems for every warm-up and timed step, resident in HBM before timing; past
+    # FRESH_POOL steps the draws repeat cyclically (a step still never follows its own problem), so
+    # the set-up time does not grow with --steps
+    npool = max(1, min(args.warmup + args.steps, FRESH_POOL))
+    fresh = [(f32(a), f32(b)) for a, b in make_stream(n, m, B, npool, rank)] if run_fresh else []
     # z and y back to back in one buffer, so the cold start of every step is one fill
     zy = torch.zeros(B * (n + m), device=dev)
     z, y = zy[: B * n].view(B, n), zy[B * n:].view(B, m)
@@ -905,7 +942,21 @@ def main():
                 sl["work"].wait()
                 sl["work"] = None
 
-    def timed(inputs):
+    def last_outputs(iters_host):
+        """What the last step returned, on the host, before another run overwrites it: z*, y* (for
+        N > 1 every rank's shard in rank order, as gathered to rank 0) and the per-instance
+        iteration counts.  None on the other ranks."""
+        if world == 1:
+            return {"z": z.cpu().numpy(), "y": y.cpu().numpy(), "iterations": iters_host.copy()}
+        it = torch.from_numpy(iters_host).to(comm_dev)
+        allit = [torch.empty_like(it) for _ in range(world)]
+        dist.all_gather(allit, it)
+        if rank != 0:
+            return None
+        zy_all = torch.cat(slots[(nstep[0] - 1) % 2]["gl"]).cpu().numpy()
+        return {"z": zy_all[:, :n], "y": zy_all[:, n:], "iterations": torch.cat(allit).cpu().numpy()}
+
+    def timed(inputs, keep_outputs=False):
         """W warm-up steps, then K timed steps enqueued back to back with no host
         synchronisation: each step's work (the sum of its per-instance iteration counts) is
         accumulated on the device after its solve; HIP events on the solve stream bracket the
@@ -940,6 +991,7 @@ def main():
         total_iters = int(acc.item())
         iters_host = np.zeros(B, np.int32)
         st = solver.last_stats(iters=iters_host)  # the last step's counters, outside the timed region
+        outputs = last_outputs(iters_host) if keep_outputs else None
         # max time over ranks, sum of work over ranks
         stats = torch.tensor([dt, float(total_iters), kern_ms, float(st["converged"])], dtype=torch.float64,
                              device=comm_dev)
@@ -960,7 +1012,7 @@ def main():
             per_rank = [[float(v) for v in t.cpu()] for t in allr]
         return dict(dt=dt_all, iters_all=iters_all, converged_all=conv_all, total_iters=total_iters,
                     kern_ms=kern_ms, st=st, iters_host=iters_host, plan=solver.phase_plan(),
-                    phases=last_phases(), drain_ms=drain_ms, per_rank=per_rank)
+                    phases=last_phases(), drain_ms=drain_ms, per_rank=per_rank, outputs=outputs)
 
     def last_phases():
         try:
@@ -984,10 +1036,13 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         return float(t.item())
 
-    fresh_run = timed(lambda k: fresh[k])
-    repeat_run = timed(lambda k: (dM, dg))
+    dump = args.dump_outputs is not None
+    fresh_run = timed(lambda k: fresh[k % npool], dump and not args.repeat_inputs) if run_fresh else None
+    repeat_run = timed(lambda k: (dM, dg), dump and args.repeat_inputs) if run_repeat else None
     head = repeat_run if args.repeat_inputs else fresh_run
-    side = fresh_run if args.repeat_inputs else repeat_run
+    side = fresh_run if args.repeat_inputs else repeat_run  # --full only
+    if dump and rank == 0:
+        dump_outputs(args.dump_outputs, head["outputs"])
     multi = None
     if world > 1:
         pr = head["per_rank"]
@@ -996,7 +1051,7 @@ def main():
             "per_rank_kernel_ms": [r[1] for r in pr],
             "solve_ms_min": min(r[1] for r in pr), "solve_ms_max": max(r[1] for r in pr),
             "drain_ms_max": max(r[2] for r in pr),
-            "gather_ms": gather_ms(),
+            "gather_ms": gather_ms() if args.full else None,
             "gather_bytes_per_rank": B * (n + m) * 4,
             "backend": args.dist_backend,
             "note": "per_rank_kernel_ms: device time per step on each rank's solve stream (solve + "
@@ -1009,16 +1064,16 @@ def main():
     ndist = min(world, ndev)
     hung = False
     if multi is not None:
-        if rank == 0 and ndist >= 2 and not args.no_sharded:
+        if rank == 0 and ndist >= 2 and args.full and not args.no_sharded:
             multi["sharded_c4_global"], hung = guarded(lambda: sharded_leg(dev, ndist, n, m), 240,
                                                        "sharded_leg")
         else:
             multi["sharded_c4_global"] = {"skipped": f"{ndist} distinct device(s) visible" if ndist < 2 else
-                                          "--no-sharded"}
+                                          "--no-sharded" if args.no_sharded else "not a --full run"}
 
     # CPU reference on rank 0 (all ranks' timed regions are over: the barrier above)
     ref = None
-    if rank == 0 and not args.no_cpu:
+    if rank == 0 and args.full and not args.no_cpu:
         ref = CpuRef()
 
     if rank == 0:
@@ -1044,16 +1099,16 @@ def main():
         pan_iters, fin_iters, v_take = panel_share(head["iters_host"], head["phases"])
         pan_ms, pan_src = kernel_ms_from_profile(kname[:-1] + ", " if kname.endswith(">") else kname)
         kernel_frac = (pan_iters * F / (pan_ms * 1e-3) / 1e12 / FP32_PEAK_TFLOPS) if pan_ms else None
-        # single instances (configs C1 and C2): latency kernels, fixed iteration counts
+        # single instances (configs C1 and C2): latency kernels, fixed iteration counts (--full)
         singles = {}
         from gpad_mpc import problems
         qp1 = problems.battery_mpc(4, 10, seed=0)
         c1 = [np.ascontiguousarray(np.asarray(a, np.float64).astype(np.float32))
               for a in (qp1.ML, qp1.G, qp1.M, qp1.g)]
-        for name, (mML, mG, mM, mg_, mL, iters) in {
+        for name, (mML, mG, mM, mg_, mL, iters) in ({
                 "c2": (dML, dG, dM[:1], dg[:1], L32, 1000),
                 "c1": (*[f32(a) for a in c1[:2]], f32(c1[2]).reshape(1, -1), f32(c1[3]).reshape(1, -1),
-                       float(np.float32(qp1.L)), 1000)}.items():
+                       float(np.float32(qp1.L)), 1000)} if args.full else {}).items():
             nn, mm = mML.shape
             with gpad_mpc.GpadSolver(dev.index, stream=stream.cuda_stream) as s1:
                 s1.setup(mML, mG, mL, n=nn, m=mm, batch=1)
@@ -1080,7 +1135,7 @@ def main():
             cpu = cpu_baseline(n, m, ML, G, L, M, g, mean_iters, ref=ref)
             cpu["qp_solves_per_s"] = cpu["value"] / max(1, int(round(mean_iters)))
         extra = {}
-        if not args.no_extra and world == 1:
+        if args.full and not args.no_extra and world == 1:
             extra["hbm_bound_c5"] = hbm_leg(dev, ref=ref)
             extra["distinct_c2_batch"] = distinct_leg(dev, n, m, ref=ref)
             extra["c3_batch4096"] = c3_leg(dev, n, m, ref=ref)
@@ -1092,7 +1147,7 @@ def main():
             extra["battery_n50"] = flat_leg(dev, horizon=50, N=50, ref=ref)
             extra["flat_tol_c1"] = flat_tol_leg(dev, batch=65536)
             extra["flat_tol_n50"] = flat_tol_leg(dev, horizon=50, tol=1e-3, batch=16384)
-        side_value = side["iters_all"] / side["dt"]
+        side_value = side["iters_all"] / side["dt"] if side else None
         out = {
             "metric": "GPAD iterations/s (instance-iterations, solve to eps=1e-4)",
             "value": value,
@@ -1100,6 +1155,7 @@ def main():
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": args.full,
             "ms_per_step": ms_per_step,
             "higher_is_better": True,
             "scaling": "weak",
@@ -1112,6 +1168,7 @@ def main():
                                    f"shared ML/G, Algorithm 1 eps={args.tol}, K=10",
                        "batch_per_gpu": B, "global_batch": B * world, "n": n, "m": m,
                        "inputs": "repeated" if args.repeat_inputs else "fresh per step",
+                       "fresh_draws": len(fresh),
                        "parallelism": (f"instance-sharded x{world}, "
                                        + ("RCCL gather" if args.dist_backend == "nccl" else "gloo gather")
                                        if world > 1 else "single GPU (no gather)")},
@@ -1129,8 +1186,8 @@ def main():
             "converged": int(head["converged_all"]),
             "multi_gpu": multi,
             "kernel": st["kernel"],
-            "single_instance": singles["c2"],
-            "single_instance_c1": singles["c1"],
+            "single_instance": singles.get("c2"),
+            "single_instance_c1": singles.get("c1"),
             "roofline": {"bound": "mfma", "achieved": achieved_tf, "peak": FP32_PEAK_TFLOPS,
                          "unit": "TFLOP/s", "frac": achieved_tf / FP32_PEAK_TFLOPS,
                          "traffic": traffic, "traffic_source": traffic_src,

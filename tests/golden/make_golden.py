@@ -222,10 +222,29 @@ def make_o3(O):
     np.savez_compressed(os.path.join(HERE, "ref_o3.npz"), **out)
 
 
+def make_c2(O, R):
+    """The reference's own steps (RefSeq, the FMA build) at the C2 shape: synthetic_qp(200, 200,
+    seed 0), 100 iterations from zero -> ref_c2.npz (fp32 end states only; the inputs come from
+    the seeded generator).  tests/test_oracle.py pins the oracle to it where the reference is not
+    built."""
+    from gpad_mpc import problems
+    qp = problems.synthetic_qp(200, 200, seed=0)
+    f32 = lambda a: np.asarray(a, np.float64).astype(np.float32)  # noqa: E731
+    MGneg, GL, pD = O.scale(f32(qp.ML), f32(qp.G), f32(qp.g), np.float32(qp.L))
+    th, be = O.schedule_f32(100)
+    z, y = R.solve_c(np.zeros(200), np.zeros(200), MGneg, f32(qp.M), GL, pD, th, be, 100)
+    np.savez_compressed(os.path.join(HERE, "ref_c2.npz"), z_100=z, y_100=y)
+    print(f"ref_c2: |z| {np.linalg.norm(z):.6g} |y| {np.linalg.norm(y):.6g}")
+
+
 def main():
     if "--o3-only" in sys.argv:
         pyoracle.build(ref=True)
         make_o3(pyoracle.Oracle())
+        return
+    if "--c2-only" in sys.argv:
+        pyoracle.build(ref=True)
+        make_c2(pyoracle.Oracle(), pyoracle.RefSeq())
         return
     pyoracle.build(ref=True)
     O = pyoracle.Oracle()
@@ -235,6 +254,7 @@ def main():
     make_datafile(O, R)
     make_closed_loop()
     make_o3(O)
+    make_c2(O, R)
     make_flat("battery_flat_4x10", 4, 10, 0, O, R)
     d = make_flat("battery_flat_3x4", 3, 4, 5, O, R)
     write_flat_datafile(os.path.join(HERE, "datafile_battery_flat_3x4.txt"), d, 3, 4)

@@ -90,8 +90,8 @@ def test_sharded_libgpad_two_ranks_bitexact(gpu, oracle, tmp_path):
 def test_bench_two_ranks_rehearsal(gpu, launcher):
     """bench.py for N = 2 (gloo, both ranks on cuda:0): as the driver launches it under
     torch.distributed.run, and as plain ``python bench.py --gpus 2`` (bench.py starts the ranks)."""
-    args = [os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dist-backend", "gloo", "--no-extra", "--no-cpu",
-            "--steps", "3", "--warmup", "2", "--batch", "2048"]
+    args = [os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dist-backend", "gloo", "--full", "--no-extra",
+            "--no-cpu", "--steps", "3", "--warmup", "2", "--batch", "2048"]
     pre = (["-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
             "--master-port", str(free_port())] if launcher == "torchrun" else [])
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}

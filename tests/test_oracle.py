@@ -188,18 +188,21 @@ def test_oracle_batch_equals_single(oracle):
 
 
 def test_reference_build_matches_oracle_c2_live(oracle):
-    """Live pin at the C2 shape (200 x 200) when the reference was compiled here."""
+    """Pin at the C2 shape (200 x 200): against the reference build's recorded end states
+    (tests/golden/ref_c2.npz, make_golden.py make_c2), and live when the reference was compiled
+    here."""
     import pyoracle
-    if not pyoracle.RefSeq.available():
-        pytest.skip("oracle/_ref not built (needs /root/reference)")
     from gpad_mpc import problems
     qp = problems.synthetic_qp(200, 200, seed=0)
     ML, M, G, g = (qp.ML.astype(np.float32), qp.M.astype(np.float32), qp.G.astype(np.float32),
                    qp.g.astype(np.float32))
     L = np.float32(qp.L)
     MGneg, GL, pD = oracle.scale(ML, G, g, L)
-    th, be = oracle.schedule_f32(100)
-    R = pyoracle.RefSeq()
-    zr, yr = R.solve_c(np.zeros(200), np.zeros(200), MGneg, M, GL, pD, th, be, 100)
     zo, yo, _, _ = oracle.solve_scaled_f32(np.zeros(200), np.zeros(200), MGneg, M, GL, pD, 100, L)
-    assert np.array_equal(zr, zo) and np.array_equal(yr, yo)
+    rec = load_golden("ref_c2")
+    assert np.array_equal(rec["z_100"], zo) and np.array_equal(rec["y_100"], yo)
+    if pyoracle.RefSeq.available():
+        th, be = oracle.schedule_f32(100)
+        R = pyoracle.RefSeq()
+        zr, yr = R.solve_c(np.zeros(200), np.zeros(200), MGneg, M, GL, pD, th, be, 100)
+        assert np.array_equal(zr, zo) and np.array_equal(yr, yo)

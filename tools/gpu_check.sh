@@ -2,7 +2,7 @@
 # GPU check of the tree (run on the box: gpurun -- 'bash tools/gpu_check.sh TAG [steps]'):
 #   tests  : every -m gpu test        -> gpurun_out/TAG_tests.log
 #   smoke  : __graft_entry__.smoke()  -> gpurun_out/TAG_smoke.log
-#   bench  : the default bench line   -> gpurun_out/TAG_bench.json
+#   bench  : the bench line with every leg (--full) -> $OUT/TAG_bench.json (OUT: default bench_out)
 #   tl     : fresh-input C4 solve timeline (tools/tl_run.sh) -> gpurun_out/TAG_tl_timeline.txt
 #   prof   : rocprofv3 kernel trace + PMC passes (tools/profile.sh TAG) -> gpurun_out/prof_TAG/
 # default steps: tests smoke bench.  Every step has its own time limit; the first failure ends
@@ -11,6 +11,8 @@ set -e
 cd $GRAFT_REPO_ROOT
 mkdir -p gpurun_out
 T=$1; shift
+OUT=${OUT:-bench_out}
+mkdir -p $OUT
 STEPS=${@:-tests smoke bench}
 for s in $STEPS; do
   case $s in
@@ -21,14 +23,14 @@ for s in $STEPS; do
       timeout -k 10 200 python -u -c "import __graft_entry__ as g; g.smoke()" > gpurun_out/${T}_smoke.log 2>&1 || { tail -20 gpurun_out/${T}_smoke.log; exit 1; }
       tail -1 gpurun_out/${T}_smoke.log ;;
     bench)
-      timeout -k 10 600 python -u bench.py > gpurun_out/${T}_bench.json 2> gpurun_out/${T}_bench.err || { tail -20 gpurun_out/${T}_bench.err; exit 1; }
+      timeout -k 10 600 python -u bench.py --full > $OUT/${T}_bench.json 2> $OUT/${T}_bench.err || { tail -20 $OUT/${T}_bench.err; exit 1; }
       python3 -c "
-import json; d=json.loads(open('gpurun_out/${T}_bench.json').read().strip().splitlines()[-1])
+import json; d=json.loads(open('$OUT/${T}_bench.json').read().strip().splitlines()[-1])
 print('value', d['value'], 'rep', d['value_repeated_inputs'], 'ms', d['ms_per_step'], 'frac', d['roofline']['frac'], 'c2', d['single_instance']['iters_per_s'])" ;;
     quickbench)
-      timeout -k 10 200 python -u bench.py --no-cpu --no-extra --steps 20 > gpurun_out/${T}_qbench.json 2> gpurun_out/${T}_qbench.err || { tail -20 gpurun_out/${T}_qbench.err; exit 1; }
+      timeout -k 10 200 python -u bench.py --full --no-cpu --no-extra --steps 20 > $OUT/${T}_qbench.json 2> $OUT/${T}_qbench.err || { tail -20 $OUT/${T}_qbench.err; exit 1; }
       python3 -c "
-import json; d=json.loads(open('gpurun_out/${T}_qbench.json').read().strip().splitlines()[-1])
+import json; d=json.loads(open('$OUT/${T}_qbench.json').read().strip().splitlines()[-1])
 print('value', d['value'], 'rep', d['value_repeated_inputs'], 'ms', d['ms_per_step'], 'frac', d['roofline']['frac'], 'c2', d['single_instance']['iters_per_s'], d['batching']['phase_ends'])" ;;
     tl)
       TAG=${T}_tl timeout -k 10 320 bash tools/tl_run.sh > /dev/null
