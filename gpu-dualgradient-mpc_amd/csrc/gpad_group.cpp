@@ -21,6 +21,7 @@
 #include <rccl/rccl.h>  // types only: librccl is loaded on first use (current_rccl() below), not linked
 
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <memory>
 #include <mutex>
@@ -482,7 +483,10 @@ int gpad_group_run(gpad_group_t g, void* z0, void* y0, const void* M, const void
                 tot.total_iterations += sd.total_iterations;
                 tot.kernel = sd.kernel;
                 tot.kernel_ms = std::max(tot.kernel_ms, sd.kernel_ms);
-                tot.tol_floor = std::max(tot.tol_floor, sd.tol_floor);
+                // a shard's NaN floor (a NaN in its g) dominates, an infinite one is kept (as
+                // status_gmax folds the slots, gpad_host.cpp); std::max alone would drop the NaN
+                if (!std::isnan(tot.tol_floor))
+                    tot.tol_floor = std::isnan(sd.tol_floor) ? sd.tol_floor : std::max(tot.tol_floor, sd.tol_floor);
                 tot.flags |= sd.flags;
             }
             int* keep = st->iters;

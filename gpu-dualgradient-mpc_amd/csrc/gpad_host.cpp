@@ -97,14 +97,20 @@ void host_schedule(int N, int kind, double* theta, double* beta) {
 int gpad::set_last_error(int code, const std::string& msg) { return fail(code, msg); }
 
 // Run status block (gpad_handle_s::status): the device error word, then the per-workgroup maxima
-// of |g| (launch_absmax) from which the host takes gmax.  The maxima are zeroed before each run's
-// first launch; the error word is sticky -- zeroed only when the block is created and right after
-// gpad_sync / the stats collection copied it out -- so a fault of an asynchronous run still
-// reaches the next sync when further runs were queued behind it.
+// of |g| from which the host takes gmax.  The maxima are never zeroed by the host: the first writer
+// of each solve (the panel pairs' launch at v_begin == 0, or launch_absmax) stores its own slots
+// and zeroes the rest, later phase launches of that solve max in (SolveArgs::gmax_part).  A run of
+// several solves (gpad_closed_loop with steps > 1) would so keep only its last step's maxima in
+// `part`: after each step launch_absmax_fold folds `part` into `acc` (stored at step 0, maxed in
+// afterwards) and the host reduces `acc` instead, so the floor covers every (step, instance).  The
+// error word is sticky -- zeroed only when the block is created and right after gpad_sync / the
+// stats collection copied it out -- so a fault of an asynchronous run still reaches the next sync
+// when further runs were queued behind it.
 struct RunStatus {
     int err;
     int pad;
     double part[gpad::kAbsmaxMaxBlocks];
+    double acc[gpad::kAbsmaxMaxBlocks];  // multi-step runs: slot-wise maxima of `part` over the steps
 };
 
 struct gpad_handle_s {
@@ -147,9 +153,8 @@ struct gpad_handle_s {
     int sched_len = 0, sched_kind = -1, sched_dtype = -1;
     DevBuf work, counters, pwork;
     std::vector<int> h_counts;
-    // run status block on the device, zeroed per run: {int error bits (gpad::kDevErr*), pad,
-    // double max |g|} -- the error word the kernels report into and the certification floor's
-    // data term (include/gpad.h gpad_run)
+    // run status block on the device (RunStatus above): the error word the kernels report into and
+    // the per-workgroup maxima of |g|, the certification floor's data term (include/gpad.h gpad_run)
     DevBuf status;             // RunStatus
     RunStatus h_status;        // ... its host copy for the stats
     double last_tol = 0.0;          // tol of the last run
@@ -209,17 +214,19 @@ static int reset_status(gpad_handle_t h, double tol, double floor_scale) {
 static int fetch_status(gpad_handle_t h, RunStatus* rs, bool maxima = false) {
     rs->err = 0;
     if (!h->status.p) return GPAD_OK;
-    const size_t bytes = maxima ? sizeof(RunStatus) : offsetof(RunStatus, part);
+    const size_t bytes = !maxima ? offsetof(RunStatus, part)
+                                 : (h->last_steps > 1 ? sizeof(RunStatus) : offsetof(RunStatus, acc));
     HIP_TRY(hipMemcpyAsync(rs, h->status.p, bytes, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipMemsetAsync(h->status.p, 0, sizeof(int), h->stream));
     return GPAD_OK;
 }
 
 static double status_gmax(gpad_handle_t h, const RunStatus& rs) {
+    const double* part = h->last_steps > 1 ? rs.acc : rs.part;  // several solves: folded per step
     double g = 0.0;
     for (int b = 0; b < gpad::kAbsmaxMaxBlocks; ++b) {
-        if (std::isnan(rs.part[b])) return rs.part[b];  // a NaN in g (absmax_nan keeps it)
-        g = std::max(g, rs.part[b]);
+        if (std::isnan(part[b])) return part[b];  // a NaN in g (absmax_nan keeps it)
+        g = std::max(g, part[b]);
     }
     return g;
 }
@@ -817,8 +824,9 @@ int gpad_phase_plan(gpad_handle_t h, int* ends, int* fins, int cap, double* cost
 int gpad_last_phases(gpad_handle_t h, int* ends, int* fins, int* counts, int cap, int* prior) {
     return gpad::abi_guard("gpad_last_phases", [&]() -> int {
         if (!h || cap < 0) return fail(GPAD_ERR_INVALID, "gpad_last_phases: bad argument");
+        if (prior) *prior = 0;
+        if (!h->last_phased || !h->pwork.p || h->flat) return 0;  // not phased: no plan, no prior
         if (prior) *prior = h->last_prior ? 1 : 0;
-        if (!h->last_phased || !h->pwork.p || h->flat) return 0;
         const int k = std::min(cap, h->last_phases.nph);
         for (int i = 0; i < k; ++i) {
             if (ends) ends[i] = h->last_phases.ends[i];
@@ -1440,6 +1448,12 @@ static int state_typed(gpad_handle_t h, T* x, T* z, T* y, int steps, int N, doub
         int* it = counters + 2 * (size_t)batch * t;
         if ((rc = launch_solve<T>(h, dz, dy, Mx, gx, N, tol, false, it, it + batch, &kernel)))
             return rc;
+        if (nsolve > 1 && tol > 0.0) {  // this step's max |g| slots -> the run's (RunStatus::acc)
+            char* sp = (char*)h->status.p;
+            HIP_TRY(gpad::launch_absmax_fold(reinterpret_cast<const double*>(sp + offsetof(RunStatus, part)),
+                                             reinterpret_cast<double*>(sp + offsetof(RunStatus, acc)), t == 0,
+                                             h->stream));
+        }
         if (loop) {  // gpad.m:91-94: u = z*(1:nu); x <- A x + B u
             HIP_TRY(gpad::launch_plant_step<T>(P + o.A, P + o.B, xc, dz, n, xnext, nx, nu, batch,
                                                dxs ? dxs + (size_t)t * xn : nullptr,

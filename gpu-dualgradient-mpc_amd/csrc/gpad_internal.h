@@ -57,9 +57,13 @@ __device__ __forceinline__ double absmax_nan(double acc, double x) {
                              b = (unsigned long long)__double_as_longlong(x) & 0x7fffffffffffffffull;
     return __longlong_as_double((long long)(a > b ? a : b));
 }
-// the decision itself, one expression everywhere (no contraction: -ffp-contract=off)
+// the decision itself, one expression everywhere (no contraction: -ffp-contract=off).  The maxima
+// start from -inf / 0 and drop NaNs (fmax), so an instance whose rows are all NaN -- a NaN or an
+// infinity in its g poisons every row within two iterations -- arrives with viol = -inf, mag = 0:
+// no evidence is not a pass (a finite problem's viol is finite; pD = -inf in every row gives
+// mag = inf, which never passed)
 __host__ __device__ inline bool viol_ok(double viol, double mag, double L, double tol, double margin) {
-    return viol * L + margin * mag * L <= tol;
+    return viol * L + margin * mag * L <= tol && viol > -INFINITY;
 }
 
 // Arguments of a fused solve launch (all kernel families).  Every instance b of the batch
@@ -253,6 +257,9 @@ inline int absmax_blocks(long long count) {
 }
 template <typename T>
 hipError_t launch_absmax(const T* g, long long count, double* part, hipStream_t s);
+// runs of several solves (gpad_closed_loop): acc[b] = part[b] (first) or max(acc[b], part[b]), NaN kept,
+// over the kAbsmaxMaxBlocks slots -- each solve's first writer stores over `part`
+hipError_t launch_absmax_fold(const double* part, double* acc, bool first, hipStream_t s);
 // flat battery data on the MFMA pipe (gpad_flatpanel.hip): per-cell skinny GEMMs over panels
 bool flatpanel_supported(int n, int m, int n_u);
 size_t flatpanel_frag_bytes(int n, int m, int n_u);

@@ -168,4 +168,17 @@ hipError_t launch_absmax(const T* g, long long count, double* part, hipStream_t 
 template hipError_t launch_absmax<float>(const float*, long long, double*, hipStream_t);
 template hipError_t launch_absmax<double>(const double*, long long, double*, hipStream_t);
 
+// One step of a multi-step run: fold the step's per-workgroup maxima into the run's (slot-wise; the
+// host reduces the slots).  Step 0 stores, so `acc` needs no zeroing either.
+__global__ __launch_bounds__(256) void absmax_fold_kernel(const double* __restrict__ part, double* acc, int first) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < kAbsmaxMaxBlocks) acc[i] = first ? part[i] : absmax_nan(acc[i], part[i]);
+}
+
+hipError_t launch_absmax_fold(const double* part, double* acc, bool first, hipStream_t s) {
+    hipLaunchKernelGGL(absmax_fold_kernel, dim3((kAbsmaxMaxBlocks + 255) / 256), dim3(256), 0, s, part, acc,
+                       first ? 1 : 0);
+    return hipGetLastError();
+}
+
 }  // namespace gpad

@@ -105,7 +105,9 @@ typedef struct gpad_stats {
 #define GPAD_FLAG_TOL_FLOOR 1 /* 0 < tol < tol_floor: no instance with an active constraint can be
                                * certified; expect converged == 0 (use f64 or a larger tol)   */
 #define GPAD_FLAG_NONFINITE_G 2 /* tol > 0 and g holds a NaN or an infinity: tol_floor is not
-                                 * finite (NaN when g has a NaN) and TOL_FLOOR is set too        */
+                                 * finite (NaN when g has a NaN) and TOL_FLOOR is set too; the
+                                 * instance holding it is never reported converged, every
+                                 * other instance is solved as if it were not there           */
 
 typedef struct gpad_handle_s* gpad_handle_t;
 

@@ -179,7 +179,8 @@ static int orc_check_f32(float* u, const float* ch, const float* pD, const float
             vc = fmaxf(vc, c + pD[i]);
             mag = fmaxf(mag, fabsf(c) + fabsf(pD[i]));
         }
-        if ((double)vc * L + ORC_MARGIN_F32 * (double)mag * L <= tol) return 1;
+        /* vc = -inf: every row NaN (fmaxf drops them) -- no evidence is not a pass (viol_ok, gpad_internal.h) */
+        if ((double)vc * L + ORC_MARGIN_F32 * (double)mag * L <= tol && vc > -INFINITY) return 1;
     }
     float violh = -INFINITY, magh = 0.0f, wmin = INFINITY;
     double gap = 0.0;
@@ -190,7 +191,7 @@ static int orc_check_f32(float* u, const float* ch, const float* pD, const float
         wmin = fminf(wmin, w[i]);
         gap -= (double)w[i] * (double)t;
     }
-    const int vh_ok = (double)violh * L + ORC_MARGIN_F32 * (double)magh * L <= tol;
+    const int vh_ok = (double)violh * L + ORC_MARGIN_F32 * (double)magh * L <= tol && violh > -INFINITY;
     if (vh_ok && wmin >= 0.0f && gap * L <= tol_gap) return 2;
     if (vh_ok && vc_ctx) return orc_value_branch_f32(vc_ctx, wmin >= 0.0f, gap * L, tol_gap);
     return 0;
@@ -337,7 +338,7 @@ static int orc_check_f64(double* u, const double* ch, const double* pD, const do
             vc = fmax(vc, c + pD[i]);
             mag = fmax(mag, fabs(c) + fabs(pD[i]));
         }
-        if (vc * L + ORC_MARGIN_F64 * mag * L <= tol) return 1;
+        if (vc * L + ORC_MARGIN_F64 * mag * L <= tol && vc > -INFINITY) return 1;
     }
     double violh = -INFINITY, magh = 0.0, wmin = INFINITY, gap = 0.0;
     for (int i = 0; i < m; i++) {
@@ -347,7 +348,7 @@ static int orc_check_f64(double* u, const double* ch, const double* pD, const do
         wmin = fmin(wmin, w[i]);
         gap -= w[i] * t;
     }
-    const int vh_ok = violh * L + ORC_MARGIN_F64 * magh * L <= tol;
+    const int vh_ok = violh * L + ORC_MARGIN_F64 * magh * L <= tol && violh > -INFINITY;
     if (vh_ok && wmin >= 0.0 && gap * L <= tol_gap) return 2;
     if (vh_ok && vc_ctx) return orc_value_branch_f64(vc_ctx, wmin >= 0.0, gap * L, tol_gap);
     return 0;
