@@ -139,7 +139,8 @@ struct gpad_handle_s {
     bool frag64_ok = false;
     int frag64_tiles = 0;
     DevBuf hfrag64;      // ... and H's, bound by gpad_setup_hessian (value branches on the f64 panels)
-    DevBuf q64;          // f64 panels: the refill queue counter (one int, zeroed per launch)
+    DevBuf q64;          // f64 panels: the refill queue counter (one int, zeroed per launch); f32: the
+                         // asynchronous closed loop's pack queue counter (gpad_loop.hip)
     // f64 panels with refills: the start order of the next solve -- the previous solve's instances by
     // its counts, longest first (SolveArgs::order; GPAD_OPT_LPT), rebuilt whenever counts arrive
     DevBuf p64_order;
@@ -384,6 +385,7 @@ int gpad_set_option(gpad_handle_t h, int option, int value) {
                 t.p64_no_relay = 1 - on;
                 return rc;
             }
+            case GPAD_OPT_LOOP_ASYNC: return set(t.loop_async, 0, 1, def.loop_async);
             default: return fail(GPAD_ERR_INVALID, "gpad_set_option: unknown option");
         }
     });
@@ -1435,10 +1437,75 @@ static int state_typed(gpad_handle_t h, T* x, T* z, T* y, int steps, int N, doub
     int kernel = 0;
     const double margin = sizeof(T) == sizeof(float) ? gpad::ViolMargin<float>::value : gpad::ViolMargin<double>::value;
     if ((rc = reset_status(h, tol, margin))) return rc;  // g(x) unscaled: margin * L * (1/L)
-    HIP_TRY(hipEventRecord(h->ev0, h->stream));
     T* xc = xa;
     T* xnext = xb;
-    for (int t = 0; t < nsolve; ++t) {
+    bool async = false;
+    if constexpr (sizeof(T) == sizeof(float)) {
+        // GPAD_OPT_LOOP_ASYNC: the whole loop in one launch of gpad_loop_kernel, every pack stepping on
+        // its own (gpad_loop.hip).  Anything it does not cover runs the lockstep loop below.
+        async = loop && h->tune.loop_async && d.shared && !h->flat && !h->hess_ok && N >= 1 &&
+                (d.kernel == GPAD_KERNEL_AUTO || d.kernel == GPAD_KERNEL_RESIDENT) &&
+                gpad::loop_supported(n, m, nx, nu);
+        if (async) {
+            if ((rc = h->q64.ensure(sizeof(int)))) return rc;
+            gpad::LoopArgs la{};
+            gpad::SolveArgs<float>& a = la.s;
+            a.MGt = (const float*)h->MGt.p;
+            a.GLt = (const float*)h->GLt.p;
+            a.gscale = -1.0 / h->L;
+            a.z = dz;
+            a.y = dy;
+            a.n = n;
+            a.m = m;
+            a.ldn = h->ldn;
+            a.ldm = h->ldm;
+            a.batch = batch;
+            a.N = N;
+            a.check_every = d.check_every;
+            a.tol = tol;
+            a.tol_gap = d.tol_gap > 0.0 ? d.tol_gap : tol;
+            a.L = h->L;
+            a.theta = (const float*)h->theta.p;
+            a.beta = (const float*)h->beta.p;
+            a.iters = counters;
+            a.conv = counters;  // (the kernel indexes both from the counters' base, [steps][iters | conv])
+            a.num_cus = h->num_cus;
+            a.qctr = static_cast<int*>(h->q64.p);
+            a.tune = &h->tune;
+            a.err = (int*)h->status.p;
+            la.PM = P + o.PM;
+            la.M0 = h->has_M0 ? P + o.M0 : nullptr;
+            la.Pg = P + o.Pg;
+            la.g0 = h->has_g0 ? P + o.g0 : nullptr;
+            la.A = P + o.A;
+            la.B = P + o.B;
+            la.x_in = xa;
+            la.x_out = xb;
+            la.xs = dxs;
+            la.us = dus;
+            la.gmax = tol > 0.0 ? reinterpret_cast<double*>((char*)h->status.p + (nsolve > 1 ? offsetof(RunStatus, acc)
+                                                                                             : offsetof(RunStatus, part)))
+                                : nullptr;
+            la.nx = nx;
+            la.nu = nu;
+            la.steps = nsolve;
+            la.warm = warm ? 1 : 0;
+            int grid = std::min(batch, h->num_cus);
+            if (h->tune.duo_max_grid > 0 && h->tune.duo_max_grid < grid) grid = h->tune.duo_max_grid;
+            grid = std::min(grid, (int)gpad::kAbsmaxMaxBlocks);
+            HIP_TRY(hipMemsetAsync(a.qctr, 0, sizeof(int), h->stream));
+            HIP_TRY(hipEventRecord(h->ev0, h->stream));
+            const hipError_t e = gpad::launch_loop(la, grid, h->stream);
+            if (e != hipSuccess) return fail(GPAD_ERR_HIP, std::string("loop kernel: ") + hipGetErrorString(e));
+            kernel = GPAD_KERNEL_LOOP;
+            h->last_phased = false;
+            h->last_p64 = false;
+            h->last_N = N;
+            xc = xb;
+        }
+    }
+    if (!async) HIP_TRY(hipEventRecord(h->ev0, h->stream));
+    for (int t = 0; t < nsolve && !async; ++t) {
         HIP_TRY(gpad::launch_affine2<T>(P + o.PM, h->has_M0 ? P + o.M0 : nullptr, n, Mx, P + o.Pg,
                                         h->has_g0 ? P + o.g0 : nullptr, m, gx, xc, nx, batch, h->stream));
         if (loop && !warm) {  // acceldualgrad.m:16-17: every MPC step starts from z = y = 0

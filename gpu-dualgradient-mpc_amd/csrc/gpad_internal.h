@@ -30,6 +30,7 @@ struct Tuning {
     int debug_drop_handoff = 0;  // GPAD_OPT_DEBUG_DROP_HANDOFF: test-only fault injection
     int p64_no_relay = 0;     // GPAD_OPT_P64_RELAY = 0: f64 panels without the relay layout
     int p64_no_refill = 0;    // GPAD_OPT_P64_REFILL = 0: f64 panels without column refills
+    int loop_async = 0;       // GPAD_OPT_LOOP_ASYNC: gpad_closed_loop in one launch, packs step on their own
 };
 
 // Device error word of a run (SolveArgs::err): kernels OR these bits in with a vector atomic;
@@ -139,6 +140,32 @@ hipError_t launch_resident(const SolveArgs<float>& a, hipStream_t s, bool* suppo
 // zeroed a.qctr.  Persistent grid of `grid` workgroups (one per CU).
 hipError_t launch_duo(const SolveArgs<float>& a, int grid, hipStream_t s);
 bool resident_supported(int n, int m);
+// Asynchronous closed loop (gpad_loop.hip, GPAD_OPT_LOOP_ASYNC): the duo kernel's ping-pong over a
+// queue of closed-loop packs -- a slot whose solve ends applies the plant update and the two affine
+// maps in place and restarts the same pack at its next MPC step; one launch for the whole loop.
+// s: the solve (shared f32 matrices; gP, g, idx_in, count_in, gmax_part unused; z, y: in when warm,
+// out after the last step; iters / conv: the counters of all steps, [steps][iters[batch] |
+// conv[batch]]; qctr zeroed).  The SolveArgs comes first, so kargs() reads it in this kernel too.
+constexpr int kLoopMaxState = 64;  // nx, nu <= this (the state and input live in one LDS row each)
+struct LoopArgs {
+    SolveArgs<float> s;
+    const float* PM;       // [n][nx]   M(x) = M0 + PM x
+    const float* M0;       // [n] or null
+    const float* Pg;       // [m][nx]   g(x) = g0 + Pg x
+    const float* g0;       // [m] or null
+    const float* A;        // [nx][nx]  x+ = A x + B z*[0:nu]
+    const float* B;        // [nx][nu]
+    const float* x_in;     // [batch][nx] initial states
+    float* x_out;          // [batch][nx] states after the last step
+    float* xs;             // [steps][batch][nx] or null
+    float* us;             // [steps][batch][nu] or null
+    double* gmax;          // [kAbsmaxMaxBlocks] per-workgroup max |g| over every (step, pack), the
+                           // unused slots zeroed; null: not wanted
+    int nx, nu, steps, warm;
+};
+bool loop_supported(int n, int m, int nx, int nu);
+// persistent grid of `grid` <= min(batch, kAbsmaxMaxBlocks) workgroups
+hipError_t launch_loop(const LoopArgs& a, int grid, hipStream_t s);
 hipError_t launch_panel(const SolveArgs<float>& a, hipStream_t s, bool* supported);
 // f64 panels on the f64 MFMA pipe (gpad_panel64.hip): shared matrices, n, m <= 256, one panel of 16
 // instances per workgroup, value-function branches when a.hfrag64 is set; a.frag = the -ML | G_L
@@ -159,7 +186,8 @@ bool panel_folds_gmax(int n, int m);
 // Without it (flat panels) the survivors are appended through a.count_out.  Every
 // panel of a phase calls it, parked or not, so no slot keeps a stale count.
 // A kernel's SolveArgs read afresh from its kernarg segment -- only in kernels whose one argument is
-// a SolveArgs<float> (gpad_panel2_kernel, gpad_duo_kernel).  The pointer passes an empty asm, so the
+// a SolveArgs<float> (gpad_panel2_kernel, gpad_duo_kernel) or begins with one (gpad_loop_kernel's
+// LoopArgs).  The pointer passes an empty asm, so the
 // fields loaded through it at a rare site (refills, results out, park, survivor lists, a panel's
 // state loads) are not kept live in SGPRs across the solve loop: loaded once at the top, the dozen
 // row-array pointers spilled to VGPR lanes and were reloaded (v_readlane) around every step.

@@ -306,7 +306,13 @@ class GpadSolver:
         """gpad.m:79-95 on the device: ``steps`` receding-horizon MPC steps for every instance.
         x [batch][nx] is advanced in place; xs [steps][batch][nx] / us [steps][batch][nu]
         receive the trajectories when given; ``iters`` / ``codes`` (host int32 [steps*batch]) the
-        counts and termination codes."""
+        counts and termination codes.
+
+        The steps run in lockstep by default.  After ``set_option("loop_async", 1)`` the whole loop
+        is one launch in which an instance starts its next step as soon as its own solve ends
+        (``kernel == "loop"`` in the stats); it applies to f32 setups with shared matrices, no flat
+        setup and no Hessian, n, m <= 208, kernel AUTO or RESIDENT, N >= 1, nx <= 64 and
+        nu <= min(n, 64), and any other call runs the lockstep loop.  Results are bit-identical."""
         st = Stats()
         for arr, field in ((iters, "iters"), (codes, "codes")):
             if arr is not None:

@@ -68,6 +68,8 @@ extern "C" {
 #define GPAD_KERNEL_FLAT 4     /* reported only: the flat battery path bound by gpad_setup_flat      */
 /* 5: the opt-in condensed operator (not the reference's arithmetic), removed in 0.4; dims.kernel = 5
  * returns GPAD_ERR_INVALID */
+#define GPAD_KERNEL_LOOP 6     /* reported only: gpad_closed_loop in one launch (GPAD_OPT_LOOP_ASYNC);
+                                * dims.kernel = 6 returns GPAD_ERR_INVALID                           */
 
 typedef struct gpad_dims {
     int n;           /* primal variables, n = n_u * N                                   */
@@ -239,7 +241,17 @@ int gpad_run_state(gpad_handle_t h, const void* x, void* z0, void* y0, int N, do
  * xs [steps][batch][nx], us [steps][batch][nu]: optional trajectories (NULL to skip).
  * st->iters and st->codes, when given, receive [steps][batch] iteration counts and termination
  * codes (size both arrays steps * batch); the other stats aggregate over every (step, instance);
- * kernel_ms times the whole loop. */
+ * kernel_ms times the whole loop.
+ *
+ * By default the steps run in lockstep: per step the affine maps, the solve of the whole batch and
+ * the plant update are enqueued one after the other, so with tol > 0 every step lasts as long as its
+ * slowest instance.  With GPAD_OPT_LOOP_ASYNC = 1 the loop is one launch (stats kernel =
+ * GPAD_KERNEL_LOOP) in which an instance whose solve terminates applies its own plant update and
+ * affine maps and starts its next step at once, no instance waiting for another.  That path is
+ * taken for f32, shared matrices bound by gpad_setup (no flat setup, no Hessian), n, m <= 208,
+ * dims.kernel AUTO or RESIDENT, N >= 1, nx <= 64 and nu <= min(n, 64); any other call runs the
+ * lockstep loop as if the option were unset.  Results are identical either way: x, z, y, xs, us and
+ * every stat (per-step counts and codes included) are bit for bit those of the lockstep loop. */
 int gpad_closed_loop(gpad_handle_t h, void* x, void* z, void* y, int steps, int N, double tol, int warm,
                      void* xs, void* us, gpad_stats_t* st);
 
@@ -419,6 +431,9 @@ int gpad_schedule(int N, int kind, double* theta, double* beta);
 #define GPAD_OPT_P64_REFILL 19     /* 1: f64 panel solves with tol > 0, N a multiple of check_every and
                                     * more panels than workgroups refill a finished column with the
                                     * next instance (default); 0: each panel runs to its slowest column */
+#define GPAD_OPT_LOOP_ASYNC 22     /* 1: gpad_closed_loop runs the whole loop in one launch in which
+                                    * every instance steps on its own (see gpad_closed_loop) where that
+                                    * kernel applies, else the lockstep loop; 0 (default): lockstep */
 int gpad_set_option(gpad_handle_t h, int option, int value);
 
 /* Synchronise the handle's stream (for callers using device memory + async runs). */

@@ -1,0 +1,112 @@
+"""A/B of the closed loop (gpad_closed_loop): the lockstep loop against the asynchronous kernel
+(GPAD_OPT_LOOP_ASYNC, csrc/gpad_loop.hip) on two handles over the same seeded states, all in device
+tensors.  C1 plant (battery_plant(4, 10): n = 40, m = 180), 20 MPC steps, batches 1 ... 8192, three
+modes: eps cold / eps warm (tol 1e-4, N 3000) and fixed N = 100.
+
+  python tools/loop_ab.py [--rounds 3] [--steps 20] [--batches 1 64 256 512 2048 8192]
+
+Per batch and mode the two variants' x, z, y, xs, us and per-step iteration counts are compared first
+(that run is also each variant's warm-up); a mismatch aborts the batch.  Then `rounds` rounds
+alternate the variants.  One JSON line per case: kernel_ms (events around the whole loop) and host
+wall time around a final sync, per round; MPC steps/s of both variants from the median kernel_ms;
+their ratio; and `faster`, which names a variant only when its slowest round beats the other's
+fastest (a difference inside the spread of the rounds is reported as "none").
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "gpu-dualgradient-mpc_amd")]
+
+MODES = {"eps_cold": dict(N=3000, tol=1e-4, warm=False), "eps_warm": dict(N=3000, tol=1e-4, warm=True),
+         "fixed_100": dict(N=100, tol=0.0, warm=False)}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--batches", type=int, nargs="*", default=[1, 64, 256, 512, 2048, 8192])
+    args = ap.parse_args()
+    rounds = max(3, args.rounds)
+    import torch
+
+    import gpad_mpc
+    from gpad_mpc import problems
+    dev = torch.device("cuda:0")
+    qp, pl = problems.battery_plant(4, 10)
+    n, m, nx, nu, steps = qp.n, qp.m, pl.nx, pl.nu, args.steps
+    t32 = lambda a: torch.from_numpy(np.ascontiguousarray(np.asarray(a, np.float64).astype(np.float32))).to(dev)  # noqa: E731
+    dML, dG, dPM, dPg, dg0, dA, dB = (t32(a) for a in (qp.ML, qp.G, pl.PM, pl.Pg, pl.g0, pl.A, pl.B))
+    print(json.dumps({"plant": "battery_plant(4, 10)", "n": n, "m": m, "steps": steps, "rounds": rounds,
+                      "device": torch.cuda.get_device_name(0)}))
+    for B in args.batches:
+        X0 = torch.from_numpy((np.random.default_rng(B).random((B, nx)) - 0.5).astype(np.float32)).to(dev)
+        var = {}
+        for name in ("lockstep", "async"):
+            s = gpad_mpc.GpadSolver(0)
+            s.setup(dML, dG, float(np.float32(qp.L)), n=n, m=m, batch=B, shared=True)
+            s.setup_plant(dPM, dPg, g0=dg0, A=dA, B=dB)
+            s.set_option("loop_async", int(name == "async"))
+            buf = dict(x=torch.empty(B, nx, device=dev), z=torch.empty(B, n, device=dev),
+                       y=torch.empty(B, m, device=dev), xs=torch.empty(steps, B, nx, device=dev),
+                       us=torch.empty(steps, B, nu, device=dev))
+            var[name] = (s, buf)
+
+        def enqueue(name, mode, **kw):
+            s, b = var[name]
+            b["x"].copy_(X0)
+            b["z"].zero_()
+            b["y"].zero_()
+            torch.cuda.synchronize()
+            return s.closed_loop(b["x"], b["z"], b["y"], steps, mode["N"], mode["tol"], warm=mode["warm"],
+                                 xs=b["xs"], us=b["us"], **kw)
+
+        for mname, mode in MODES.items():
+            its, kern = {}, {}
+            for name in var:  # the output check, and each variant's warm-up
+                its[name] = np.zeros(steps * B, np.int32)
+                kern[name] = enqueue(name, mode, iters=its[name])["kernel"]
+            bad = [k for k in ("x", "z", "y", "xs", "us")
+                   if not torch.equal(var["lockstep"][1][k].view(torch.int32), var["async"][1][k].view(torch.int32))]
+            if not np.array_equal(its["lockstep"], its["async"]):
+                bad.append("iters")
+            if bad or kern["async"] != "loop" or kern["lockstep"] == "loop":
+                print(json.dumps({"batch": B, "mode": mname, "error": "outputs differ" if bad else "wrong kernel",
+                                  "differ": bad, "kernels": kern}))
+                break
+            ms = {k: [] for k in var}
+            wall = {k: [] for k in var}
+            for _ in range(rounds):
+                for name in var:
+                    s = var[name][0]
+                    t0 = time.perf_counter()
+                    enqueue(name, mode, stats=False)
+                    s.sync()
+                    wall[name].append((time.perf_counter() - t0) * 1e3)
+                    ms[name].append(s.last_stats()["kernel_ms"])
+            med = {k: float(np.median(v)) for k, v in ms.items()}
+            rate = {k: B * steps / (med[k] / 1e3) for k in var}
+            faster = ("async" if max(ms["async"]) < min(ms["lockstep"]) else
+                      "lockstep" if min(ms["async"]) > max(ms["lockstep"]) else "none")
+            print(json.dumps({
+                "batch": B, "mode": mname, "lockstep_kernel": kern["lockstep"],
+                "mean_iters_per_solve": round(float(its["async"].mean()), 1),
+                "max_iters_per_solve": int(its["async"].max()),
+                "kernel_ms": {k: [round(x, 4) for x in v] for k, v in ms.items()},
+                "wall_ms": {k: [round(x, 4) for x in v] for k, v in wall.items()},
+                "mpc_steps_per_s": {k: round(v, 1) for k, v in rate.items()},
+                "async_over_lockstep": round(rate["async"] / rate["lockstep"], 3), "faster": faster}), flush=True)
+        for s, _ in var.values():
+            s.close()
+
+
+if __name__ == "__main__":
+    main()
