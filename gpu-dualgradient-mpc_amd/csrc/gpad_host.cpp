@@ -183,7 +183,9 @@ struct gpad_handle_s {
     // plant binding (gpad_setup_plant): affine state maps and dynamics, device copies
     int nx = 0, nu = 0;
     bool plant_ready = false, plant_dyn = false;
-    DevBuf plant;                       // [PM n*nx | M0 n | Pg m*nx | g0 m | A nx*nx | B nx*nu]
+    DevBuf plant;                       // [PM n*nx | M0 n | Pg m*nx | g0 m | A nx*nx | B nx*nu], each
+                                        // array plant_batch times over when per instance
+    int plant_batch = 0;                // 0: one plant for the batch; else the dims.batch it was bound for
     bool has_M0 = false, has_g0 = false;
     int plant_n = 0, plant_m = 0, plant_dtype = -1;
     DevBuf state;                       // per-state workspaces (M(x), g(x), x ping-pong, ...)
@@ -246,7 +248,7 @@ static int status_error(gpad_handle_t h, const RunStatus& rs) {
 
 extern "C" {
 
-const char* gpad_version(void) { return "gpad-mi355x 0.5 (gfx950)"; }
+const char* gpad_version(void) { return "gpad-mi355x 0.6 (gfx950)"; }
 
 int gpad_device_count(void) {
     return gpad::abi_guard("gpad_device_count", [&]() -> int {
@@ -1275,15 +1277,16 @@ namespace {
 struct PlantOffsets {
     size_t PM, M0, Pg, g0, A, B, total;
 };
-PlantOffsets plant_offsets(int n, int m, int nx, int nu) {
+// element offsets of the maps in Handle::plant, each array holding `copies` consecutive instances
+PlantOffsets plant_offsets(int n, int m, int nx, int nu, size_t copies) {
     PlantOffsets o{};
     o.PM = 0;
-    o.M0 = o.PM + (size_t)n * nx;
-    o.Pg = o.M0 + (size_t)n;
-    o.g0 = o.Pg + (size_t)m * nx;
-    o.A = o.g0 + (size_t)m;
-    o.B = o.A + (size_t)nx * nx;
-    o.total = o.B + (size_t)nx * nu;
+    o.M0 = o.PM + copies * n * nx;
+    o.Pg = o.M0 + copies * n;
+    o.g0 = o.Pg + copies * m * nx;
+    o.A = o.g0 + copies * m;
+    o.B = o.A + copies * nx * nx;
+    o.total = o.B + copies * nx * nu;
     return o;
 }
 }  // namespace
@@ -1354,44 +1357,59 @@ extern "C" int gpad_precompute(gpad_handle_t h, int n, int m, int batch, int sha
     });
 }
 
+// gpad_setup_plant (copies == 0: one plant) and gpad_setup_plant_batch (copies == dims.batch)
+static int setup_plant_impl(gpad_handle_t h, int nx, int nu, const void* PM, const void* M0, const void* Pg,
+                            const void* g0, const void* A, const void* B, bool per_instance, const char* fn) {
+    const std::string where(fn);
+    if (!h) return fail(GPAD_ERR_INVALID, where + ": null handle");
+    if (!h->ready) return fail(GPAD_ERR_NOT_SETUP, where + ": call gpad_setup first");
+    if (nx <= 0 || nu < 0 || !PM || !Pg) return fail(GPAD_ERR_INVALID, where + ": bad arguments");
+    if ((A == nullptr) != (B == nullptr) || (A && nu == 0))
+        return fail(GPAD_ERR_INVALID, where + ": give A and B together (nu >= 1)");
+    if (nu > h->dims.n) return fail(GPAD_ERR_INVALID, where + ": nu > n");
+    HIP_TRY(hipSetDevice(h->device));
+    const int n = h->dims.n, m = h->dims.m;
+    const size_t es = esize(h->dims.dtype), copies = per_instance ? (size_t)h->dims.batch : 1;
+    const PlantOffsets o = plant_offsets(n, m, nx, nu, copies);
+    int rc;
+    if ((rc = h->plant.ensure(es * o.total))) return rc;
+    char* base = (char*)h->plant.p;
+    const hipMemcpyKind kind = h->dims.memory == GPAD_MEM_HOST ? hipMemcpyHostToDevice
+                                                                : hipMemcpyDeviceToDevice;
+    auto put = [&](size_t off, const void* src, size_t elems) -> int {
+        if (!src || elems == 0) return GPAD_OK;
+        HIP_TRY(hipMemcpyAsync(base + es * off, src, es * copies * elems, kind, h->stream));
+        return GPAD_OK;
+    };
+    if ((rc = put(o.PM, PM, (size_t)n * nx)) || (rc = put(o.M0, M0, n)) ||
+        (rc = put(o.Pg, Pg, (size_t)m * nx)) || (rc = put(o.g0, g0, m)) ||
+        (rc = put(o.A, A, (size_t)nx * nx)) || (rc = put(o.B, B, (size_t)nx * nu)))
+        return rc;
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    h->nx = nx;
+    h->nu = nu;
+    h->has_M0 = M0 != nullptr;
+    h->has_g0 = g0 != nullptr;
+    h->plant_dyn = A != nullptr;
+    h->plant_ready = true;
+    h->plant_batch = per_instance ? h->dims.batch : 0;
+    h->plant_n = n;
+    h->plant_m = m;
+    h->plant_dtype = h->dims.dtype;
+    return GPAD_OK;
+}
+
 extern "C" int gpad_setup_plant(gpad_handle_t h, int nx, int nu, const void* PM, const void* M0,
                                 const void* Pg, const void* g0, const void* A, const void* B) {
     return gpad::abi_guard("gpad_setup_plant", [&]() -> int {
-        if (!h) return fail(GPAD_ERR_INVALID, "gpad_setup_plant: null handle");
-        if (!h->ready) return fail(GPAD_ERR_NOT_SETUP, "gpad_setup_plant: call gpad_setup first");
-        if (nx <= 0 || nu < 0 || !PM || !Pg) return fail(GPAD_ERR_INVALID, "gpad_setup_plant: bad arguments");
-        if ((A == nullptr) != (B == nullptr) || (A && nu == 0))
-            return fail(GPAD_ERR_INVALID, "gpad_setup_plant: give A and B together (nu >= 1)");
-        if (nu > h->dims.n) return fail(GPAD_ERR_INVALID, "gpad_setup_plant: nu > n");
-        HIP_TRY(hipSetDevice(h->device));
-        const int n = h->dims.n, m = h->dims.m;
-        const size_t es = esize(h->dims.dtype);
-        const PlantOffsets o = plant_offsets(n, m, nx, nu);
-        int rc;
-        if ((rc = h->plant.ensure(es * o.total))) return rc;
-        char* base = (char*)h->plant.p;
-        const hipMemcpyKind kind = h->dims.memory == GPAD_MEM_HOST ? hipMemcpyHostToDevice
-                                                                    : hipMemcpyDeviceToDevice;
-        auto put = [&](size_t off, const void* src, size_t elems) -> int {
-            if (!src || elems == 0) return GPAD_OK;
-            HIP_TRY(hipMemcpyAsync(base + es * off, src, es * elems, kind, h->stream));
-            return GPAD_OK;
-        };
-        if ((rc = put(o.PM, PM, (size_t)n * nx)) || (rc = put(o.M0, M0, n)) ||
-            (rc = put(o.Pg, Pg, (size_t)m * nx)) || (rc = put(o.g0, g0, m)) ||
-            (rc = put(o.A, A, (size_t)nx * nx)) || (rc = put(o.B, B, (size_t)nx * nu)))
-            return rc;
-        HIP_TRY(hipStreamSynchronize(h->stream));
-        h->nx = nx;
-        h->nu = nu;
-        h->has_M0 = M0 != nullptr;
-        h->has_g0 = g0 != nullptr;
-        h->plant_dyn = A != nullptr;
-        h->plant_ready = true;
-        h->plant_n = n;
-        h->plant_m = m;
-        h->plant_dtype = h->dims.dtype;
-        return GPAD_OK;
+        return setup_plant_impl(h, nx, nu, PM, M0, Pg, g0, A, B, false, "gpad_setup_plant");
+    });
+}
+
+extern "C" int gpad_setup_plant_batch(gpad_handle_t h, int nx, int nu, const void* PM, const void* M0,
+                                      const void* Pg, const void* g0, const void* A, const void* B) {
+    return gpad::abi_guard("gpad_setup_plant_batch", [&]() -> int {
+        return setup_plant_impl(h, nx, nu, PM, M0, Pg, g0, A, B, true, "gpad_setup_plant_batch");
     });
 }
 
@@ -1431,7 +1449,8 @@ static int state_typed(gpad_handle_t h, T* x, T* z, T* y, int steps, int N, doub
         HIP_TRY(hipMemcpyAsync(dz, z, sizeof(T) * zn, hipMemcpyHostToDevice, h->stream));
         HIP_TRY(hipMemcpyAsync(dy, y, sizeof(T) * yn, hipMemcpyHostToDevice, h->stream));
     }
-    const PlantOffsets o = plant_offsets(n, m, nx, nu);
+    const bool per_plant = h->plant_batch != 0;  // per-instance maps (gpad_setup_plant_batch)
+    const PlantOffsets o = plant_offsets(n, m, nx, nu, per_plant ? (size_t)batch : 1);
     const T* P = (const T*)h->plant.p;
     int* counters = (int*)h->counters.p;
     int kernel = 0;
@@ -1443,7 +1462,8 @@ static int state_typed(gpad_handle_t h, T* x, T* z, T* y, int steps, int N, doub
     if constexpr (sizeof(T) == sizeof(float)) {
         // GPAD_OPT_LOOP_ASYNC: the whole loop in one launch of gpad_loop_kernel, every pack stepping on
         // its own (gpad_loop.hip).  Anything it does not cover runs the lockstep loop below.
-        async = loop && h->tune.loop_async && d.shared && !h->flat && !h->hess_ok && N >= 1 &&
+        // (per-instance matrices: its solo variant, where the resident kernel holds the shape)
+        async = loop && h->tune.loop_async && !h->flat && !h->hess_ok && N >= 1 &&
                 (d.kernel == GPAD_KERNEL_AUTO || d.kernel == GPAD_KERNEL_RESIDENT) &&
                 gpad::loop_supported(n, m, nx, nu);
         if (async) {
@@ -1452,6 +1472,8 @@ static int state_typed(gpad_handle_t h, T* x, T* z, T* y, int steps, int N, doub
             gpad::SolveArgs<float>& a = la.s;
             a.MGt = (const float*)h->MGt.p;
             a.GLt = (const float*)h->GLt.p;
+            a.strideA = d.shared ? 0 : (long long)m * h->ldn;
+            a.strideB = d.shared ? 0 : (long long)n * h->ldm;
             a.gscale = -1.0 / h->L;
             a.z = dz;
             a.y = dy;
@@ -1490,7 +1512,8 @@ static int state_typed(gpad_handle_t h, T* x, T* z, T* y, int steps, int N, doub
             la.nu = nu;
             la.steps = nsolve;
             la.warm = warm ? 1 : 0;
-            int grid = std::min(batch, h->num_cus);
+            la.per_plant = per_plant ? 1 : 0;
+            int grid = std::min(batch, h->num_cus * gpad::loop_blocks_per_cu(la));
             if (h->tune.duo_max_grid > 0 && h->tune.duo_max_grid < grid) grid = h->tune.duo_max_grid;
             grid = std::min(grid, (int)gpad::kAbsmaxMaxBlocks);
             HIP_TRY(hipMemsetAsync(a.qctr, 0, sizeof(int), h->stream));
@@ -1507,7 +1530,7 @@ static int state_typed(gpad_handle_t h, T* x, T* z, T* y, int steps, int N, doub
     if (!async) HIP_TRY(hipEventRecord(h->ev0, h->stream));
     for (int t = 0; t < nsolve && !async; ++t) {
         HIP_TRY(gpad::launch_affine2<T>(P + o.PM, h->has_M0 ? P + o.M0 : nullptr, n, Mx, P + o.Pg,
-                                        h->has_g0 ? P + o.g0 : nullptr, m, gx, xc, nx, batch, h->stream));
+                                        h->has_g0 ? P + o.g0 : nullptr, m, gx, xc, nx, batch, per_plant, h->stream));
         if (loop && !warm) {  // acceldualgrad.m:16-17: every MPC step starts from z = y = 0
             HIP_TRY(hipMemsetAsync(dz, 0, sizeof(T) * zn, h->stream));
             HIP_TRY(hipMemsetAsync(dy, 0, sizeof(T) * yn, h->stream));
@@ -1524,7 +1547,7 @@ static int state_typed(gpad_handle_t h, T* x, T* z, T* y, int steps, int N, doub
         if (loop) {  // gpad.m:91-94: u = z*(1:nu); x <- A x + B u
             HIP_TRY(gpad::launch_plant_step<T>(P + o.A, P + o.B, xc, dz, n, xnext, nx, nu, batch,
                                                dxs ? dxs + (size_t)t * xn : nullptr,
-                                               dus ? dus + (size_t)t * batch * nu : nullptr, h->stream));
+                                               dus ? dus + (size_t)t * batch * nu : nullptr, per_plant, h->stream));
             std::swap(xc, xnext);
         }
     }
@@ -1550,7 +1573,7 @@ static int state_impl(gpad_handle_t h, void* x, void* z, void* y, int steps, int
     if (!h) return fail(GPAD_ERR_INVALID, std::string(where) + ": null handle");
     if (!h->ready) return fail(GPAD_ERR_NOT_SETUP, std::string(where) + ": call gpad_setup first");
     if (!h->plant_ready || h->plant_n != h->dims.n || h->plant_m != h->dims.m ||
-        h->plant_dtype != h->dims.dtype)
+        h->plant_dtype != h->dims.dtype || (h->plant_batch && h->plant_batch != h->dims.batch))
         return fail(GPAD_ERR_NOT_SETUP, std::string(where) + ": call gpad_setup_plant after gpad_setup");
     if (steps > 0 && !h->plant_dyn)
         return fail(GPAD_ERR_NOT_SETUP, std::string(where) + ": plant bound without A, B");

@@ -140,17 +140,19 @@ hipError_t launch_resident(const SolveArgs<float>& a, hipStream_t s, bool* suppo
 // zeroed a.qctr.  Persistent grid of `grid` workgroups (one per CU).
 hipError_t launch_duo(const SolveArgs<float>& a, int grid, hipStream_t s);
 bool resident_supported(int n, int m);
-// Asynchronous closed loop (gpad_loop.hip, GPAD_OPT_LOOP_ASYNC): the duo kernel's ping-pong over a
+// Asynchronous closed loop (gpad_loop.h / gpad_loop*.hip, GPAD_OPT_LOOP_ASYNC): the duo kernel's ping-pong over a
 // queue of closed-loop packs -- a slot whose solve ends applies the plant update and the two affine
 // maps in place and restarts the same pack at its next MPC step; one launch for the whole loop.
-// s: the solve (shared f32 matrices; gP, g, idx_in, count_in, gmax_part unused; z, y: in when warm,
+// s: the solve (f32 matrices; gP, g, idx_in, count_in, gmax_part unused; z, y: in when warm,
 // out after the last step; iters / conv: the counters of all steps, [steps][iters[batch] |
 // conv[batch]]; qctr zeroed).  The SolveArgs comes first, so kargs() reads it in this kernel too.
+// Shared matrices (strideA == strideB == 0) run the two-slot kernel; per-instance matrices run
+// gpad_loop_fleet_kernel, one slot per workgroup whose register rows are reloaded per pack.
 constexpr int kLoopMaxState = 64;  // nx, nu <= this (the state and input live in one LDS row each)
 struct LoopArgs {
     SolveArgs<float> s;
-    const float* PM;       // [n][nx]   M(x) = M0 + PM x
-    const float* M0;       // [n] or null
+    const float* PM;       // [n][nx]   M(x) = M0 + PM x        (per_plant: [batch] of each map,
+    const float* M0;       // [n] or null                        pack b reads copy b)
     const float* Pg;       // [m][nx]   g(x) = g0 + Pg x
     const float* g0;       // [m] or null
     const float* A;        // [nx][nx]  x+ = A x + B z*[0:nu]
@@ -162,8 +164,12 @@ struct LoopArgs {
     double* gmax;          // [kAbsmaxMaxBlocks] per-workgroup max |g| over every (step, pack), the
                            // unused slots zeroed; null: not wanted
     int nx, nu, steps, warm;
+    int per_plant;         // 1: the six maps are per pack (gpad_setup_plant_batch), 0: one plant
 };
 bool loop_supported(int n, int m, int nx, int nu);
+// workgroups of a's kernel that fit one CU by the runtime's occupancy figure, clamped to [1, 2]
+// (always 1 for the two-slot kernel, whose grid is one workgroup per CU)
+int loop_blocks_per_cu(const LoopArgs& a);
 // persistent grid of `grid` <= min(batch, kAbsmaxMaxBlocks) workgroups
 hipError_t launch_loop(const LoopArgs& a, int grid, hipStream_t s);
 hipError_t launch_panel(const SolveArgs<float>& a, hipStream_t s, bool* supported);
@@ -251,14 +257,15 @@ template <typename T>
 hipError_t launch_pack_kmajor(const T* in, T* out, int rows, int cols, int ld, double scale,
                               int batch, long long in_stride, long long out_stride, hipStream_t s);
 
-// gpad_plant.hip: out1 = c1 + P1 x (rows1), out2 = c2 + P2 x (rows2) per instance; c may be null
+// gpad_plant.hip: out1 = c1 + P1 x (rows1), out2 = c2 + P2 x (rows2) per instance; c may be null.
+// per_instance: every map holds `batch` consecutive copies, instance b reads its own (else one map)
 template <typename T>
 hipError_t launch_affine2(const T* P1, const T* c1, int rows1, T* out1, const T* P2, const T* c2,
-                          int rows2, T* out2, const T* x, int nx, int batch, hipStream_t s);
+                          int rows2, T* out2, const T* x, int nx, int batch, bool per_instance, hipStream_t s);
 // xn = A x + B z[:, 0:nu]; xs/us (nullable) receive x and z[:, 0:nu]
 template <typename T>
 hipError_t launch_plant_step(const T* A, const T* B, const T* x, const T* z, long long ldz, T* xn, int nx,
-                             int nu, int batch, T* xs, T* us, hipStream_t s);
+                             int nu, int batch, T* xs, T* us, bool per_instance, hipStream_t s);
 
 // gpad_flat.hip (flat battery path; MGt = flat -ML [Nh][m], GLt = flat G_L t-major [Nh][m])
 hipError_t launch_flat(const SolveArgs<float>& a, hipStream_t s);

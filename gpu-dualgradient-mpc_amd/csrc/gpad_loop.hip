@@ -1,381 +1,39 @@
-// gpad_loop.hip -- the asynchronous closed-loop kernel: gpad_duo_kernel's two-slot ping-pong over a
-// queue of closed-loop PACKS instead of single solves (GPAD_OPT_LOOP_ASYNC, gpad_closed_loop).
-#include <hip/hip_runtime.h>
-
-#include <cmath>
-
-#include "gpad_chain.h"
-#include "gpad_duo.h"
-#include "gpad_internal.h"
+// gpad_loop.hip -- the asynchronous closed loop (gpad_loop.h): the shared-plant instantiations of the
+// two-slot kernel and the launcher.
+#include "gpad_loop.h"
 
 namespace gpad {
 
-// =========================================================================================
-// gpad_loop_kernel: one launch for a whole T-step closed loop, every pack stepping on its own.
-// =========================================================================================
-// The lockstep loop (gpad_host.cpp state_typed) enqueues per MPC step the two affine maps, the
-// solve, the |g| maxima and the plant update, and with a tolerance every step lasts as long as its
-// slowest pack.  A pack's next step depends on its own z* only (gpad.m:91-93), so here a slot holds
-// (pack b, MPC step t, state x_t) and, when its solve terminates, advances the SAME pack: the plant
-// update and the affine maps g_P(x), g(x) are evaluated in place by the workgroup (x in LDS, the P,
-// A, B rows through uniform-base buffer loads), and the slot restarts at iteration 0 of step t + 1.
-// Only after its last step is the slot refilled from the queue, exactly as the duo kernel claims
-// instances.  No workgroup waits for another: every loop is bounded by N, by `steps` and by the
-// finite queue.
-//
-// Per iteration the arithmetic is gpad_duo.h's half-steps and test, i.e. the duo / resident
-// kernels'; the step boundary restates affine2_kernel and plant_step_kernel (gpad_plant.hip) in
-// their order with explicit fmas.  Results, counts and codes are therefore bit-identical to the
-// lockstep loop.
-struct LoopSlot : DuoSlot {
-    int t;  // MPC step of the pack in this slot (uniform)
-};
-
-typedef const __attribute__((address_space(4))) LoopArgs LoopKernArgs;
-// the kernel's LoopArgs read afresh from its kernarg segment (as kargs(): nothing kept live in
-// SGPRs across the solve loop); its first member is the SolveArgs the shared half-steps take
-__device__ __forceinline__ LoopKernArgs& largs() {
-    LoopKernArgs* p = (LoopKernArgs*)__builtin_amdgcn_kernarg_segment_ptr();
-    asm volatile("" : "+s"(p));
-    return *p;
+// the instantiation for a: the two-slot kernel for shared matrices (with one plant or per-pack maps),
+// the fleet kernel for per-pack matrices
+static LoopFn loop_fn(const LoopArgs& a) {
+    const SolveArgs<float>& s = a.s;
+    const int ka = res_bucket(s.m), kb = res_bucket(s.n);
+    if (s.strideA || s.strideB) return loop_fn_fleet(ka, kb);
+    return a.per_plant ? loop_fn_per_plant(ka, kb) : loop_fn_of<kLoopShared>(ka, kb);
 }
-
-// LDS of the step boundaries
-struct LoopLds {
-    float x[2][2][64];   // per slot: x_t at [t & 1], x_{t+1} written to the other half
-    float u[64];         // u = z*[0:nu] of the slot at its boundary
-    float gm[kResidentMaxThreads];  // per lane: NaN-keeping max |g| of every g row it formed
-};
-
-// c + P x for this lane's row of a [rows][nx] map (affine2_kernel's order): acc = c0[row] (0 if
-// absent), then fma(P[row][k], x[k], acc) for ascending k
-__device__ __forceinline__ float loop_affine(const float* P, const float* c0, int rows, int row, int nx,
-                                             const float* x_l) {
-    float acc = c0 ? row_ld(c0, 0, rows, 4 * row) : 0.0f;
-    const int o4 = 4 * row * nx;
-#pragma unroll 1
-    for (int k = 0; k < nx; ++k) acc = __builtin_fmaf(row_ld(P, 0, rows * nx, o4 + 4 * k), x_l[k], acc);
-    return acc;
-}
-
-// Start the solve of slot s at state x_l (barrier-published by the caller) from (z_{-1}, y_0) = v0
-// of this lane's row: g_P(x) / p_D(x) to the slot's LDS rows, then the fresh path of duo_refill.
-// Uniform, contains barriers.
-template <int KB, int K>
-__device__ __forceinline__ void loop_start(const SolveArgs<float>& a, const DuoCtx& c, LoopSlot& s, float v0,
-                                           const float* x_l, float* w_l, float* gp_l, float* pd_l, float* z_l,
-                                           float* gm_l, const float (&r)[K]) {
-    s.vs = 0;
-    s.kc = c.Kc;
-    s.need8d = false;
-    s.th = sched(a.theta, 0);
-    s.bn = sched(a.beta, 1);
-    s.x0 = s.x1 = s.x2 = 0.0f;
-    if (c.live) {
-        LoopKernArgs& A = largs();
-        if (c.isA) {
-            gp_l[c.row] = loop_affine(A.PM, A.M0, c.n, c.row, A.nx, x_l);
-            s.x0 = v0;
-            if (c.use_tol) z_l[c.row] = v0;
-        } else {
-            const float gv = loop_affine(A.Pg, A.g0, c.m, c.row, A.nx, x_l);
-            gm_l[c.tid] = absmax_nan(gm_l[c.tid], gv);
-            pd_l[c.row] = (float)(A.s.gscale * (double)gv);
-            s.x0 = v0;
-            s.x1 = __builtin_fmaf(A.s.beta[0], v0 - v0, v0);
-            w_l[c.row] = s.x1;
-        }
-    }
-    __syncthreads();
-    if (c.use_tol) {  // u = G_L z_{-1}, then the 8c recursion
-        if (!c.isA) {
-            const float us = chain_regs<KB, K>(r, z_l);
-            s.x2 = c.live ? us : 0.0f;
-        }
-        __syncthreads();  // z_l free again
-    }
-}
-
-// slot s takes pack p at its step 0 (empty if p >= count): x from the input states, (z, y) from the
-// caller's arrays when warm, else zero.  Uniform, contains barriers.
-template <int KB, int K>
-__device__ __forceinline__ void loop_refill(const SolveArgs<float>& a, const DuoCtx& c, LoopSlot& s, int p,
-                                            float* x_s, float* w_l, float* gp_l, float* pd_l, float* z_l,
-                                            float* gm_l, const float (&r)[K]) {
-    s.pos = __builtin_amdgcn_readfirstlane(p);
-    s.t = 0;
-    const bool has = p < c.count;
-    float v0 = 0.0f;
-    if (has) {
-        LoopKernArgs& A = largs();
-        if (c.tid < A.nx) x_s[c.tid] = row_ld(A.x_in, (size_t)p, A.nx, 4 * c.tid);
-        if (A.warm && c.live)
-            v0 = c.isA ? row_ld(A.s.z, (size_t)p, c.n, 4 * c.row) : row_ld(A.s.y, (size_t)p, c.m, 4 * c.row);
-    }
-    __syncthreads();  // x_s (and the claim cell, loop_claim) published
-    if (has) {
-        loop_start<KB, K>(a, c, s, v0, x_s, w_l, gp_l, pd_l, z_l, gm_l, r);
-    } else {
-        s.vs = 0;
-        s.kc = c.Kc;
-        s.need8d = false;
-        s.th = s.bn = 0.0f;
-        s.x0 = s.x1 = s.x2 = 0.0f;
-    }
-}
-
-// consume the pre-claimed position of slot s, claim its next one (claim_l: this slot's cell)
-template <int KB, int K>
-__device__ __forceinline__ void loop_claim(const SolveArgs<float>& a, const DuoCtx& c, LoopSlot& s, int* claim_l,
-                                           float* x_s, float* w_l, float* gp_l, float* pd_l, float* z_l,
-                                           float* gm_l, const float (&r)[K]) {
-    const int p = s.nextp;
-    if (c.tid == 0 && p < c.count) *claim_l = c.claim_base + atomicAdd(a.qctr, 1);
-    loop_refill<KB, K>(a, c, s, p, x_s, w_l, gp_l, pd_l, z_l, gm_l, r);  // (its barrier publishes *claim_l)
-    s.nextp = p < c.count ? __builtin_amdgcn_readfirstlane(*claim_l) : c.count;
-}
-
-// after the barrier that closes slot sb's 8d half (every wave): the shared test, and when the solve
-// terminates the step boundary -- record the step, x_{t+1} = A x_t + B u, then either the pack's
-// next step in place or, after its last step, the results out and the next pack from the queue.
-// x_b: this slot's two x vectors; u_l: boundary scratch.
-template <int KB, int K, bool PRE = false>
-__device__ __forceinline__ void loop_post_b(const SolveArgs<float>& a, const DuoCtx& c, LoopSlot& sb, bool chk,
-                                            float* wb_l, float* gpb_l, float* pdb_l, CheckSlot* slots_b,
-                                            CheckSlot* vslots, int* claim_b, float* z_l, float* x_b, float* u_l,
-                                            float* gm_l, const float (&r)[K], float th_n = 0.0f,
-                                            float bn_n = 0.0f) {
-    const int done = duo_test_b<KB, K, PRE>(a, c, sb, chk, pdb_l, slots_b, vslots, z_l, r, th_n, bn_n);
-    const int v = sb.vs;
-    if (done || v >= c.N) {
-        LoopKernArgs& A = largs();
-        const int t = sb.t, nx = A.nx, nu = A.nu;
-        const size_t b = (size_t)sb.pos;
-        const size_t tb = (size_t)t * (size_t)c.count + b;  // (step, pack) row of xs / us
-        const bool last = t + 1 == A.steps;
-        // z* (-ML lanes; (B) certifies zhat) or y* (G/L lanes) of this lane's row
-        const float star = c.isA ? (done == 2 ? sb.x1 : sb.x0) : sb.x0;
-        const float* xc = x_b + 64 * (t & 1);
-        float* xn = x_b + 64 * ((t + 1) & 1);
-        if (c.tid == 0) {  // the counters of step t: [iters[batch] | conv[batch]]
-            A.s.iters[(size_t)(2 * t) * c.count + b] = v;
-            A.s.conv[(size_t)(2 * t + 1) * c.count + b] = done;
-        }
-        if (c.isA && c.row < nu) {
-            u_l[c.row] = star;
-            if (A.us) row_st(A.us, tb, nu, 4 * c.row, star);
-        }
-        if (c.tid < nx && A.xs) row_st(A.xs, tb, nx, 4 * c.tid, xc[c.tid]);
-        __syncthreads();  // u_l published
-        if (c.tid < nx) {  // plant_step_kernel's order: A x first, then B u, one fma chain
-            float acc = 0.0f;
-            const int oa = 4 * c.tid * nx, ob = 4 * c.tid * nu;
-#pragma unroll 1
-            for (int k = 0; k < nx; ++k) acc = __builtin_fmaf(row_ld(A.A, 0, nx * nx, oa + 4 * k), xc[k], acc);
-#pragma unroll 1
-            for (int j = 0; j < nu; ++j) acc = __builtin_fmaf(row_ld(A.B, 0, nx * nu, ob + 4 * j), u_l[j], acc);
-            xn[c.tid] = acc;
-            if (last) row_st(A.x_out, b, nx, 4 * c.tid, acc);
-        }
-        if (last && c.live) {
-            if (c.isA) row_st(A.s.z, b, c.n, 4 * c.row, star);
-            else row_st(A.s.y, b, c.m, 4 * c.row, star);
-        }
-        __syncthreads();  // xn published; xc and u_l free
-        if (last) {
-            loop_claim<KB, K>(a, c, sb, claim_b, x_b, wb_l, gpb_l, pdb_l, z_l, gm_l, r);
-        } else {
-            sb.t = t + 1;  // cold: z = y = 0 (acceldualgrad.m:16-17); warm: z_{-1} = z*, y_0 = y*
-            loop_start<KB, K>(a, c, sb, A.warm ? star : 0.0f, xn, wb_l, gpb_l, pdb_l, z_l, gm_l, r);
-        }
-    }
-}
-
-// one step: -ML waves run 8b+8c of slot sa, G/L waves 8d+8a (+ test) of slot sb (as duo_step)
-template <int KA, int KB, int K>
-__device__ __forceinline__ void loop_step(const SolveArgs<float>& a, const DuoCtx& c, LoopSlot& sa, LoopSlot& sb,
-                                          float* wa_l, float* zha_l, const float* gpa_l, float* wb_l,
-                                          const float* zhb_l, float* gpb_l, float* pdb_l, CheckSlot* slots_b,
-                                          CheckSlot* vslots, int* claim_b, float* z_l, float* x_b, float* u_l,
-                                          float* gm_l, const float (&r)[K]) {
-    const bool runA = sa.pos < c.count && !sa.need8d;
-    const bool runB = sb.need8d;
-    const bool chk = runB && c.use_tol && sb.kc == 1;  // ((vs + 1) % Kc == 0, as a countdown)
-    if (c.isA) {
-        if (runA) duo_half_a<KA, K>(c, sa, wa_l, zha_l, gpa_l, r);
-    } else {
-        if (runB) duo_half_b<KB, K>(c, sb, chk, zhb_l, wb_l, pdb_l, slots_b, r);
-    }
-    __syncthreads();
-    if (runA) sa.need8d = true;
-    if (runB)
-        loop_post_b<KB, K>(a, c, sb, chk, wb_l, gpb_l, pdb_l, slots_b, vslots, claim_b, z_l, x_b, u_l, gm_l, r);
-}
-
-// One live slot left, the queue drained: the resident kernel's loop on it (as duo_solo; with at
-// most one pack per workgroup this is the whole run)
-template <int KA, int KB, int K>
-__device__ __forceinline__ void loop_solo(const SolveArgs<float>& a, const DuoCtx& c, LoopSlot& s, float* w_l,
-                                          float* zh_l, float* gp_l, float* pd_l, CheckSlot* slots,
-                                          CheckSlot* vslots, int* claim, float* z_l, float* x_s, float* u_l,
-                                          float* gm_l, const float (&r)[K]) {
-    float th_n = a.theta[s.vs + 1], bn_n = a.beta[s.vs + 2];
-    while (s.pos < c.count) {
-        if (!s.need8d) {  // (a slot that enters after its 8b half starts at 8d)
-            if (c.isA) {
-                duo_half_a<KA, K>(c, s, w_l, zh_l, gp_l, r);
-            } else {
-                th_n = a.theta[s.vs + 1];
-                bn_n = a.beta[s.vs + 2];
-            }
-            __syncthreads();
-        }
-        const bool chk = c.use_tol && s.kc == 1;
-        if (!c.isA) {
-            duo_half_b<KB, K>(c, s, chk, zh_l, w_l, pd_l, slots, r);
-        } else {
-            th_n = a.theta[s.vs + 1];
-            bn_n = a.beta[s.vs + 2];
-        }
-        __syncthreads();
-        loop_post_b<KB, K, true>(a, c, s, chk, w_l, gp_l, pd_l, slots, vslots, claim, z_l, x_s, u_l, gm_l, r, th_n,
-                                 bn_n);
-    }
-}
-
-struct OpAbsmaxNan { __device__ float operator()(float x, float y) const { return absmax_nan(x, y); } };
-
-template <int KA, int KB>
-__global__ __launch_bounds__(kResidentMaxThreads) void gpad_loop_kernel(LoopArgs la) {
-    const SolveArgs<float>& a = la.s;
-    constexpr int K = KA > KB ? KA : KB;
-    constexpr int PA = (KA + 63) / 64 * 64, PB = (KB + 63) / 64 * 64;
-    __shared__ __attribute__((aligned(16))) float w_l[2][PA];   // w per slot (broadcast to -ML rows)
-    __shared__ __attribute__((aligned(16))) float zh_l[2][PB];  // zhat per slot (to G/L rows)
-    __shared__ __attribute__((aligned(16))) float z_l[PB];      // z_{-1} of a fresh solve (u seed)
-    __shared__ float gp_l[2][PB];                               // per slot: g_P of the -ML rows
-    __shared__ float pd_l[2][PA];                               //           p_D of the G/L rows
-    __shared__ CheckSlot slots[2][kResidentMaxThreads / 64];
-    __shared__ CheckSlot vslots[kResidentMaxThreads / 64];  // verification of a nominated test (A)
-    __shared__ int claim_l[2];
-    __shared__ LoopLds L;
-
-    DuoCtx c;
-    c.tid = threadIdx.x;
-    c.count = a.batch;
-    c.G = gridDim.x;
-    c.v0 = 0;
-    c.fresh = true;
-    c.use_tol = a.tol > 0.0;
-    c.n = a.n;
-    c.m = a.m;
-    c.N = a.N;
-    c.Kc = a.check_every;
-    c.kc0 = c.Kc;
-    c.nA = (c.n + 63) >> 6;
-    c.nwaves = blockDim.x >> 6;
-    {   // the G/L waves first (the older wave of each SIMD), as gpad_duo_kernel
-        const int nB = c.nwaves - c.nA;
-        c.isA = (c.tid >> 6) >= nB;
-        c.row = c.isA ? c.tid - 64 * nB : c.tid;
-        c.b0 = 0;
-    }
-    c.live = c.isA ? c.row < c.n : c.row < c.m;
-
-    float r[K];
-    {
-        const int len = c.isA ? c.m : c.n;
-        const float* __restrict__ Mt = c.isA ? a.MGt : a.GLt;
-        const int ld = c.isA ? a.ldn : a.ldm;
-#pragma unroll
-        for (int k = 0; k < K; ++k) r[k] = (c.live && k < len) ? Mt[(size_t)k * ld + c.row] : 0.0f;
-    }
-    for (int i = c.tid; i < 2 * PA; i += blockDim.x) (&w_l[0][0])[i] = 0.0f;
-    for (int i = c.tid; i < 2 * PB; i += blockDim.x) (&zh_l[0][0])[i] = 0.0f;
-    for (int i = c.tid; i < PB; i += blockDim.x) z_l[i] = 0.0f;
-    for (int i = c.tid; i < kResidentMaxThreads; i += blockDim.x) L.gm[i] = 0.0f;
-    // Static start: slot 0 of workgroup b takes pack b, slot 1 pack G + b; later packs are claimed
-    // from the counter.  (The grid is at most `batch` workgroups, so every slot 0 has a pack.)
-    c.claim_base = 2 * c.G;
-    if (c.tid == 0) {  // first claims of the queue (positions 2G, ...)
-        claim_l[0] = c.claim_base + atomicAdd(a.qctr, 1);
-        claim_l[1] = c.claim_base + atomicAdd(a.qctr, 1);
-    }
-    __syncthreads();
-    LoopSlot s0, s1;
-    s0.nextp = __builtin_amdgcn_readfirstlane(claim_l[0]);
-    s1.nextp = __builtin_amdgcn_readfirstlane(claim_l[1]);
-    loop_refill<KB, K>(a, c, s0, blockIdx.x, &L.x[0][0][0], w_l[0], gp_l[0], pd_l[0], z_l, L.gm, r);
-    loop_refill<KB, K>(a, c, s1, blockIdx.x + c.G, &L.x[1][0][0], w_l[1], gp_l[1], pd_l[1], z_l, L.gm, r);
-    while (s0.pos < c.count || s1.pos < c.count) {
-        if (s0.pos >= c.count) {
-            loop_solo<KA, KB, K>(a, c, s1, w_l[1], zh_l[1], gp_l[1], pd_l[1], slots[1], vslots, &claim_l[1], z_l,
-                                 &L.x[1][0][0], L.u, L.gm, r);
-            break;
-        }
-        if (s1.pos >= c.count) {
-            loop_solo<KA, KB, K>(a, c, s0, w_l[0], zh_l[0], gp_l[0], pd_l[0], slots[0], vslots, &claim_l[0], z_l,
-                                 &L.x[0][0][0], L.u, L.gm, r);
-            break;
-        }
-        loop_step<KA, KB, K>(a, c, s0, s1, w_l[0], zh_l[0], gp_l[0], w_l[1], zh_l[1], gp_l[1], pd_l[1], slots[1],
-                             vslots, &claim_l[1], z_l, &L.x[1][0][0], L.u, L.gm, r);
-        loop_step<KA, KB, K>(a, c, s1, s0, w_l[1], zh_l[1], gp_l[1], w_l[0], zh_l[0], gp_l[0], pd_l[0], slots[0],
-                             vslots, &claim_l[0], z_l, &L.x[0][0][0], L.u, L.gm, r);
-    }
-    // the run's max |g| (the certification floor): this workgroup's slot, workgroup 0 zeroes the rest
-    LoopKernArgs& A = largs();
-    if (A.gmax) {
-        const float wm = wave_reduce(L.gm[c.tid], OpAbsmaxNan{});
-        __syncthreads();  // (every lane has read its L.gm word)
-        if ((c.tid & 63) == 0) L.gm[c.tid >> 6] = wm;
-        __syncthreads();
-        if (c.tid == 0) {
-            float mx = 0.0f;
-            for (int w = 0; w < c.nwaves; ++w) mx = absmax_nan(mx, L.gm[w]);
-            A.gmax[blockIdx.x] = (double)mx;
-        }
-        if (blockIdx.x == 0)
-            for (int i = c.G + c.tid; i < kAbsmaxMaxBlocks; i += blockDim.x) A.gmax[i] = 0.0;
-    }
-}
-
-template <int KA>
-static void launch_loop_b(int kb, dim3 g, dim3 bl, hipStream_t st, const LoopArgs& a) {
-    switch (kb) {
-        case 32: hipLaunchKernelGGL((gpad_loop_kernel<KA, 32>), g, bl, 0, st, a); break;
-        case 64: hipLaunchKernelGGL((gpad_loop_kernel<KA, 64>), g, bl, 0, st, a); break;
-        case 96: hipLaunchKernelGGL((gpad_loop_kernel<KA, 96>), g, bl, 0, st, a); break;
-        case 128: hipLaunchKernelGGL((gpad_loop_kernel<KA, 128>), g, bl, 0, st, a); break;
-        case 160: hipLaunchKernelGGL((gpad_loop_kernel<KA, 160>), g, bl, 0, st, a); break;
-        case 192: hipLaunchKernelGGL((gpad_loop_kernel<KA, 192>), g, bl, 0, st, a); break;
-        case 200: hipLaunchKernelGGL((gpad_loop_kernel<KA, 200>), g, bl, 0, st, a); break;
-        default: hipLaunchKernelGGL((gpad_loop_kernel<KA, 208>), g, bl, 0, st, a); break;
-    }
-}
+static int loop_threads(const SolveArgs<float>& s) { return 64 * (((s.n + 63) >> 6) + ((s.m + 63) >> 6)); }
 
 bool loop_supported(int n, int m, int nx, int nu) {
     return resident_supported(n, m) && nx >= 1 && nx <= kLoopMaxState && nu >= 1 && nu <= kLoopMaxState && nu <= n;
 }
 
+int loop_blocks_per_cu(const LoopArgs& a) {
+    const SolveArgs<float>& s = a.s;
+    if (!(s.strideA || s.strideB)) return 1;
+    int nb = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void*>(loop_fn(a)), loop_threads(s),
+                                                     0) != hipSuccess)
+        return 1;
+    return nb < 1 ? 1 : (nb > 2 ? 2 : nb);
+}
+
 hipError_t launch_loop(const LoopArgs& a, int grid, hipStream_t st) {
     const SolveArgs<float>& s = a.s;
-    if (!loop_supported(s.n, s.m, a.nx, a.nu) || s.strideA || s.strideB || !s.qctr || s.N < 1 || a.steps < 1 ||
-        s.batch < 1 || grid < 1 || grid > s.batch || grid > kAbsmaxMaxBlocks)
+    if (!loop_supported(s.n, s.m, a.nx, a.nu) || !s.qctr || s.N < 1 || a.steps < 1 || s.batch < 1 || grid < 1 ||
+        grid > s.batch || grid > kAbsmaxMaxBlocks)
         return hipErrorInvalidValue;
-    const int threads = 64 * (((s.n + 63) >> 6) + ((s.m + 63) >> 6));
-    const dim3 g(grid), bl(threads);
-    const int ka = res_bucket(s.m), kb = res_bucket(s.n);
-    switch (ka) {
-        case 32: launch_loop_b<32>(kb, g, bl, st, a); break;
-        case 64: launch_loop_b<64>(kb, g, bl, st, a); break;
-        case 96: launch_loop_b<96>(kb, g, bl, st, a); break;
-        case 128: launch_loop_b<128>(kb, g, bl, st, a); break;
-        case 160: launch_loop_b<160>(kb, g, bl, st, a); break;
-        case 192: launch_loop_b<192>(kb, g, bl, st, a); break;
-        case 200: launch_loop_b<200>(kb, g, bl, st, a); break;
-        default: launch_loop_b<208>(kb, g, bl, st, a); break;
-    }
+    hipLaunchKernelGGL(loop_fn(a), dim3(grid), dim3(loop_threads(s)), 0, st, a);
     return hipGetLastError();
 }
 

@@ -16,6 +16,10 @@
 // The work is O(batch (n + m) nx) per step -- a few hundred flops per instance against the
 // O(iterations n m) of the solve -- so one thread per output row with the short chain in
 // registers is the right shape; P rows are re-read from L2 by every instance.
+//
+// Every map has an element stride between consecutive instances' copies (gpad_setup_plant_batch);
+// 0 = one map for the batch (gpad_setup_plant).  The stride only moves the row an instance reads:
+// the chain above is the same, so stride 0 gives the shared binding's bits.
 #include "gpad_internal.h"
 
 namespace gpad {
@@ -23,11 +27,13 @@ namespace gpad {
 // out1[b][i] = affine row i (i < rows1) ; out2[b][j] = affine row j (j < rows2).
 // grid.x covers the rows of one instance, grid.y the instances (grid-stride beyond 65535):
 // no integer division on the path, the state x[b] is a broadcast read per block.
+// sP*, sc*: elements between consecutive instances' P / c (0 = shared).
 template <typename T>
 __global__ __launch_bounds__(256) void affine2_kernel(const T* __restrict__ P1, const T* __restrict__ c1,
-                                                      int rows1, T* __restrict__ out1,
-                                                      const T* __restrict__ P2, const T* __restrict__ c2,
-                                                      int rows2, T* __restrict__ out2,
+                                                      int rows1, T* __restrict__ out1, long long sP1,
+                                                      long long sc1, const T* __restrict__ P2,
+                                                      const T* __restrict__ c2, int rows2,
+                                                      T* __restrict__ out2, long long sP2, long long sc2,
                                                       const T* __restrict__ x, int nx, int batch) {
     int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= rows1 + rows2) return;
@@ -35,26 +41,31 @@ __global__ __launch_bounds__(256) void affine2_kernel(const T* __restrict__ P1, 
     const T* c = c1;
     T* out = out1;
     int ld = rows1;
+    long long sP = sP1, sc = sc1;
     if (i >= rows1) {
         i -= rows1;
         P = P2;
         c = c2;
         out = out2;
         ld = rows2;
+        sP = sP2;
+        sc = sc2;
     }
-    const T* Pi = P + (size_t)i * nx;
-    const T c0 = c ? c[i] : T(0);
+    P += (size_t)i * nx;
     for (int b = blockIdx.y; b < batch; b += gridDim.y) {
         const T* xb = x + (size_t)b * nx;
-        T acc = c0;
+        const T* Pi = P + b * sP;
+        T acc = c ? c[b * sc + i] : T(0);
         for (int k = 0; k < nx; ++k) acc = __builtin_fma(Pi[k], xb[k], acc);
         out[(size_t)b * ld + i] = acc;
     }
 }
 
 // xn[b] = A x[b] + B z[b][0:nu];  optional trajectories xs[b] = x[b], us[b] = z[b][0:nu]
+// sA, sB: elements between consecutive instances' A / B (0 = shared)
 template <typename T>
 __global__ __launch_bounds__(256) void plant_step_kernel(const T* __restrict__ A, const T* __restrict__ B,
+                                                         long long sA, long long sB,
                                                          const T* __restrict__ x, const T* __restrict__ z,
                                                          long long ldz, T* __restrict__ xn, int nx, int nu,
                                                          int batch, T* __restrict__ xs, T* __restrict__ us) {
@@ -68,9 +79,9 @@ __global__ __launch_bounds__(256) void plant_step_kernel(const T* __restrict__ A
         const T* ub = z + (long long)b * ldz;
         if (i < nx) {
             T acc = T(0);
-            const T* Ai = A + (long long)i * nx;
+            const T* Ai = A + b * sA + (long long)i * nx;
             for (int k = 0; k < nx; ++k) acc = __builtin_fma(Ai[k], xb[k], acc);
-            const T* Bi = B + (long long)i * nu;
+            const T* Bi = B + b * sB + (long long)i * nu;
             for (int j = 0; j < nu; ++j) acc = __builtin_fma(Bi[j], ub[j], acc);
             xn[(long long)b * nx + i] = acc;
             if (xs) xs[(long long)b * nx + i] = xb[i];
@@ -88,31 +99,33 @@ static dim3 grid_for(long long total) {
 
 template <typename T>
 hipError_t launch_affine2(const T* P1, const T* c1, int rows1, T* out1, const T* P2, const T* c2,
-                          int rows2, T* out2, const T* x, int nx, int batch, hipStream_t s) {
+                          int rows2, T* out2, const T* x, int nx, int batch, bool per_instance, hipStream_t s) {
     const dim3 grid((rows1 + rows2 + 255) / 256, batch < 65535 ? batch : 65535);
-    hipLaunchKernelGGL(affine2_kernel<T>, grid, dim3(256), 0, s, P1, c1, rows1, out1, P2, c2, rows2, out2, x,
-                       nx, batch);
+    const long long p = per_instance ? 1 : 0;
+    hipLaunchKernelGGL(affine2_kernel<T>, grid, dim3(256), 0, s, P1, c1, rows1, out1, p * rows1 * nx, p * rows1,
+                       P2, c2, rows2, out2, p * rows2 * nx, p * rows2, x, nx, batch);
     return hipGetLastError();
 }
 
 template <typename T>
 hipError_t launch_plant_step(const T* A, const T* B, const T* x, const T* z, long long ldz, T* xn, int nx,
-                             int nu, int batch, T* xs, T* us, hipStream_t s) {
+                             int nu, int batch, T* xs, T* us, bool per_instance, hipStream_t s) {
     const int per = nx > nu ? nx : nu;
-    hipLaunchKernelGGL(plant_step_kernel<T>, grid_for((long long)batch * per), dim3(256), 0, s, A, B, x, z,
-                       ldz, xn, nx, nu, batch, xs, us);
+    const long long p = per_instance ? 1 : 0;
+    hipLaunchKernelGGL(plant_step_kernel<T>, grid_for((long long)batch * per), dim3(256), 0, s, A, B,
+                       p * nx * nx, p * nx * nu, x, z, ldz, xn, nx, nu, batch, xs, us);
     return hipGetLastError();
 }
 
 template hipError_t launch_affine2<float>(const float*, const float*, int, float*, const float*,
-                                          const float*, int, float*, const float*, int, int, hipStream_t);
+                                          const float*, int, float*, const float*, int, int, bool, hipStream_t);
 template hipError_t launch_affine2<double>(const double*, const double*, int, double*, const double*,
-                                           const double*, int, double*, const double*, int, int,
+                                           const double*, int, double*, const double*, int, int, bool,
                                            hipStream_t);
 template hipError_t launch_plant_step<float>(const float*, const float*, const float*, const float*,
-                                             long long, float*, int, int, int, float*, float*, hipStream_t);
+                                             long long, float*, int, int, int, float*, float*, bool, hipStream_t);
 template hipError_t launch_plant_step<double>(const double*, const double*, const double*, const double*,
-                                              long long, double*, int, int, int, double*, double*,
+                                              long long, double*, int, int, int, double*, double*, bool,
                                               hipStream_t);
 
 // acc += sum of per-instance iteration counts (one workgroup; wave sums then one atomic per wave)

@@ -12,7 +12,7 @@ import os
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "libgpad.so")
 
-VERSION_MAJOR, VERSION_MINOR = 0, 5  # include/gpad.h GPAD_VERSION_*: the layouts this binding declares
+VERSION_MAJOR, VERSION_MINOR = 0, 6  # include/gpad.h GPAD_VERSION_*: the layouts this binding declares
 GPAD_OK = 0
 ERR_INVALID, ERR_HIP, ERR_NOMEM, ERR_UNSUPPORTED, ERR_NOT_SETUP, ERR_NO_DEVICE = -1, -2, -3, -4, -5, -6
 ERR_DEVICE = -7  # a kernel reported a device-side failure (include/gpad.h)
@@ -33,7 +33,7 @@ EXPORTS = [
     "gpad_last_stats", "gpad_phase_plan", "gpad_plan_phases", "gpad_solve", "gpad_step1_extrapolate",
     "gpad_step2_primal",
     "gpad_step3_average", "gpad_step4_project", "gpad_schedule", "gpad_sync",
-    "gpad_setup_plant", "gpad_run_state", "gpad_closed_loop",
+    "gpad_setup_plant", "gpad_setup_plant_batch", "gpad_run_state", "gpad_closed_loop",
     "gpad_datafile_read", "gpad_datafile_write", "gpad_datafile_free",
     "gpad_setup_flat", "gpad_step2_primal_flat", "gpad_step4_project_flat", "gpad_precompute",
     "gpad_accumulate_iterations", "gpad_set_option",
@@ -178,6 +178,7 @@ def load(path: str | None = None) -> C.CDLL:
     L.gpad_schedule.argtypes = [i, i, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     del f
     L.gpad_setup_plant.argtypes = [vp, i, i, cvp, cvp, cvp, cvp, cvp, cvp]
+    L.gpad_setup_plant_batch.argtypes = [vp, i, i, cvp, cvp, cvp, cvp, cvp, cvp]
     L.gpad_run_state.argtypes = [vp, cvp, vp, vp, i, d, C.POINTER(Stats)]
     L.gpad_closed_loop.argtypes = [vp, vp, vp, vp, i, i, d, i, vp, vp, C.POINTER(Stats)]
     L.gpad_datafile_read.argtypes = [C.c_char_p, i, C.POINTER(DataFile)]
@@ -201,7 +202,7 @@ def load(path: str | None = None) -> C.CDLL:
     for name in ["gpad_create", "gpad_destroy", "gpad_set_stream", "gpad_sync", "gpad_setup", "gpad_setup_hessian",
                  "gpad_setup_scaled", "gpad_run", "gpad_run_scaled", "gpad_last_stats",
                  "gpad_phase_plan", "gpad_plan_phases", "gpad_solve", "gpad_step1_extrapolate", "gpad_step2_primal",
-                 "gpad_step3_average", "gpad_step4_project", "gpad_schedule", "gpad_setup_plant",
+                 "gpad_step3_average", "gpad_step4_project", "gpad_schedule", "gpad_setup_plant", "gpad_setup_plant_batch",
                  "gpad_run_state", "gpad_closed_loop", "gpad_datafile_read",
                  "gpad_datafile_write", "gpad_setup_flat", "gpad_step2_primal_flat",
                  "gpad_step4_project_flat", "gpad_precompute", "gpad_accumulate_iterations",

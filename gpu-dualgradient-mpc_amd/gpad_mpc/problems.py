@@ -41,11 +41,12 @@ class QP:
         return self.ML.shape[-1]
 
 
-def battery_matrices(n_u: int, N: int, capacity_ah: float = 0.027 * 4.1, qx: float = 100.0,
+def battery_matrices(n_u: int, N: int, capacity_ah=0.027 * 4.1, qx: float = 100.0,
                      qu: float = 1.0):
-    """gpad.m:18-77 -- A, B, M_ak, M_ab, K, H, F for ``n_u`` cells over horizon ``N``."""
+    """gpad.m:18-77 -- A, B, M_ak, M_ab, K, H, F for ``n_u`` cells over horizon ``N``.
+    ``capacity_ah``: one capacity for every cell, or the n_u CellCapacities of gpad.m:18."""
     n, p = n_u, N
-    cap = np.full(n, capacity_ah)
+    cap = np.broadcast_to(np.asarray(capacity_ah, np.float64), (n,)).copy()
     A = np.eye(n)
     B = np.diag(-1.0 / (3600.0 * cap))                                   # gpad.m:38-41
     M_ak = np.zeros((n * p, n))
@@ -148,20 +149,20 @@ class Plant:
 
     @property
     def nx(self) -> int:
-        return self.PM.shape[1]
+        return self.PM.shape[-1]
 
     @property
     def nu(self) -> int:
-        return self.B.shape[1]
+        return self.B.shape[-1]
 
 
 def battery_plant(n_u: int = 4, N: int = 10, xmax: float = 0.5, xmin: float = -0.5,
-                  umax: float = 0.3, umin: float = -0.3):
+                  umax: float = 0.3, umin: float = -0.3, capacity_ah=0.027 * 4.1):
     """The battery-balancing MPC of gpad.m as (QP, Plant): the constant ML, G, L of the QP
     and the affine maps of gpad.m:81-85 -- f = x0'F so M(x) = H^-1 F' x (M0 = 0);
     b_i(x) = [xmax - M_ak x; -xmin + M_ak x; umax; -umin; 0; 0] -- plus x+ = A x + B u
-    (gpad.m:93).  Everything float64."""
-    mats = battery_matrices(n_u, N)
+    (gpad.m:93).  ``capacity_ah``: as battery_matrices.  Everything float64."""
+    mats = battery_matrices(n_u, N, capacity_ah)
     x0 = np.zeros(n_u)
     f0, A_i, b0 = battery_constraints(mats, x0, n_u, N, xmax, xmin, umax, umin)
     qp = gpad_precompute(mats["H"], f0, A_i, b0)
@@ -172,6 +173,32 @@ def battery_plant(n_u: int = 4, N: int = 10, xmax: float = 0.5, xmin: float = -0
     Pg = np.vstack([-M_ak, M_ak, z, z, np.zeros((N, n_u)), np.zeros((N, n_u))])
     plant = Plant(PM=PM, Pg=Pg, A=mats["A"], B=mats["B"], M0=None, g0=b0)
     qp.meta = dict(kind="battery_plant", n_u=n_u, N=N)
+    return qp, plant
+
+
+def battery_fleet_caps(batch: int, n_u: int, seed: int, spread: float = 0.4) -> np.ndarray:
+    """Cell capacities [batch][n_u] in Ah for a fleet of unequal packs: the nominal 0.027 * 4.1 of
+    gpad.m:18 times U(1 - spread, 1 + spread), seeded."""
+    return 0.027 * 4.1 * np.random.default_rng(seed).uniform(1.0 - spread, 1.0 + spread, (batch, n_u))
+
+
+def battery_fleet(n_u: int, N: int, caps, **limits):
+    """A fleet of battery packs with their own cell capacities ``caps`` [batch][n_u] (Ah): pack b is
+    ``battery_plant(n_u, N, capacity_ah=caps[b])``, i.e. B = diag(-1 / (3600 caps[b])) and the H, F,
+    constraint stack that follow from it.  Returns (QP, Plant) with every array stacked on a
+    leading batch axis -- ML (batch, n, m), G (batch, m, n), PM, Pg, g0, A, B -- for
+    ``setup(..., shared=False)`` and a stacked ``setup_plant``.  L is one scalar, the maximum over
+    the packs (the C-ABI takes one L; the maximum is valid for every pack, as synthetic_qp)."""
+    caps = np.asarray(caps, np.float64)
+    if caps.ndim != 2 or caps.shape[1] != n_u:
+        raise ValueError(f"caps must be [batch][{n_u}], got {caps.shape}")
+    packs = [battery_plant(n_u, N, capacity_ah=c, **limits) for c in caps]
+    stack = lambda f: np.stack([f(qp, pl) for qp, pl in packs])  # noqa: E731
+    qp = QP(ML=stack(lambda q, p: q.ML), M=stack(lambda q, p: q.M), G=stack(lambda q, p: q.G),
+            g=stack(lambda q, p: q.g), L=max(q.L for q, _ in packs), H=stack(lambda q, p: q.H),
+            q=stack(lambda q, p: q.q), meta=dict(kind="battery_fleet", n_u=n_u, N=N, caps=caps))
+    plant = Plant(PM=stack(lambda q, p: p.PM), Pg=stack(lambda q, p: p.Pg), A=stack(lambda q, p: p.A),
+                  B=stack(lambda q, p: p.B), M0=None, g0=stack(lambda q, p: p.g0))
     return qp, plant
 
 

@@ -286,12 +286,29 @@ class GpadSolver:
 
     def setup_plant(self, PM, Pg, *, M0=None, g0=None, A=None, B=None) -> None:
         """Bind M(x) = M0 + PM x, g(x) = g0 + Pg x and (optionally) x+ = A x + B u.
-        Same dtype / memory kind as the preceding ``setup``."""
+        Same dtype / memory kind as the preceding ``setup``.
+
+        One plant for the batch: PM (n, nx), Pg (m, nx), M0 (n), g0 (m), A (nx, nx), B (nx, nu).
+        A stacked PM (batch, n, nx) binds per-instance maps (gpad_setup_plant_batch): every array
+        given must then carry the leading batch axis.  That serves a fleet of distinct plants
+        (``setup(..., shared=False)``) and one controller against per-instance true plants
+        (``shared=True``) alike."""
+        stacked = PM.ndim == 3
+        arrays = dict(PM=PM, Pg=Pg, M0=M0, g0=g0, A=A, B=B)
+        if stacked:
+            batch = PM.shape[0]
+            if self.dims is not None and batch != self.dims.batch:
+                raise ValueError(f"setup_plant: PM is stacked for {batch} instances, the setup has {self.dims.batch}")
+            for name, a in arrays.items():
+                want = 2 if name in ("M0", "g0") else 3
+                if a is not None and (a.ndim != want or a.shape[0] != batch):
+                    raise ValueError(f"setup_plant: PM is stacked (batch = {batch}), so {name} must be "
+                                     f"{want}-dimensional with the same leading batch axis")
         nx = PM.shape[-1]
         nu = 0 if B is None else B.shape[-1]
         opt = lambda a: _ptr(a) if a is not None else None  # noqa: E731
-        check(self.lib.gpad_setup_plant(self.h, nx, nu, _ptr(PM), opt(M0), _ptr(Pg), opt(g0),
-                                        opt(A), opt(B)), "gpad_setup_plant")
+        fn = "gpad_setup_plant_batch" if stacked else "gpad_setup_plant"
+        check(getattr(self.lib, fn)(self.h, nx, nu, _ptr(PM), opt(M0), _ptr(Pg), opt(g0), opt(A), opt(B)), fn)
 
     def run_state(self, x, z, y, N: int, tol: float = 0.0, *, stats: bool = True):
         """GPAD for every instance's state x [batch][nx] (M(x), g(x) formed on the device)."""
@@ -310,9 +327,10 @@ class GpadSolver:
 
         The steps run in lockstep by default.  After ``set_option("loop_async", 1)`` the whole loop
         is one launch in which an instance starts its next step as soon as its own solve ends
-        (``kernel == "loop"`` in the stats); it applies to f32 setups with shared matrices, no flat
-        setup and no Hessian, n, m <= 208, kernel AUTO or RESIDENT, N >= 1, nx <= 64 and
-        nu <= min(n, 64), and any other call runs the lockstep loop.  Results are bit-identical."""
+        (``kernel == "loop"`` in the stats); it applies to f32 setups, shared matrices or per-instance
+        ones, no flat setup and no Hessian, n, m <= 208, kernel AUTO or RESIDENT, N >= 1, nx <= 64 and
+        nu <= min(n, 64), with one plant or per-instance maps (``setup_plant``), and any other call
+        runs the lockstep loop.  Results are bit-identical."""
         st = Stats()
         for arr, field in ((iters, "iters"), (codes, "codes")):
             if arr is not None:

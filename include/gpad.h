@@ -26,11 +26,12 @@ extern "C" {
 #endif
 
 #define GPAD_VERSION_MAJOR 0
-#define GPAD_VERSION_MINOR 5 /* 0.3: gpad_stats_t gained tol_floor / flags, gpad_dims_t an explicit reserved
+#define GPAD_VERSION_MINOR 6 /* 0.3: gpad_stats_t gained tol_floor / flags, gpad_dims_t an explicit reserved
                               * word (layouts changed: rebuild callers against this header);
                               * 0.4: the condensed operator (kernel 5, option 14) removed, the device
                               * error word sticky until reported; layouts as in 0.3;
-                              * 0.5: options 20, 21 removed; layouts as in 0.3 */
+                              * 0.5: options 20, 21 removed; layouts as in 0.3;
+                              * 0.6: gpad_setup_plant_batch added; layouts as in 0.3 */
 
 /* status codes */
 #define GPAD_OK 0
@@ -228,6 +229,24 @@ int gpad_precompute(gpad_handle_t h, int n, int m, int batch, int shared, int me
 int gpad_setup_plant(gpad_handle_t h, int nx, int nu, const void* PM, const void* M0, const void* Pg,
                      const void* g0, const void* A, const void* B);
 
+/* gpad_setup_plant for a batch of distinct plants: same meaning and validation, but every non-NULL
+ * array holds dims.batch consecutive per-instance copies,
+ *   PM [batch][n][nx], M0 [batch][n], Pg [batch][m][nx], g0 [batch][m], A [batch][nx][nx],
+ *   B [batch][nx][nu],
+ * and gpad_run_state / gpad_closed_loop evaluate instance b with copy b of each map:
+ *   M_b(x) = M0_b + PM_b x,  g_b(x) = g0_b + Pg_b x,  x+ = A_b x + B_b z*[0:nu].
+ * The arithmetic per instance is gpad_setup_plant's, so a batch bound here gives, instance for
+ * instance, the bits of `batch` separate batch-1 handles bound with gpad_setup_plant.
+ * It combines with either setting of dims.shared: 0 is a fleet (every instance its own ML, G and
+ * maps, all of which derive from its plant), 1 is one controller (shared ML, G) run against
+ * per-instance true plants -- a plant/model mismatch study.  L stays the one scalar of gpad_setup:
+ * a fleet passes an L valid for every instance, e.g. the maximum of the per-instance bounds.
+ * A later gpad_setup_plant rebinds one shared plant.  The binding is for the dims.batch of the
+ * preceding gpad_setup: after a gpad_setup with another batch, gpad_run_state / gpad_closed_loop
+ * return GPAD_ERR_NOT_SETUP until a plant is bound again. */
+int gpad_setup_plant_batch(gpad_handle_t h, int nx, int nu, const void* PM, const void* M0, const void* Pg,
+                           const void* g0, const void* A, const void* B);
+
 /* gpad_run with M = M(x), g = g(x) evaluated on the device for every instance's state
  * x [batch][nx] (no host round trip for the per-state precompute). */
 int gpad_run_state(gpad_handle_t h, const void* x, void* z0, void* y0, int N, double tol,
@@ -248,9 +267,12 @@ int gpad_run_state(gpad_handle_t h, const void* x, void* z0, void* y0, int N, do
  * slowest instance.  With GPAD_OPT_LOOP_ASYNC = 1 the loop is one launch (stats kernel =
  * GPAD_KERNEL_LOOP) in which an instance whose solve terminates applies its own plant update and
  * affine maps and starts its next step at once, no instance waiting for another.  That path is
- * taken for f32, shared matrices bound by gpad_setup (no flat setup, no Hessian), n, m <= 208,
- * dims.kernel AUTO or RESIDENT, N >= 1, nx <= 64 and nu <= min(n, 64); any other call runs the
- * lockstep loop as if the option were unset.  Results are identical either way: x, z, y, xs, us and
+ * taken for f32 matrices bound by gpad_setup (shared or per instance; no flat setup, no Hessian),
+ * n, m <= 208, dims.kernel AUTO or RESIDENT, N >= 1, nx <= 64 and nu <= min(n, 64), with a plant
+ * bound by gpad_setup_plant or gpad_setup_plant_batch; any other call runs the lockstep loop as if
+ * the option were unset.  With per-instance matrices a workgroup holds one instance at a time and
+ * keeps its matrix rows in registers for all `steps` steps; the grid is up to two workgroups per
+ * compute unit where they fit, capped by GPAD_OPT_DUO_MAX_GRID like the shared-matrix grid.  Results are identical either way: x, z, y, xs, us and
  * every stat (per-step counts and codes included) are bit for bit those of the lockstep loop. */
 int gpad_closed_loop(gpad_handle_t h, void* x, void* z, void* y, int steps, int N, double tol, int warm,
                      void* xs, void* us, gpad_stats_t* st);

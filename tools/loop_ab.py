@@ -3,7 +3,13 @@
 tensors.  C1 plant (battery_plant(4, 10): n = 40, m = 180), 20 MPC steps, batches 1 ... 8192, three
 modes: eps cold / eps warm (tol 1e-4, N 3000) and fixed N = 100.
 
-  python tools/loop_ab.py [--rounds 3] [--steps 20] [--batches 1 64 256 512 2048 8192]
+  python tools/loop_ab.py [--rounds 3] [--steps 20] [--batches 1 64 256 512 2048 8192] [--fleet]
+
+--fleet: a fleet of distinct packs instead (problems.battery_fleet(4, 10, battery_fleet_caps(batch, 4,
+seed = batch)): per-pack ML, G and plant maps, setup(shared=False) + a stacked setup_plant), default
+batches 1 64 256 2048 8192.  The lockstep loop runs the resident kernel there, the option the fleet
+kernel; a third variant, "async_1wg", caps the grid at one workgroup per CU (duo_max_grid = CUs) to
+show what the second workgroup per CU buys, and `async_1wg_over_async` is its rate over the default's.
 
 Per batch and mode the two variants' x, z, y, xs, us and per-step iteration counts are compared first
 (that run is also each variant's warm-up); a mismatch aborts the batch.  Then `rounds` rounds
@@ -33,8 +39,11 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--steps", type=int, default=20)
-    ap.add_argument("--batches", type=int, nargs="*", default=[1, 64, 256, 512, 2048, 8192])
+    ap.add_argument("--batches", type=int, nargs="*", default=None)
+    ap.add_argument("--fleet", action="store_true")
     args = ap.parse_args()
+    if args.batches is None:
+        args.batches = [1, 64, 256, 2048, 8192] if args.fleet else [1, 64, 256, 512, 2048, 8192]
     rounds = max(3, args.rounds)
     import torch
 
@@ -45,16 +54,22 @@ def main():
     n, m, nx, nu, steps = qp.n, qp.m, pl.nx, pl.nu, args.steps
     t32 = lambda a: torch.from_numpy(np.ascontiguousarray(np.asarray(a, np.float64).astype(np.float32))).to(dev)  # noqa: E731
     dML, dG, dPM, dPg, dg0, dA, dB = (t32(a) for a in (qp.ML, qp.G, pl.PM, pl.Pg, pl.g0, pl.A, pl.B))
-    print(json.dumps({"plant": "battery_plant(4, 10)", "n": n, "m": m, "steps": steps, "rounds": rounds,
-                      "device": torch.cuda.get_device_name(0)}))
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    print(json.dumps({"plant": "battery_fleet(4, 10)" if args.fleet else "battery_plant(4, 10)", "n": n, "m": m,
+                      "steps": steps, "rounds": rounds, "device": torch.cuda.get_device_name(0), "cus": cus}))
     for B in args.batches:
         X0 = torch.from_numpy((np.random.default_rng(B).random((B, nx)) - 0.5).astype(np.float32)).to(dev)
+        if args.fleet:
+            qp, pl = problems.battery_fleet(4, 10, problems.battery_fleet_caps(B, 4, B))
+            dML, dG, dPM, dPg, dg0, dA, dB = (t32(a) for a in (qp.ML, qp.G, pl.PM, pl.Pg, pl.g0, pl.A, pl.B))
         var = {}
-        for name in ("lockstep", "async"):
+        for name in ("lockstep", "async") + (("async_1wg",) if args.fleet else ()):
             s = gpad_mpc.GpadSolver(0)
-            s.setup(dML, dG, float(np.float32(qp.L)), n=n, m=m, batch=B, shared=True)
+            s.setup(dML, dG, float(np.float32(qp.L)), n=n, m=m, batch=B, shared=not args.fleet)
             s.setup_plant(dPM, dPg, g0=dg0, A=dA, B=dB)
-            s.set_option("loop_async", int(name == "async"))
+            s.set_option("loop_async", int(name != "lockstep"))
+            if name == "async_1wg":
+                s.set_option("duo_max_grid", cus)
             buf = dict(x=torch.empty(B, nx, device=dev), z=torch.empty(B, n, device=dev),
                        y=torch.empty(B, m, device=dev), xs=torch.empty(steps, B, nx, device=dev),
                        us=torch.empty(steps, B, nu, device=dev))
@@ -74,11 +89,11 @@ def main():
             for name in var:  # the output check, and each variant's warm-up
                 its[name] = np.zeros(steps * B, np.int32)
                 kern[name] = enqueue(name, mode, iters=its[name])["kernel"]
-            bad = [k for k in ("x", "z", "y", "xs", "us")
-                   if not torch.equal(var["lockstep"][1][k].view(torch.int32), var["async"][1][k].view(torch.int32))]
-            if not np.array_equal(its["lockstep"], its["async"]):
+            bad = [k for k in ("x", "z", "y", "xs", "us") for v in var if v != "lockstep"
+                   if not torch.equal(var["lockstep"][1][k].view(torch.int32), var[v][1][k].view(torch.int32))]
+            if any(not np.array_equal(its["lockstep"], its[v]) for v in var):
                 bad.append("iters")
-            if bad or kern["async"] != "loop" or kern["lockstep"] == "loop":
+            if bad or any((kern[v] == "loop") != (v != "lockstep") for v in var):
                 print(json.dumps({"batch": B, "mode": mname, "error": "outputs differ" if bad else "wrong kernel",
                                   "differ": bad, "kernels": kern}))
                 break
@@ -103,7 +118,9 @@ def main():
                 "kernel_ms": {k: [round(x, 4) for x in v] for k, v in ms.items()},
                 "wall_ms": {k: [round(x, 4) for x in v] for k, v in wall.items()},
                 "mpc_steps_per_s": {k: round(v, 1) for k, v in rate.items()},
-                "async_over_lockstep": round(rate["async"] / rate["lockstep"], 3), "faster": faster}), flush=True)
+                "async_over_lockstep": round(rate["async"] / rate["lockstep"], 3), "faster": faster,
+                **({"async_1wg_over_async": round(rate["async_1wg"] / rate["async"], 3)} if args.fleet else {})}),
+                flush=True)
         for s, _ in var.values():
             s.close()
 
