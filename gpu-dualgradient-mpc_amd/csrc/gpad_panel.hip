@@ -1126,10 +1126,12 @@ __device__ __forceinline__ void panel2_run(const SolveArgs<float>& a, Panel2Lds<
         int v = a.v_begin;
         GPAD_STAMP_DECL
         int kc = K - v % K;  // iterations to the next test: chk <=> v % K == 0 (a countdown, no division)
-        float th = a.theta[v], bn = a.beta[v + 1];
         while (true) {
             GPAD_STAMP_AT(0);  // (before the schedule's scalar loads, which a later s_memtime queues behind)
-            const float th_next = a.theta[v + 1], bn_next = a.beta[v + 2];
+            // this iteration's schedule, loaded here and first used after GEMM 1: the loads are older
+            // than every A load of the GEMM, so the GEMM's own vmcnt waits cover them (r09: loading
+            // one iteration ahead cost two carried registers and two moves per iteration)
+            const float th = a.theta[v], bn = a.beta[v + 1];
             ++v;
             const bool chk = use_tol && --kc == 0;
             if (kc == 0) kc = K;
@@ -1186,15 +1188,6 @@ __device__ __forceinline__ void panel2_run(const SolveArgs<float>& a, Panel2Lds<
             __syncthreads();
             GPAD_STAMP_AT(3);
             // ---- GEMM 2 + epilogue: y+ = [w + G_L zhat + p_D]+ (8d), next w (8a) ----------
-            float violz[Q], violh[Q], wmin[Q], magh[Q];
-            double gap[Q];
-#pragma unroll
-            for (int q = 0; q < Q; ++q) {
-                violz[q] = violh[q] = -INFINITY;
-                wmin[q] = INFINITY;
-                magh[q] = 0.0f;
-                gap[q] = 0.0;
-            }
             if constexpr (NU > 0) {
                 f32x4 acc[2];
                 ++hgen;
@@ -1229,29 +1222,48 @@ __device__ __forceinline__ void panel2_run(const SolveArgs<float>& a, Panel2Lds<
                 // only -- so the per-element masks of the active columns are not needed.  This
                 // epilogue sits between the GEMM and the barrier on every SIMD at once; packing
                 // halves its VALU issue: C4 to eps +1.3-1.5 % (profiles/r02_epilogue_ab.txt).
-                const f32x2 th2 = f2(th, th), omt2 = f2(omt, omt), bn2 = f2(bn, bn), half2 = f2(0.5f, 0.5f);
+                // Three straight-line stages (r09): 8d / 8a of every panel, then the u recursion, then
+                // (test iterations only) the partials.  Interleaved per panel, the uniform use_tol / chk
+                // branches cut the epilogue into blocks that shared the splats and the partials' seeds:
+                // a plain iteration of a double wave paid 10 seed moves and 3 splat moves (each stage now
+                // forms its own splats, which the packed ops read by op_sel broadcast).
+                {
+                    const f32x2 bn2 = f2(bn, bn), half2 = f2(0.5f, 0.5f);
 #pragma unroll
-                for (int q = 0; q < Q; ++q) {
-                    const f32x2 c0 = f2(acc[q][0], acc[q][1]), c1 = f2(acc[q][2], acc[q][3]);
-                    const f32x2 s0 = (f2(w4[q].x, w4[q].y) + f2(p4[q].x, p4[q].y)) + c0;
-                    const f32x2 s1 = (f2(w4[q].z, w4[q].w) + f2(p4[q].z, p4[q].w)) + c1;
-                    const f32x2 y0 = f2(__builtin_fabsf(s0.x) + s0.x, __builtin_fabsf(s0.y) + s0.y) * half2;
-                    const f32x2 y1 = f2(__builtin_fabsf(s1.x) + s1.x, __builtin_fabsf(s1.y) + s1.y) * half2;
-                    const f32x2 n0 = pk_fma(bn2, y0 - f2(y[q][0], y[q][1]), y0);
-                    const f32x2 n1 = pk_fma(bn2, y1 - f2(y[q][2], y[q][3]), y1);
-                    L.Wl[p0 + q][slot] = make_float4(n0.x, n0.y, n1.x, n1.y);
-                    y[q][0] = y0.x;
-                    y[q][1] = y0.y;
-                    y[q][2] = y1.x;
-                    y[q][3] = y1.y;
-                    if (use_tol) {
+                    for (int q = 0; q < Q; ++q) {
+                        const f32x2 c0 = f2(acc[q][0], acc[q][1]), c1 = f2(acc[q][2], acc[q][3]);
+                        const f32x2 s0 = (f2(w4[q].x, w4[q].y) + f2(p4[q].x, p4[q].y)) + c0;
+                        const f32x2 s1 = (f2(w4[q].z, w4[q].w) + f2(p4[q].z, p4[q].w)) + c1;
+                        const f32x2 y0 = f2(__builtin_fabsf(s0.x) + s0.x, __builtin_fabsf(s0.y) + s0.y) * half2;
+                        const f32x2 y1 = f2(__builtin_fabsf(s1.x) + s1.x, __builtin_fabsf(s1.y) + s1.y) * half2;
+                        const f32x2 n0 = pk_fma(bn2, y0 - f2(y[q][0], y[q][1]), y0);
+                        const f32x2 n1 = pk_fma(bn2, y1 - f2(y[q][2], y[q][3]), y1);
+                        L.Wl[p0 + q][slot] = make_float4(n0.x, n0.y, n1.x, n1.y);
+                        y[q][0] = y0.x;
+                        y[q][1] = y0.y;
+                        y[q][2] = y1.x;
+                        y[q][3] = y1.y;
+                    }
+                }
+                if (use_tol) {
+                    const f32x2 th2 = f2(th, th), omt2 = f2(omt, omt);
+#pragma unroll
+                    for (int q = 0; q < Q; ++q) {
+                        const f32x2 c0 = f2(acc[q][0], acc[q][1]), c1 = f2(acc[q][2], acc[q][3]);
                         const f32x2 u0 = pk_fma(omt2, f2(u[q][0], u[q][1]), th2 * c0);
                         const f32x2 u1 = pk_fma(omt2, f2(u[q][2], u[q][3]), th2 * c1);
                         u[q][0] = u0.x;
                         u[q][1] = u0.y;
                         u[q][2] = u1.x;
                         u[q][3] = u1.y;
-                        if (chk && act[q]) {
+                    }
+                }
+                if (chk) {  // (implies use_tol) this tile's per-column partials of the test -> LDS
+#pragma unroll
+                    for (int q = 0; q < Q; ++q) {
+                        float violz = -INFINITY, violh = -INFINITY, wmin = INFINITY, magh = 0.0f;
+                        double gap = 0.0;
+                        if (act[q]) {
                             const float wv[4] = {w4[q].x, w4[q].y, w4[q].z, w4[q].w};
                             const float pd[4] = {p4[q].x, p4[q].y, p4[q].z, p4[q].w};
 #pragma unroll
@@ -1259,26 +1271,24 @@ __device__ __forceinline__ void panel2_run(const SolveArgs<float>& a, Panel2Lds<
                                 if ((16 * t + 4 * r + j) < m) {
                                     const float cv = acc[q][r];
                                     const float tt = cv + pd[r];
-                                    violh[q] = fmaxf(violh[q], tt);
-                                    magh[q] = fmaxf(magh[q], __builtin_fabsf(cv) + __builtin_fabsf(pd[r]));
-                                    wmin[q] = fminf(wmin[q], wv[r]);
-                                    gap[q] -= (double)wv[r] * (double)tt;
-                                    violz[q] = fmaxf(violz[q], u[q][r] + pd[r]);
+                                    violh = fmaxf(violh, tt);
+                                    magh = fmaxf(magh, __builtin_fabsf(cv) + __builtin_fabsf(pd[r]));
+                                    wmin = fminf(wmin, wv[r]);
+                                    gap -= (double)wv[r] * (double)tt;
+                                    violz = fmaxf(violz, u[q][r] + pd[r]);
                                 }
                             }
                         }
-                    }
-                    if (chk) {  // this tile's per-column partials of the test -> LDS
                         // lane groups j (xor 16, 32) on the VALU (gpad_chain.h)
-                        violz[q] = bfly<32>(bfly<16>(violz[q], OpMax{}), OpMax{});
-                        violh[q] = bfly<32>(bfly<16>(violh[q], OpMax{}), OpMax{});
-                        magh[q] = bfly<32>(bfly<16>(magh[q], OpMax{}), OpMax{});
-                        wmin[q] = bfly<32>(bfly<16>(wmin[q], OpMin{}), OpMin{});
-                        gap[q] = bfly<32>(bfly<16>(gap[q], OpAdd{}), OpAdd{});
+                        violz = bfly<32>(bfly<16>(violz, OpMax{}), OpMax{});
+                        violh = bfly<32>(bfly<16>(violh, OpMax{}), OpMax{});
+                        magh = bfly<32>(bfly<16>(magh, OpMax{}), OpMax{});
+                        wmin = bfly<32>(bfly<16>(wmin, OpMin{}), OpMin{});
+                        gap = bfly<32>(bfly<16>(gap, OpAdd{}), OpAdd{});
                         if (j == 0) {
                             PanelSlot2& S = L.slots[p0 + q][t];
-                            S.f[c] = make_float4(violz[q], violh[q], magh[q], wmin[q]);
-                            S.gap[c] = gap[q];
+                            S.f[c] = make_float4(violz, violh, magh, wmin);
+                            S.gap[c] = gap;
                         }
                     }
                 }
@@ -1290,8 +1300,6 @@ __device__ __forceinline__ void panel2_run(const SolveArgs<float>& a, Panel2Lds<
             } else {
                 GPAD_PRELUDE_LO();
             }
-            th = th_next;
-            bn = bn_next;
             GPAD_STAMP_AT(5);
             GPAD_PRELUDE_HI();
             __syncthreads();
@@ -1385,6 +1393,13 @@ __device__ __forceinline__ void panel2_run(const SolveArgs<float>& a, Panel2Lds<
                 GPAD_PSTAMP_END(8);
             }
             // ---- finished columns: results out ---------------------------------------------
+            // (r09) nothing finished and the run goes on -- m1, m2, v are uniform over the workgroup: skip
+            // results-out.  Before, every test ran its selects, row pointers and the LDS transposes of
+            // both stores with every lane masked off: ~17 of phase 1's 26 tests at C4.
+            if ((m1 | m2) == 0u && v < N) {
+                if (v >= a.v_end) break;
+                continue;
+            }
             if constexpr (NU > 0) {
                 // values and row pointers first, the stores after (see the phase-end park below)
                 bool out[Q];
