@@ -188,6 +188,10 @@ struct gpad_handle_s {
     int plant_batch = 0;                // 0: one plant for the batch; else the dims.batch it was bound for
     bool has_M0 = false, has_g0 = false;
     int plant_n = 0, plant_m = 0, plant_dtype = -1;
+    // exogenous signals (gpad_setup_signals): the plant's maps packed over the augmented state [x; s]
+    int ns = 0;                         // 0: none bound
+    DevBuf sig;                         // [PM SM] n*(nx+ns) | [Pg Sg] m*(nx+ns) | [A E] nx*(nx+ns), each
+                                        // array plant_batch times over when per instance
     DevBuf state;                       // per-state workspaces (M(x), g(x), x ping-pong, ...)
     int num_cus = 256;
     bool timed = false;
@@ -324,6 +328,7 @@ int gpad_destroy(gpad_handle_t h) {
         h->pwork.release();
         h->status.release();
         h->plant.release();
+        h->sig.release();
         h->state.release();
         if (h->ev0) (void)hipEventDestroy(h->ev0);
         if (h->ev1) (void)hipEventDestroy(h->ev1);
@@ -440,6 +445,7 @@ static int setup_impl(gpad_handle_t h, const gpad_dims_t* d, const void* A, cons
     HIP_TRY(hipSetDevice(h->device));
     h->ready = false;
     h->flat = false;
+    h->ns = 0;  // (a new problem unbinds the signals)
     h->shadow_ok = false;
     h->hess_ok = false;
     h->frag64_ok = false;
@@ -583,6 +589,7 @@ int gpad_setup_flat(gpad_handle_t h, const gpad_dims_t* d, int n_u, const float*
         HIP_TRY(hipSetDevice(h->device));
         h->ready = false;
         h->flat = false;
+        h->ns = 0;
         h->shadow_ok = false;
         h->hess_ok = false;
         h->plan.nph = 0;
@@ -1289,6 +1296,19 @@ PlantOffsets plant_offsets(int n, int m, int nx, int nu, size_t copies) {
     o.total = o.B + copies * nx * nu;
     return o;
 }
+struct SigOffsets {
+    size_t PM, Pg, A, total;
+};
+// element offsets of the packed images in Handle::sig (rows of nx + ns columns)
+SigOffsets sig_offsets(int n, int m, int nx, int ns, size_t copies) {
+    SigOffsets o{};
+    const size_t w = (size_t)nx + ns;
+    o.PM = 0;
+    o.Pg = o.PM + copies * n * w;
+    o.A = o.Pg + copies * m * w;
+    o.total = o.A + copies * nx * w;
+    return o;
+}
 }  // namespace
 
 extern "C" int gpad_precompute(gpad_handle_t h, int n, int m, int batch, int shared, int memory, const double* H,
@@ -1386,6 +1406,7 @@ static int setup_plant_impl(gpad_handle_t h, int nx, int nu, const void* PM, con
         (rc = put(o.A, A, (size_t)nx * nx)) || (rc = put(o.B, B, (size_t)nx * nu)))
         return rc;
     HIP_TRY(hipStreamSynchronize(h->stream));
+    h->ns = 0;  // (a new plant unbinds the signals)
     h->nx = nx;
     h->nu = nu;
     h->has_M0 = M0 != nullptr;
@@ -1413,12 +1434,73 @@ extern "C" int gpad_setup_plant_batch(gpad_handle_t h, int nx, int nu, const voi
     });
 }
 
+static bool plant_bound(gpad_handle_t h) {
+    return h->plant_ready && h->plant_n == h->dims.n && h->plant_m == h->dims.m && h->plant_dtype == h->dims.dtype &&
+           !(h->plant_batch && h->plant_batch != h->dims.batch);
+}
+
+// gpad_setup_signals: [PM SM], [Pg Sg], [A E] packed once over the augmented state (zeros for a NULL map)
 template <typename T>
-static int state_typed(gpad_handle_t h, T* x, T* z, T* y, int steps, int N, double tol, int warm,
+static int setup_signals_typed(gpad_handle_t h, int ns, const T* SM, const T* Sg, const T* E) {
+    const int n = h->dims.n, m = h->dims.m, nx = h->nx, nu = h->nu;
+    const size_t copies = h->plant_batch ? (size_t)h->plant_batch : 1;
+    const PlantOffsets o = plant_offsets(n, m, nx, nu, copies);
+    const SigOffsets so = sig_offsets(n, m, nx, ns, copies);
+    int rc;
+    if ((rc = h->sig.ensure(sizeof(T) * so.total))) return rc;
+    const T *dSM = SM, *dSg = Sg, *dE = E;
+    if (h->dims.memory == GPAD_MEM_HOST) {  // staged through the per-run workspace
+        const size_t eSM = copies * n * ns, eSg = copies * m * ns, eE = copies * nx * ns;
+        if ((rc = h->state.ensure(sizeof(T) * (eSM + eSg + eE)))) return rc;
+        T* b = (T*)h->state.p;
+        auto up = [&](const T* src, T* dst, size_t elems) -> int {
+            if (src) HIP_TRY(hipMemcpyAsync(dst, src, sizeof(T) * elems, hipMemcpyHostToDevice, h->stream));
+            return GPAD_OK;
+        };
+        if ((rc = up(SM, b, eSM)) || (rc = up(Sg, b + eSM, eSg)) || (rc = up(E, b + eSM + eSg, eE))) return rc;
+        dSM = SM ? b : nullptr;
+        dSg = Sg ? b + eSM : nullptr;
+        dE = E ? b + eSM + eSg : nullptr;
+    }
+    const T* P = (const T*)h->plant.p;
+    T* I = (T*)h->sig.p;
+    HIP_TRY(gpad::launch_pack_aug<T>(P + o.PM, dSM, I + so.PM, (long long)copies * n, nx, ns, h->stream));
+    HIP_TRY(gpad::launch_pack_aug<T>(P + o.Pg, dSg, I + so.Pg, (long long)copies * m, nx, ns, h->stream));
+    if (h->plant_dyn)
+        HIP_TRY(gpad::launch_pack_aug<T>(P + o.A, dE, I + so.A, (long long)copies * nx, nx, ns, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    h->ns = ns;
+    return GPAD_OK;
+}
+
+extern "C" int gpad_setup_signals(gpad_handle_t h, int ns, const void* SM, const void* Sg, const void* E) {
+    return gpad::abi_guard("gpad_setup_signals", [&]() -> int {
+        if (!h) return fail(GPAD_ERR_INVALID, "gpad_setup_signals: null handle");
+        if (!h->ready || !plant_bound(h))
+            return fail(GPAD_ERR_NOT_SETUP, "gpad_setup_signals: call gpad_setup_plant first");
+        if (ns < 0) return fail(GPAD_ERR_INVALID, "gpad_setup_signals: ns < 0");
+        if (ns == 0) {
+            h->ns = 0;
+            return GPAD_OK;
+        }
+        if (E && !h->plant_dyn) return fail(GPAD_ERR_INVALID, "gpad_setup_signals: E given, plant bound without A, B");
+        HIP_TRY(hipSetDevice(h->device));
+        h->ns = 0;  // (a failed rebinding leaves none)
+        if (h->dims.dtype == GPAD_DTYPE_F64)
+            return setup_signals_typed<double>(h, ns, (const double*)SM, (const double*)Sg, (const double*)E);
+        return setup_signals_typed<float>(h, ns, (const float*)SM, (const float*)Sg, (const float*)E);
+    });
+}
+
+template <typename T>
+static int state_typed(gpad_handle_t h, T* x, T* z, T* y, const T* sg, int steps, int N, double tol, int warm,
                        T* xs, T* us, gpad_stats_t* st) {
     // steps == 0: one solve at x (gpad_run_state); steps >= 1: closed loop (gpad_closed_loop)
     const gpad_dims_t& d = h->dims;
     const int n = d.n, m = d.m, batch = d.batch, nx = h->nx, nu = h->nu;
+    // signals (sg != null): the same run on the augmented state [x; s], rows of nxa = nx + ns columns over
+    // the packed images of gpad_setup_signals; sg is [batch][ns], or [steps][batch][ns] for a loop
+    const int ns = sg ? h->ns : 0, nxa = nx + ns;
     const bool loop = steps > 0;
     const int nsolve = loop ? steps : 1;
     int rc = ensure_schedule(h, N, nullptr, nullptr);
@@ -1426,25 +1508,35 @@ static int state_typed(gpad_handle_t h, T* x, T* z, T* y, int steps, int N, doub
     if ((rc = h->counters.ensure(sizeof(int) * 2 * (size_t)batch * nsolve))) return rc;
     const bool host = d.memory == GPAD_MEM_HOST;
     const size_t zn = (size_t)batch * n, yn = (size_t)batch * m, xn = (size_t)batch * nx;
+    const size_t xan = (size_t)batch * nxa;  // a row of the x ping-pong: [x; s] with signals
     const size_t xsn = loop && xs ? (size_t)steps * xn : 0, usn = loop && us ? (size_t)steps * batch * nu : 0;
-    // workspace: M(x) | g(x) | x ping | x pong | (host) z | y | xs | us
-    size_t elems = zn + yn + 2 * xn;
-    if (host) elems += zn + yn + xsn + usn;
+    const size_t sn = (size_t)nsolve * batch * ns;
+    // workspace: M(x) | g(x) | x ping | x pong | (signals) x in / out | (host) z | y | xs | us | S
+    size_t elems = zn + yn + 2 * xan + (ns ? xn : 0);
+    if (host) elems += zn + yn + xsn + usn + sn;
     if ((rc = h->state.ensure(sizeof(T) * elems))) return rc;
     T* Mx = (T*)h->state.p;
     T* gx = Mx + zn;
     T* xa = gx + yn;
-    T* xb = xa + xn;
+    T* xb = xa + xan;
+    T* xd = ns ? xb + xan : nullptr;  // signals: the dense [batch][nx] states in, then out
+    T* wend = xb + xan + (ns ? xn : 0);
     T *dz = z, *dy = y, *dxs = xs, *dus = us;
+    const T* dS = sg;
     if (host) {
-        dz = xb + xn;
+        dz = wend;
         dy = dz + zn;
         dxs = xsn ? dy + yn : nullptr;
         dus = usn ? dy + yn + xsn : nullptr;
+        if (ns) {
+            T* up = dy + yn + xsn + usn;
+            HIP_TRY(hipMemcpyAsync(up, sg, sizeof(T) * sn, hipMemcpyHostToDevice, h->stream));
+            dS = up;
+        }
     }
     const hipMemcpyKind in_kind = host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
     const hipMemcpyKind out_kind = host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
-    HIP_TRY(hipMemcpyAsync(xa, x, sizeof(T) * xn, in_kind, h->stream));
+    HIP_TRY(hipMemcpyAsync(ns ? xd : xa, x, sizeof(T) * xn, in_kind, h->stream));
     if (host && (!loop || warm)) {
         HIP_TRY(hipMemcpyAsync(dz, z, sizeof(T) * zn, hipMemcpyHostToDevice, h->stream));
         HIP_TRY(hipMemcpyAsync(dy, y, sizeof(T) * yn, hipMemcpyHostToDevice, h->stream));
@@ -1452,6 +1544,12 @@ static int state_typed(gpad_handle_t h, T* x, T* z, T* y, int steps, int N, doub
     const bool per_plant = h->plant_batch != 0;  // per-instance maps (gpad_setup_plant_batch)
     const PlantOffsets o = plant_offsets(n, m, nx, nu, per_plant ? (size_t)batch : 1);
     const T* P = (const T*)h->plant.p;
+    // the maps the run reads: the plant's, or with signals their packed images [PM SM], [Pg Sg], [A E]
+    const SigOffsets so = sig_offsets(n, m, nx, ns, per_plant ? (size_t)batch : 1);
+    const T* I = (const T*)h->sig.p;
+    const T* mPM = ns ? I + so.PM : P + o.PM;
+    const T* mPg = ns ? I + so.Pg : P + o.Pg;
+    const T* mA = ns ? I + so.A : P + o.A;
     int* counters = (int*)h->counters.p;
     int kernel = 0;
     const double margin = sizeof(T) == sizeof(float) ? gpad::ViolMargin<float>::value : gpad::ViolMargin<double>::value;
@@ -1465,7 +1563,7 @@ static int state_typed(gpad_handle_t h, T* x, T* z, T* y, int steps, int N, doub
         // (per-instance matrices: its solo variant, where the resident kernel holds the shape)
         async = loop && h->tune.loop_async && !h->flat && !h->hess_ok && N >= 1 &&
                 (d.kernel == GPAD_KERNEL_AUTO || d.kernel == GPAD_KERNEL_RESIDENT) &&
-                gpad::loop_supported(n, m, nx, nu);
+                gpad::loop_supported(n, m, nxa, nu);
         if (async) {
             if ((rc = h->q64.ensure(sizeof(int)))) return rc;
             gpad::LoopArgs la{};
@@ -1495,14 +1593,16 @@ static int state_typed(gpad_handle_t h, T* x, T* z, T* y, int steps, int N, doub
             a.qctr = static_cast<int*>(h->q64.p);
             a.tune = &h->tune;
             a.err = (int*)h->status.p;
-            la.PM = P + o.PM;
+            la.PM = mPM;
             la.M0 = h->has_M0 ? P + o.M0 : nullptr;
-            la.Pg = P + o.Pg;
+            la.Pg = mPg;
             la.g0 = h->has_g0 ? P + o.g0 : nullptr;
-            la.A = P + o.A;
+            la.A = mA;
             la.B = P + o.B;
-            la.x_in = xa;
-            la.x_out = xb;
+            la.x_in = ns ? xd : xa;  // (dense rows of nx either way; the kernel reads S itself)
+            la.x_out = ns ? xa : xb;
+            la.ns = ns;
+            la.S = ns ? dS : nullptr;
             la.xs = dxs;
             la.us = dus;
             la.gmax = tol > 0.0 ? reinterpret_cast<double*>((char*)h->status.p + (nsolve > 1 ? offsetof(RunStatus, acc)
@@ -1524,13 +1624,14 @@ static int state_typed(gpad_handle_t h, T* x, T* z, T* y, int steps, int N, doub
             h->last_phased = false;
             h->last_p64 = false;
             h->last_N = N;
-            xc = xb;
+            xc = ns ? xa : xb;
         }
     }
     if (!async) HIP_TRY(hipEventRecord(h->ev0, h->stream));
+    if (!async && ns) HIP_TRY(gpad::launch_sig_state<T>(xd, dS, xa, nx, ns, batch, h->stream));  // [x_0; S[0]]
     for (int t = 0; t < nsolve && !async; ++t) {
-        HIP_TRY(gpad::launch_affine2<T>(P + o.PM, h->has_M0 ? P + o.M0 : nullptr, n, Mx, P + o.Pg,
-                                        h->has_g0 ? P + o.g0 : nullptr, m, gx, xc, nx, batch, per_plant, h->stream));
+        HIP_TRY(gpad::launch_affine2<T>(mPM, h->has_M0 ? P + o.M0 : nullptr, n, Mx, mPg,
+                                        h->has_g0 ? P + o.g0 : nullptr, m, gx, xc, nxa, batch, per_plant, h->stream));
         if (loop && !warm) {  // acceldualgrad.m:16-17: every MPC step starts from z = y = 0
             HIP_TRY(hipMemsetAsync(dz, 0, sizeof(T) * zn, h->stream));
             HIP_TRY(hipMemsetAsync(dy, 0, sizeof(T) * yn, h->stream));
@@ -1544,13 +1645,22 @@ static int state_typed(gpad_handle_t h, T* x, T* z, T* y, int steps, int N, doub
                                              reinterpret_cast<double*>(sp + offsetof(RunStatus, acc)), t == 0,
                                              h->stream));
         }
-        if (loop) {  // gpad.m:91-94: u = z*(1:nu); x <- A x + B u
+        if (loop && ns) {  // x <- A x + E S[t] + B u, with S[t + 1] moved in beside it
+            const bool last = t + 1 == nsolve;
+            HIP_TRY(gpad::launch_plant_step_sig<T>(mA, P + o.B, xc, dz, n, xnext,
+                                                   last ? nullptr : dS + (size_t)(t + 1) * batch * ns, nx, ns, nu,
+                                                   batch, dxs ? dxs + (size_t)t * xn : nullptr,
+                                                   dus ? dus + (size_t)t * batch * nu : nullptr,
+                                                   last ? xd : nullptr, per_plant, h->stream));
+            std::swap(xc, xnext);
+        } else if (loop) {  // gpad.m:91-94: u = z*(1:nu); x <- A x + B u
             HIP_TRY(gpad::launch_plant_step<T>(P + o.A, P + o.B, xc, dz, n, xnext, nx, nu, batch,
                                                dxs ? dxs + (size_t)t * xn : nullptr,
                                                dus ? dus + (size_t)t * batch * nu : nullptr, per_plant, h->stream));
             std::swap(xc, xnext);
         }
     }
+    if (ns && !async) xc = xd;  // (the last step wrote the dense states there)
     HIP_TRY(hipEventRecord(h->ev1, h->stream));
     h->timed = true;
     h->last_kernel = kernel;
@@ -1568,23 +1678,27 @@ static int state_typed(gpad_handle_t h, T* x, T* z, T* y, int steps, int N, doub
     return GPAD_OK;
 }
 
-static int state_impl(gpad_handle_t h, void* x, void* z, void* y, int steps, int N, double tol, int warm,
-                      void* xs, void* us, gpad_stats_t* st, const char* where) {
+// with_sig: the _signals entry points (sg: their s / S)
+static int state_impl(gpad_handle_t h, void* x, void* z, void* y, const void* sg, bool with_sig, int steps, int N,
+                      double tol, int warm, void* xs, void* us, gpad_stats_t* st, const char* where) {
     if (!h) return fail(GPAD_ERR_INVALID, std::string(where) + ": null handle");
     if (!h->ready) return fail(GPAD_ERR_NOT_SETUP, std::string(where) + ": call gpad_setup first");
-    if (!h->plant_ready || h->plant_n != h->dims.n || h->plant_m != h->dims.m ||
-        h->plant_dtype != h->dims.dtype || (h->plant_batch && h->plant_batch != h->dims.batch))
+    if (!plant_bound(h))
         return fail(GPAD_ERR_NOT_SETUP, std::string(where) + ": call gpad_setup_plant after gpad_setup");
+    if (with_sig && h->ns == 0)
+        return fail(GPAD_ERR_NOT_SETUP, std::string(where) + ": call gpad_setup_signals first");
+    if (!with_sig && h->ns != 0)  // (dropping a disturbance silently is worse than an error)
+        return fail(GPAD_ERR_INVALID, std::string(where) + ": signals are bound, call the _signals entry point");
     if (steps > 0 && !h->plant_dyn)
         return fail(GPAD_ERR_NOT_SETUP, std::string(where) + ": plant bound without A, B");
-    if (!x || !z || !y) return fail(GPAD_ERR_INVALID, std::string(where) + ": null vector");
+    if (!x || !z || !y || (with_sig && !sg)) return fail(GPAD_ERR_INVALID, std::string(where) + ": null vector");
     if (N < 0 || steps < 0) return fail(GPAD_ERR_INVALID, std::string(where) + ": N, steps must be >= 0");
     if (!(tol <= 0.0) && !std::isfinite(tol)) return fail(GPAD_ERR_INVALID, std::string(where) + ": bad tol");
     HIP_TRY(hipSetDevice(h->device));
     if (h->dims.dtype == GPAD_DTYPE_F64)
-        return state_typed<double>(h, (double*)x, (double*)z, (double*)y, steps, N, tol, warm, (double*)xs,
-                                   (double*)us, st);
-    return state_typed<float>(h, (float*)x, (float*)z, (float*)y, steps, N, tol, warm, (float*)xs,
+        return state_typed<double>(h, (double*)x, (double*)z, (double*)y, (const double*)sg, steps, N, tol, warm,
+                                   (double*)xs, (double*)us, st);
+    return state_typed<float>(h, (float*)x, (float*)z, (float*)y, (const float*)sg, steps, N, tol, warm, (float*)xs,
                               (float*)us, st);
 }
 
@@ -1593,8 +1707,16 @@ extern "C" {
 int gpad_run_state(gpad_handle_t h, const void* x, void* z0, void* y0, int N, double tol,
                    gpad_stats_t* st) {
     return gpad::abi_guard("gpad_run_state", [&]() -> int {
-        return state_impl(h, const_cast<void*>(x), z0, y0, 0, N, tol, 1, nullptr, nullptr, st,
+        return state_impl(h, const_cast<void*>(x), z0, y0, nullptr, false, 0, N, tol, 1, nullptr, nullptr, st,
                           "gpad_run_state");
+    });
+}
+
+int gpad_run_state_signals(gpad_handle_t h, const void* x, const void* s, void* z0, void* y0, int N, double tol,
+                           gpad_stats_t* st) {
+    return gpad::abi_guard("gpad_run_state_signals", [&]() -> int {
+        return state_impl(h, const_cast<void*>(x), z0, y0, s, true, 0, N, tol, 1, nullptr, nullptr, st,
+                          "gpad_run_state_signals");
     });
 }
 
@@ -1602,7 +1724,15 @@ int gpad_closed_loop(gpad_handle_t h, void* x, void* z, void* y, int steps, int 
                      void* xs, void* us, gpad_stats_t* st) {
     return gpad::abi_guard("gpad_closed_loop", [&]() -> int {
         if (steps == 0) return GPAD_OK;
-        return state_impl(h, x, z, y, steps, N, tol, warm, xs, us, st, "gpad_closed_loop");
+        return state_impl(h, x, z, y, nullptr, false, steps, N, tol, warm, xs, us, st, "gpad_closed_loop");
+    });
+}
+
+int gpad_closed_loop_signals(gpad_handle_t h, void* x, void* z, void* y, const void* S, int steps, int N, double tol,
+                             int warm, void* xs, void* us, gpad_stats_t* st) {
+    return gpad::abi_guard("gpad_closed_loop_signals", [&]() -> int {
+        if (steps == 0) return GPAD_OK;
+        return state_impl(h, x, z, y, S, true, steps, N, tol, warm, xs, us, st, "gpad_closed_loop_signals");
     });
 }
 

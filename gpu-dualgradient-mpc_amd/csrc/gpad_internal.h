@@ -165,7 +165,13 @@ struct LoopArgs {
                            // unused slots zeroed; null: not wanted
     int nx, nu, steps, warm;
     int per_plant;         // 1: the six maps are per pack (gpad_setup_plant_batch), 0: one plant
+    // exogenous signals (gpad_setup_signals; ns == 0: none, S unused).  PM, Pg, A are then the packed
+    // images over the augmented state [x; s]: [n][nx + ns] = [PM SM], [m][nx + ns] = [Pg Sg],
+    // [nx][nx + ns] = [A E]; the slot's LDS state row holds [x_t; S[t][pack]]
+    int ns;
+    const float* S;        // [steps][batch][ns]
 };
+// nx: columns of the state row, nx + ns with signals bound
 bool loop_supported(int n, int m, int nx, int nu);
 // workgroups of a's kernel that fit one CU by the runtime's occupancy figure, clamped to [1, 2]
 // (always 1 for the two-slot kernel, whose grid is one workgroup per CU)
@@ -266,6 +272,19 @@ hipError_t launch_affine2(const T* P1, const T* c1, int rows1, T* out1, const T*
 template <typename T>
 hipError_t launch_plant_step(const T* A, const T* B, const T* x, const T* z, long long ldz, T* xn, int nx,
                              int nu, int batch, T* xs, T* us, bool per_instance, hipStream_t s);
+// exogenous signals (gpad_setup_signals): the binding on the augmented state [x; s], rows of nx + ns.
+// out = [P S] row by row over rows_total = copies * rows rows (S null: zeros)
+template <typename T>
+hipError_t launch_pack_aug(const T* P, const T* S, T* out, long long rows_total, int nx, int ns, hipStream_t s);
+// xt[b] = [x[b]; sg[b]]
+template <typename T>
+hipError_t launch_sig_state(const T* x, const T* sg, T* xt, int nx, int ns, int batch, hipStream_t s);
+// launch_plant_step over [x; s] rows with AE = [A E] ([nx][nx + ns]): xtn = [x+; sn] (sn null: the
+// signal columns are left alone), xs / xo (nullable) receive x and x+ as dense rows of nx
+template <typename T>
+hipError_t launch_plant_step_sig(const T* AE, const T* B, const T* xt, const T* z, long long ldz, T* xtn,
+                                 const T* sn, int nx, int ns, int nu, int batch, T* xs, T* us, T* xo,
+                                 bool per_instance, hipStream_t s);
 
 // gpad_flat.hip (flat battery path; MGt = flat -ML [Nh][m], GLt = flat G_L t-major [Nh][m])
 hipError_t launch_flat(const SolveArgs<float>& a, hipStream_t s);

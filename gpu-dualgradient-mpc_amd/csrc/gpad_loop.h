@@ -33,6 +33,12 @@ namespace gpad {
 // their order with explicit fmas.  Results, counts and codes are therefore bit-identical to the
 // lockstep loop.
 //
+// Exogenous signals (LoopArgs::ns, S; gpad_setup_signals): the state row of a slot is [x_t; S[t][pack]],
+// the maps are the packed images [PM SM], [Pg Sg], [A E] with rows of nx + ns columns, and the same
+// chains run over nx + ns columns -- today's binding on the augmented state.  The signal lanes
+// (nx <= tid < nx + ns) load their words at the start of every step (loop_start), for a refill and
+// for a pack's next step alike; nothing of S or ns is held across the solve loop.
+//
 // Per-pack plant maps (LoopArgs::per_plant, gpad_setup_plant_batch): a slot reads the P, A, B rows of
 // its own pack -- the instance index of row_ld, 0 for one shared plant.  Per-pack matrices
 // (SolveArgs::strideA/strideB != 0, a fleet of distinct plants) run gpad_loop_fleet_kernel below.
@@ -51,7 +57,8 @@ __device__ __forceinline__ LoopKernArgs& largs() {
 
 // LDS of the step boundaries
 struct LoopLds {
-    float x[2][2][64];   // per slot: x_t at [t & 1], x_{t+1} written to the other half
+    float x[2][2][64];   // per slot: [x_t; s_t] at [t & 1] (s_t = S[t][pack], gpad_setup_signals; nx + ns
+                         // <= 64), x_{t+1} written to the other half
     float u[64];         // u = z*[0:nu] of the slot at its boundary
     float gm[kResidentMaxThreads];  // per lane: NaN-keeping max |g| of every g row it formed
 };
@@ -65,6 +72,15 @@ __device__ __forceinline__ float loop_affine(const float* P, const float* c0, si
 #pragma unroll 1
     for (int k = 0; k < nx; ++k) acc = __builtin_fmaf(row_ld(P, pi, rows * nx, o4 + 4 * k), x_l[k], acc);
     return acc;
+}
+
+// Lane tid in [nx, nx + ns) reads word tid - nx of row `row` of the signals S ([rows][ns]): the row's
+// descriptor starts nx words early, so the lane's offset is the 4 tid its state accesses already hold
+// (no per-lane subtraction); lanes below nx must not call (their words lie before the row).
+__device__ __forceinline__ float loop_sig_ld(const float* S, size_t row, int ns, int nx, int tid4) {
+    const char* base = reinterpret_cast<const char*>(S) + 4 * (row * (size_t)ns) - 4 * (size_t)nx;
+    return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(
+        __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(base), 0, 4 * (nx + ns), 0x00020000), tid4, 0, 0));
 }
 
 // What a kernel is compiled for.  The shared-plant two-slot kernel is at its register budget (an
@@ -107,7 +123,7 @@ __device__ __forceinline__ void loop_rows(const DuoCtx& c, int p, float (&r)[K])
 // Uniform, contains barriers.
 template <int KB, int K, int MODE>
 __device__ __forceinline__ void loop_start(const SolveArgs<float>& a, const DuoCtx& c, LoopSlot& s, float v0,
-                                           const float* x_l, float* w_l, float* gp_l, float* pd_l, float* z_l,
+                                           float* x_l, float* w_l, float* gp_l, float* pd_l, float* z_l,
                                            float* gm_l, const float (&r)[K]) {
     s.vs = 0;
     s.kc = c.Kc;
@@ -115,14 +131,20 @@ __device__ __forceinline__ void loop_start(const SolveArgs<float>& a, const DuoC
     s.th = sched(a.theta, 0);
     s.bn = sched(a.beta, 1);
     s.x0 = s.x1 = s.x2 = 0.0f;
+    if (largs().ns) {  // the step's signals beside its state: x_l = [x_t; S[t][pack]]
+        LoopKernArgs& A = largs();
+        if (c.tid >= A.nx && c.tid < A.nx + A.ns)
+            x_l[c.tid] = loop_sig_ld(A.S, (size_t)s.t * (size_t)c.count + (size_t)s.pos, A.ns, A.nx, 4 * c.tid);
+        __syncthreads();
+    }
     if (c.live) {
         LoopKernArgs& A = largs();
         if (c.isA) {
-            gp_l[c.row] = loop_affine(A.PM, A.M0, loop_plant_of<MODE>(A, s.pos), c.n, c.row, A.nx, x_l);
+            gp_l[c.row] = loop_affine(A.PM, A.M0, loop_plant_of<MODE>(A, s.pos), c.n, c.row, A.nx + A.ns, x_l);
             s.x0 = v0;
             if (c.use_tol) z_l[c.row] = v0;
         } else {
-            const float gv = loop_affine(A.Pg, A.g0, loop_plant_of<MODE>(A, s.pos), c.m, c.row, A.nx, x_l);
+            const float gv = loop_affine(A.Pg, A.g0, loop_plant_of<MODE>(A, s.pos), c.m, c.row, A.nx + A.ns, x_l);
             gm_l[c.tid] = absmax_nan(gm_l[c.tid], gv);
             pd_l[c.row] = (float)(A.s.gscale * (double)gv);
             s.x0 = v0;
@@ -214,11 +236,12 @@ __device__ __forceinline__ void loop_post_b(const SolveArgs<float>& a, const Duo
         }
         if (c.tid < nx && A.xs) row_st(A.xs, tb, nx, 4 * c.tid, xc[c.tid]);
         __syncthreads();  // u_l published
-        if (c.tid < nx) {  // plant_step_kernel's order: A x first, then B u, one fma chain
+        if (c.tid < nx) {  // plant_step_kernel's order: A x (then E s_t: the row is [A E]), then B u, one fma chain
             float acc = 0.0f;
-            const int oa = 4 * c.tid * nx, ob = 4 * c.tid * nu;
+            const int nxa = nx + A.ns;
+            const int oa = 4 * c.tid * nxa, ob = 4 * c.tid * nu;
 #pragma unroll 1
-            for (int k = 0; k < nx; ++k) acc = __builtin_fmaf(row_ld(A.A, pi, nx * nx, oa + 4 * k), xc[k], acc);
+            for (int k = 0; k < nxa; ++k) acc = __builtin_fmaf(row_ld(A.A, pi, nx * nxa, oa + 4 * k), xc[k], acc);
 #pragma unroll 1
             for (int j = 0; j < nu; ++j) acc = __builtin_fmaf(row_ld(A.B, pi, nx * nu, ob + 4 * j), u_l[j], acc);
             xn[c.tid] = acc;

@@ -30,7 +30,7 @@ int loop_blocks_per_cu(const LoopArgs& a) {
 
 hipError_t launch_loop(const LoopArgs& a, int grid, hipStream_t st) {
     const SolveArgs<float>& s = a.s;
-    if (!loop_supported(s.n, s.m, a.nx, a.nu) || !s.qctr || s.N < 1 || a.steps < 1 || s.batch < 1 || grid < 1 ||
+    if (!loop_supported(s.n, s.m, a.nx + a.ns, a.nu) || a.nx < 1 || a.ns < 0 || (a.ns && !a.S) || !s.qctr || s.N < 1 || a.steps < 1 || s.batch < 1 || grid < 1 ||
         grid > s.batch || grid > kAbsmaxMaxBlocks)
         return hipErrorInvalidValue;
     hipLaunchKernelGGL(loop_fn(a), dim3(grid), dim3(loop_threads(s)), 0, st, a);

@@ -97,6 +97,114 @@ static dim3 grid_for(long long total) {
     return dim3((unsigned)blocks);
 }
 
+// ---- exogenous signals (gpad_setup_signals) ------------------------------------------------
+// The binding with signals is the plain binding on the augmented state x~ = [x; s]: the maps are
+// packed once into images with rows of nx + ns columns, [P S] (zeros where S is absent, so a NULL map's
+// terms are evaluated), affine2_kernel runs over x~ as it stands, and the step below is
+// plant_step_kernel with a row stride of nx + ns that also moves the next step's signals in.
+
+// out[c][i][0:nx] = P[c][i][:], out[c][i][nx:nx+ns] = S[c][i][:] (or zeros), c < copies, i < rows
+template <typename T>
+__global__ __launch_bounds__(256) void pack_aug_kernel(const T* __restrict__ P, const T* __restrict__ S,
+                                                       T* __restrict__ out, long long rows_total, int nx, int ns) {
+    const int nxa = nx + ns;
+    const long long total = rows_total * nxa;
+    for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < total;
+         t += (long long)gridDim.x * blockDim.x) {
+        const long long r = t / nxa;
+        const int k = (int)(t - r * nxa);
+        out[t] = k < nx ? P[r * nx + k] : (S ? S[r * ns + (k - nx)] : T(0));
+    }
+}
+
+// xt[b] = [x[b]; s[b]] (rows of nx + ns)
+template <typename T>
+__global__ __launch_bounds__(256) void sig_state_kernel(const T* __restrict__ x, const T* __restrict__ s,
+                                                        T* __restrict__ xt, int nx, int ns, int batch) {
+    const int nxa = nx + ns;
+    const long long total = (long long)batch * nxa;
+    for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < total;
+         t += (long long)gridDim.x * blockDim.x) {
+        const long long b = t / nxa;
+        const int k = (int)(t - b * nxa);
+        xt[t] = k < nx ? x[b * nx + k] : s[b * ns + (k - nx)];
+    }
+}
+
+// xt, xtn: [batch][nx + ns] = [x; s].  xtn[b][0:nx] = [A E] xt[b] + B z[b][0:nu] (one chain: the A x
+// terms, the E s terms, the B u terms), xtn[b][nx:] = sn[b] (the next step's signals; null after the
+// last step: left alone).  xs[b] = x[b] and xo[b] = x+ are dense rows of nx, us[b] = z[b][0:nu]; all
+// three optional.  AE: [nx][nx + ns] per copy.
+template <typename T>
+__global__ __launch_bounds__(256) void plant_step_sig_kernel(const T* __restrict__ AE, const T* __restrict__ B,
+                                                             long long sA, long long sB,
+                                                             const T* __restrict__ xt, const T* __restrict__ z,
+                                                             long long ldz, T* __restrict__ xtn,
+                                                             const T* __restrict__ sn, int nx, int ns, int nu,
+                                                             int batch, T* __restrict__ xs, T* __restrict__ us,
+                                                             T* __restrict__ xo) {
+    const int nxa = nx + ns;
+    const int per = nxa > nu ? nxa : nu;
+    const long long total = (long long)batch * per;
+    for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < total;
+         t += (long long)gridDim.x * blockDim.x) {
+        const int b = (int)(t / per);
+        const int i = (int)(t - (long long)b * per);
+        const T* xb = xt + (long long)b * nxa;
+        const T* ub = z + (long long)b * ldz;
+        if (i < nx) {
+            T acc = T(0);
+            const T* Ai = AE + b * sA + (long long)i * nxa;
+            for (int k = 0; k < nxa; ++k) acc = __builtin_fma(Ai[k], xb[k], acc);
+            const T* Bi = B + b * sB + (long long)i * nu;
+            for (int j = 0; j < nu; ++j) acc = __builtin_fma(Bi[j], ub[j], acc);
+            xtn[(long long)b * nxa + i] = acc;
+            if (xo) xo[(long long)b * nx + i] = acc;
+            if (xs) xs[(long long)b * nx + i] = xb[i];
+        } else if (i < nxa && sn) {
+            xtn[(long long)b * nxa + i] = sn[(long long)b * ns + (i - nx)];
+        }
+        if (i < nu && us) us[(long long)b * nu + i] = ub[i];
+    }
+}
+
+template <typename T>
+hipError_t launch_pack_aug(const T* P, const T* S, T* out, long long rows_total, int nx, int ns, hipStream_t s) {
+    if (rows_total <= 0) return hipSuccess;
+    hipLaunchKernelGGL(pack_aug_kernel<T>, grid_for(rows_total * (nx + ns)), dim3(256), 0, s, P, S, out, rows_total,
+                       nx, ns);
+    return hipGetLastError();
+}
+
+template <typename T>
+hipError_t launch_sig_state(const T* x, const T* sg, T* xt, int nx, int ns, int batch, hipStream_t s) {
+    hipLaunchKernelGGL(sig_state_kernel<T>, grid_for((long long)batch * (nx + ns)), dim3(256), 0, s, x, sg, xt, nx,
+                       ns, batch);
+    return hipGetLastError();
+}
+
+template <typename T>
+hipError_t launch_plant_step_sig(const T* AE, const T* B, const T* xt, const T* z, long long ldz, T* xtn,
+                                 const T* sn, int nx, int ns, int nu, int batch, T* xs, T* us, T* xo,
+                                 bool per_instance, hipStream_t s) {
+    const int nxa = nx + ns, per = nxa > nu ? nxa : nu;
+    const long long p = per_instance ? 1 : 0;
+    hipLaunchKernelGGL(plant_step_sig_kernel<T>, grid_for((long long)batch * per), dim3(256), 0, s, AE, B,
+                       p * nx * nxa, p * nx * nu, xt, z, ldz, xtn, sn, nx, ns, nu, batch, xs, us, xo);
+    return hipGetLastError();
+}
+
+template hipError_t launch_pack_aug<float>(const float*, const float*, float*, long long, int, int, hipStream_t);
+template hipError_t launch_pack_aug<double>(const double*, const double*, double*, long long, int, int, hipStream_t);
+template hipError_t launch_sig_state<float>(const float*, const float*, float*, int, int, int, hipStream_t);
+template hipError_t launch_sig_state<double>(const double*, const double*, double*, int, int, int, hipStream_t);
+template hipError_t launch_plant_step_sig<float>(const float*, const float*, const float*, const float*, long long,
+                                                 float*, const float*, int, int, int, int, float*, float*, float*,
+                                                 bool, hipStream_t);
+template hipError_t launch_plant_step_sig<double>(const double*, const double*, const double*, const double*,
+                                                  long long, double*, const double*, int, int, int, int, double*,
+                                                  double*, double*, bool, hipStream_t);
+
 template <typename T>
 hipError_t launch_affine2(const T* P1, const T* c1, int rows1, T* out1, const T* P2, const T* c2,
                           int rows2, T* out2, const T* x, int nx, int batch, bool per_instance, hipStream_t s) {

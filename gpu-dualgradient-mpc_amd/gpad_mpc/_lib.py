@@ -41,6 +41,7 @@ EXPORTS = [
     "gpad_solve_sharded", "gpad_device_count", "gpad_group_set_stream",
     "gpad_setup_hessian", "gpad_release_cached", "gpad_phase_counts", "gpad_last_phases",
     "gpad_group_rccl_library",
+    "gpad_setup_signals", "gpad_run_state_signals", "gpad_closed_loop_signals",
 ]
 GROUP_RCCL, GROUP_PEER = 1, 2
 
@@ -181,6 +182,12 @@ def load(path: str | None = None) -> C.CDLL:
     L.gpad_setup_plant_batch.argtypes = [vp, i, i, cvp, cvp, cvp, cvp, cvp, cvp]
     L.gpad_run_state.argtypes = [vp, cvp, vp, vp, i, d, C.POINTER(Stats)]
     L.gpad_closed_loop.argtypes = [vp, vp, vp, vp, i, i, d, i, vp, vp, C.POINTER(Stats)]
+    if hasattr(L, "gpad_setup_signals"):  # (added within 0.6; absent from older builds under GPAD_LIB_TOLERANT)
+        L.gpad_setup_signals.argtypes = [vp, i, cvp, cvp, cvp]
+        L.gpad_run_state_signals.argtypes = [vp, cvp, cvp, vp, vp, i, d, C.POINTER(Stats)]
+        L.gpad_closed_loop_signals.argtypes = [vp, vp, vp, vp, cvp, i, i, d, i, vp, vp, C.POINTER(Stats)]
+        for name in ("gpad_setup_signals", "gpad_run_state_signals", "gpad_closed_loop_signals"):
+            getattr(L, name).restype = i
     L.gpad_datafile_read.argtypes = [C.c_char_p, i, C.POINTER(DataFile)]
     L.gpad_datafile_write.argtypes = [C.c_char_p, i, C.POINTER(DataFile)]
     L.gpad_datafile_free.argtypes = [C.POINTER(DataFile)]

@@ -146,10 +146,21 @@ class Plant:
     B: np.ndarray   # nx x nu
     M0: np.ndarray | None = None  # n
     g0: np.ndarray | None = None  # m
+    # exogenous signals s (gpad_setup_signals): M += SM s, g += Sg s, x+ += E s
+    SM: np.ndarray | None = None  # n x ns
+    Sg: np.ndarray | None = None  # m x ns
+    E: np.ndarray | None = None   # nx x ns
 
     @property
     def nx(self) -> int:
         return self.PM.shape[-1]
+
+    @property
+    def ns(self) -> int:
+        for a in (self.SM, self.Sg, self.E):
+            if a is not None:
+                return a.shape[-1]
+        return 0
 
     @property
     def nu(self) -> int:
@@ -173,6 +184,39 @@ def battery_plant(n_u: int = 4, N: int = 10, xmax: float = 0.5, xmin: float = -0
     Pg = np.vstack([-M_ak, M_ak, z, z, np.zeros((N, n_u)), np.zeros((N, n_u))])
     plant = Plant(PM=PM, Pg=Pg, A=mats["A"], B=mats["B"], M0=None, g0=b0)
     qp.meta = dict(kind="battery_plant", n_u=n_u, N=N)
+    return qp, plant
+
+
+def battery_plant_signals(n_u: int = 4, N: int = 10, **limits):
+    """``battery_plant`` under load and with state-of-charge references: (QP, Plant) with the signal
+    maps of ``gpad_setup_signals`` for s = [i_load, r_1 .. r_{n_u}] (ns = 1 + n_u).
+
+    i_load is a load current through every cell, held over the horizon: x+ = A x + B u + E_l i_load with
+    E_l = B 1, so the predicted states gain M_e i_load, M_e stacking sum_{j<k} A^j E_l for k = 1..N.
+    r holds per-cell references, held over the horizon (T = N stacked identities): the cost is
+    (X - R)' Mx (X - R) + z' Mu z with R = T r.  Hence
+        SM = H^-1 M_ab' Mx [M_e, -T],   Sg = [[-M_e, 0]; [M_e, 0]; 0; 0; 0; 0],   E = [E_l, 0].
+    With s = 0 everything else is ``battery_plant``'s, bit for bit.  ``limits``: as battery_plant."""
+    qp, plant = battery_plant(n_u, N, **limits)
+    mats = battery_matrices(n_u, N, limits.get("capacity_ah", 0.027 * 4.1))
+    A, B, M_ab = mats["A"], mats["B"], mats["M_ab"]
+    E_l = B @ np.ones((n_u, 1))
+    M_e = np.zeros((n_u * N, 1))
+    acc = np.zeros((n_u, 1))
+    for k in range(1, N + 1):  # sum_{j<k} A^j E_l
+        acc = acc + np.linalg.matrix_power(A, k - 1) @ E_l
+        M_e[(k - 1) * n_u:k * n_u] = acc
+    T = np.tile(np.eye(n_u), (N, 1))
+    Mx = 100.0 * np.eye(n_u * N)  # battery_matrices' qx
+    Hinv = np.linalg.inv(mats["H"])
+    plant.SM = Hinv @ M_ab.T @ Mx @ np.hstack([M_e, -T])
+    zc = np.zeros((n_u * N, n_u))
+    Sg = np.zeros((qp.m, 1 + n_u))
+    Sg[:n_u * N] = np.hstack([-M_e, zc])
+    Sg[n_u * N:2 * n_u * N] = np.hstack([M_e, zc])
+    plant.Sg = Sg
+    plant.E = np.hstack([E_l, np.zeros((n_u, n_u))])
+    qp.meta = dict(kind="battery_plant_signals", n_u=n_u, N=N)
     return qp, plant
 
 

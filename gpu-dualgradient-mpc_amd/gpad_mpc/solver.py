@@ -310,16 +310,38 @@ class GpadSolver:
         fn = "gpad_setup_plant_batch" if stacked else "gpad_setup_plant"
         check(getattr(self.lib, fn)(self.h, nx, nu, _ptr(PM), opt(M0), _ptr(Pg), opt(g0), opt(A), opt(B)), fn)
 
-    def run_state(self, x, z, y, N: int, tol: float = 0.0, *, stats: bool = True):
-        """GPAD for every instance's state x [batch][nx] (M(x), g(x) formed on the device)."""
+    def setup_signals(self, SM=None, Sg=None, E=None, *, ns: int | None = None) -> None:
+        """Bind exogenous signals s (ns) on top of the plant (gpad_setup_signals):
+        M(x, s) = M0 + PM x + SM s, g(x, s) = g0 + Pg x + Sg s, x+ = A x + E s + B u.
+        SM (n, ns), Sg (m, ns), E (nx, ns) -- each with a leading batch axis after a stacked
+        ``setup_plant`` -- in the dtype / memory kind of ``setup``; None is a map of zeros.  ``ns`` is
+        read from the maps given, so it is needed only when all three are None; ``ns=0`` unbinds.
+        Then pass ``s=`` to ``run_state`` and ``signals=`` to ``closed_loop``."""
+        given = [a for a in (SM, Sg, E) if a is not None]
+        if ns is None:
+            if not given:
+                raise ValueError("setup_signals: give a map or ns")
+            ns = given[0].shape[-1]
+        if any(a.shape[-1] != ns for a in given):
+            raise ValueError(f"setup_signals: every map needs {ns} columns")
+        opt = lambda a: _ptr(a) if a is not None else None  # noqa: E731
+        check(self.lib.gpad_setup_signals(self.h, int(ns), opt(SM), opt(Sg), opt(E)), "gpad_setup_signals")
+
+    def run_state(self, x, z, y, N: int, tol: float = 0.0, *, stats: bool = True, s=None):
+        """GPAD for every instance's state x [batch][nx] (M(x), g(x) formed on the device); with
+        signals bound (``setup_signals``), ``s`` [batch][ns] is required."""
         st = Stats()
         want = stats or not _is_torch(z)
-        check(self.lib.gpad_run_state(self.h, _ptr(x), _ptr(z), _ptr(y), int(N), float(tol),
-                                      C.byref(st) if want else None), "gpad_run_state")
+        if s is not None:
+            check(self.lib.gpad_run_state_signals(self.h, _ptr(x), _ptr(s), _ptr(z), _ptr(y), int(N), float(tol),
+                                                  C.byref(st) if want else None), "gpad_run_state_signals")
+        else:
+            check(self.lib.gpad_run_state(self.h, _ptr(x), _ptr(z), _ptr(y), int(N), float(tol),
+                                          C.byref(st) if want else None), "gpad_run_state")
         return self._stats_dict(st) if want else None
 
     def closed_loop(self, x, z, y, steps: int, N: int, tol: float = 0.0, *, warm: bool = False,
-                    xs=None, us=None, iters=None, codes=None, stats: bool = True):
+                    xs=None, us=None, iters=None, codes=None, stats: bool = True, signals=None):
         """gpad.m:79-95 on the device: ``steps`` receding-horizon MPC steps for every instance.
         x [batch][nx] is advanced in place; xs [steps][batch][nx] / us [steps][batch][nu]
         receive the trajectories when given; ``iters`` / ``codes`` (host int32 [steps*batch]) the
@@ -330,16 +352,25 @@ class GpadSolver:
         (``kernel == "loop"`` in the stats); it applies to f32 setups, shared matrices or per-instance
         ones, no flat setup and no Hessian, n, m <= 208, kernel AUTO or RESIDENT, N >= 1, nx <= 64 and
         nu <= min(n, 64), with one plant or per-instance maps (``setup_plant``), and any other call
-        runs the lockstep loop.  Results are bit-identical."""
+        runs the lockstep loop.  Results are bit-identical.
+
+        With signals bound (``setup_signals``), ``signals`` [steps][batch][ns] is required: step t
+        uses signals[t] for its QP data and for the update from x_t to x_{t+1}.  The one-launch loop
+        then needs nx + ns <= 64."""
         st = Stats()
         for arr, field in ((iters, "iters"), (codes, "codes")):
             if arr is not None:
                 setattr(st, field, _count_array(arr, field, steps * max(1, self.dims.batch if self.dims else 1)))
         want = stats or iters is not None or codes is not None or not _is_torch(z)
         opt = lambda a: _ptr(a) if a is not None else None  # noqa: E731
-        check(self.lib.gpad_closed_loop(self.h, _ptr(x), _ptr(z), _ptr(y), int(steps), int(N),
-                                        float(tol), int(bool(warm)), opt(xs), opt(us),
-                                        C.byref(st) if want else None), "gpad_closed_loop")
+        if signals is not None:
+            check(self.lib.gpad_closed_loop_signals(self.h, _ptr(x), _ptr(z), _ptr(y), _ptr(signals), int(steps),
+                                                    int(N), float(tol), int(bool(warm)), opt(xs), opt(us),
+                                                    C.byref(st) if want else None), "gpad_closed_loop_signals")
+        else:
+            check(self.lib.gpad_closed_loop(self.h, _ptr(x), _ptr(z), _ptr(y), int(steps), int(N),
+                                            float(tol), int(bool(warm)), opt(xs), opt(us),
+                                            C.byref(st) if want else None), "gpad_closed_loop")
         return self._stats_dict(st) if want else None
 
     # ---- per-step entry points (device tensors; kernel_functions.h one-for-one) ----------

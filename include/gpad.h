@@ -31,7 +31,9 @@ extern "C" {
                               * 0.4: the condensed operator (kernel 5, option 14) removed, the device
                               * error word sticky until reported; layouts as in 0.3;
                               * 0.5: options 20, 21 removed; layouts as in 0.3;
-                              * 0.6: gpad_setup_plant_batch added; layouts as in 0.3 */
+                              * 0.6: gpad_setup_plant_batch added; layouts as in 0.3.  Added since
+                              * without a new minor (no layout or behaviour of 0.6 changes):
+                              * gpad_setup_signals, gpad_run_state_signals, gpad_closed_loop_signals */
 
 /* status codes */
 #define GPAD_OK 0
@@ -276,6 +278,42 @@ int gpad_run_state(gpad_handle_t h, const void* x, void* z0, void* y0, int N, do
  * every stat (per-step counts and codes included) are bit for bit those of the lockstep loop. */
 int gpad_closed_loop(gpad_handle_t h, void* x, void* z, void* y, int steps, int N, double tol, int warm,
                      void* xs, void* us, gpad_stats_t* st);
+
+/* ---- exogenous signals: references, measured disturbances, time-varying bounds, noise ---------
+ * A handle with a plant bound may bind three more maps for a signal vector s (ns), known at each
+ * MPC step and not generated by the plant:
+ *   M(x, s) = M0 + PM x + SM s      SM: n  x ns
+ *   g(x, s) = g0 + Pg x + Sg s      Sg: m  x ns
+ *   x+      = A x + E s + B u       E : nx x ns,  u = z*[0:nu]
+ * Evaluation order, in dims.dtype with explicit fmas: an affine row is acc = c0[i], then
+ * fma(P[i][k], x[k], acc) for k < nx, then fma(S[i][j], s[j], acc) for j < ns; a plant row is acc = 0,
+ * then the A x terms, the E s terms, the B u terms.  A NULL map is a map of zeros whose terms are
+ * evaluated, not a skipped chain.  Step t of a loop uses S[t] for the QP data of step t and for the
+ * update from x_t to x_{t+1}.  This is, bit for bit, gpad_setup_plant on the augmented state
+ * x~ = [x; s] with PM~ = [PM SM], Pg~ = [Pg Sg], A~ = [[A E]; [0 0]], B~ = [B; 0], the s rows of x~
+ * replaced by the caller's S[t] before every step.  A preview of a reference over the horizon is a
+ * longer s: the caller stacks r_t .. r_{t+N-1}.
+ *
+ * gpad_setup_signals is called after gpad_setup_plant / gpad_setup_plant_batch (GPAD_ERR_NOT_SETUP
+ * before) and uses the dtype and memory of the bound problem.  After gpad_setup_plant_batch every
+ * non-NULL map holds dims.batch consecutive copies -- SM [batch][n][ns], Sg [batch][m][ns],
+ * E [batch][nx][ns] -- else one.  ns >= 1 binds; ns == 0 unbinds (the pointers are ignored); ns < 0
+ * and a non-NULL E on a plant bound without A, B are GPAD_ERR_INVALID.  A later gpad_setup_plant,
+ * gpad_setup_plant_batch or gpad_setup unbinds the signals. */
+int gpad_setup_signals(gpad_handle_t h, int ns, const void* SM, const void* Sg, const void* E);
+
+/* gpad_run_state with signals s [batch][ns], and gpad_closed_loop with S [steps][batch][ns] (in the
+ * memory of dims.memory).  xs stays [steps][batch][nx]: the signals are not echoed.  Everything else
+ * is as in gpad_run_state / gpad_closed_loop; tol_floor and the flags cover the g(x, s) of every step.
+ * With signals bound the plain gpad_run_state / gpad_closed_loop return GPAD_ERR_INVALID (a silently
+ * dropped disturbance is worse than an error); with none bound these two return GPAD_ERR_NOT_SETUP.
+ * A NULL s / S is GPAD_ERR_INVALID.  GPAD_OPT_LOOP_ASYNC applies when, in addition to
+ * gpad_closed_loop's conditions, nx + ns <= 64 (the state and the signals share one 64-word row); any
+ * other call runs the lockstep loop, where ns is unbounded.  Results are identical either way. */
+int gpad_run_state_signals(gpad_handle_t h, const void* x, const void* s, void* z0, void* y0, int N, double tol,
+                           gpad_stats_t* st);
+int gpad_closed_loop_signals(gpad_handle_t h, void* x, void* z, void* y, const void* S, int steps, int N,
+                             double tol, int warm, void* xs, void* us, gpad_stats_t* st);
 
 /* ---- reference data-file boundary (main.cu:29-67 readData) ------------------------------
  * Text file: "n_u N m num_iterations L", then M_G (n*m), g_P (n), G_L (n*m), p_D (m),

@@ -3,13 +3,19 @@
 tensors.  C1 plant (battery_plant(4, 10): n = 40, m = 180), 20 MPC steps, batches 1 ... 8192, three
 modes: eps cold / eps warm (tol 1e-4, N 3000) and fixed N = 100.
 
-  python tools/loop_ab.py [--rounds 3] [--steps 20] [--batches 1 64 256 512 2048 8192] [--fleet]
+  python tools/loop_ab.py [--rounds 3] [--steps 20] [--batches 1 64 256 512 2048 8192] [--fleet | --signals]
 
 --fleet: a fleet of distinct packs instead (problems.battery_fleet(4, 10, battery_fleet_caps(batch, 4,
 seed = batch)): per-pack ML, G and plant maps, setup(shared=False) + a stacked setup_plant), default
 batches 1 64 256 2048 8192.  The lockstep loop runs the resident kernel there, the option the fleet
 kernel; a third variant, "async_1wg", caps the grid at one workgroup per CU (duo_max_grid = CUs) to
 show what the second workgroup per CU buys, and `async_1wg_over_async` is its rate over the default's.
+
+--signals: two more variants in the same process, "sig_lockstep" and "sig_async", on
+problems.battery_plant_signals(4, 10) (gpad_setup_signals: s = [i_load, r_1 .. r_4], loads U(-5, 5) A and
+references U(-0.1, 0.1) per step and pack, seeded by the batch), each checked against the other; the
+plain variants run unchanged beside them, and `sig_over_plain` is the rate with signals over the rate
+without, per loop kind (informational: the signals change the QPs, so also the iteration counts).
 
 Per batch and mode the two variants' x, z, y, xs, us and per-step iteration counts are compared first
 (that run is also each variant's warm-up); a mismatch aborts the batch.  Then `rounds` rounds
@@ -41,7 +47,10 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--batches", type=int, nargs="*", default=None)
     ap.add_argument("--fleet", action="store_true")
+    ap.add_argument("--signals", action="store_true")
     args = ap.parse_args()
+    if args.fleet and args.signals:
+        ap.error("--fleet and --signals exclude each other")
     if args.batches is None:
         args.batches = [1, 64, 256, 2048, 8192] if args.fleet else [1, 64, 256, 512, 2048, 8192]
     rounds = max(3, args.rounds)
@@ -54,6 +63,9 @@ def main():
     n, m, nx, nu, steps = qp.n, qp.m, pl.nx, pl.nu, args.steps
     t32 = lambda a: torch.from_numpy(np.ascontiguousarray(np.asarray(a, np.float64).astype(np.float32))).to(dev)  # noqa: E731
     dML, dG, dPM, dPg, dg0, dA, dB = (t32(a) for a in (qp.ML, qp.G, pl.PM, pl.Pg, pl.g0, pl.A, pl.B))
+    if args.signals:
+        qs, ps = problems.battery_plant_signals(4, 10)
+        dSM, dSg, dE = (t32(a) for a in (ps.SM, ps.Sg, ps.E))
     cus = torch.cuda.get_device_properties(0).multi_processor_count
     print(json.dumps({"plant": "battery_fleet(4, 10)" if args.fleet else "battery_plant(4, 10)", "n": n, "m": m,
                       "steps": steps, "rounds": rounds, "device": torch.cuda.get_device_name(0), "cus": cus}))
@@ -63,11 +75,20 @@ def main():
             qp, pl = problems.battery_fleet(4, 10, problems.battery_fleet_caps(B, 4, B))
             dML, dG, dPM, dPg, dg0, dA, dB = (t32(a) for a in (qp.ML, qp.G, pl.PM, pl.Pg, pl.g0, pl.A, pl.B))
         var = {}
-        for name in ("lockstep", "async") + (("async_1wg",) if args.fleet else ()):
+        sig = None
+        if args.signals:
+            rng = np.random.default_rng([B, 1])
+            sig = torch.from_numpy(np.concatenate([rng.uniform(-5, 5, (steps, B, 1)),
+                                                   rng.uniform(-0.1, 0.1, (steps, B, nx))],
+                                                  axis=-1).astype(np.float32)).to(dev)
+        for name in ("lockstep", "async") + (("async_1wg",) if args.fleet else ()) + (
+                ("sig_lockstep", "sig_async") if args.signals else ()):
             s = gpad_mpc.GpadSolver(0)
             s.setup(dML, dG, float(np.float32(qp.L)), n=n, m=m, batch=B, shared=not args.fleet)
             s.setup_plant(dPM, dPg, g0=dg0, A=dA, B=dB)
-            s.set_option("loop_async", int(name != "lockstep"))
+            if name.startswith("sig_"):
+                s.setup_signals(dSM, dSg, dE)
+            s.set_option("loop_async", int(not name.endswith("lockstep")))
             if name == "async_1wg":
                 s.set_option("duo_max_grid", cus)
             buf = dict(x=torch.empty(B, nx, device=dev), z=torch.empty(B, n, device=dev),
@@ -82,18 +103,19 @@ def main():
             b["y"].zero_()
             torch.cuda.synchronize()
             return s.closed_loop(b["x"], b["z"], b["y"], steps, mode["N"], mode["tol"], warm=mode["warm"],
-                                 xs=b["xs"], us=b["us"], **kw)
+                                 xs=b["xs"], us=b["us"], signals=sig if name.startswith("sig_") else None, **kw)
 
         for mname, mode in MODES.items():
             its, kern = {}, {}
             for name in var:  # the output check, and each variant's warm-up
                 its[name] = np.zeros(steps * B, np.int32)
                 kern[name] = enqueue(name, mode, iters=its[name])["kernel"]
-            bad = [k for k in ("x", "z", "y", "xs", "us") for v in var if v != "lockstep"
-                   if not torch.equal(var["lockstep"][1][k].view(torch.int32), var[v][1][k].view(torch.int32))]
-            if any(not np.array_equal(its["lockstep"], its[v]) for v in var):
+            base = lambda v: "sig_lockstep" if v.startswith("sig_") else "lockstep"  # noqa: E731
+            bad = [k for k in ("x", "z", "y", "xs", "us") for v in var if v != base(v)
+                   if not torch.equal(var[base(v)][1][k].view(torch.int32), var[v][1][k].view(torch.int32))]
+            if any(not np.array_equal(its[base(v)], its[v]) for v in var):
                 bad.append("iters")
-            if bad or any((kern[v] == "loop") != (v != "lockstep") for v in var):
+            if bad or any((kern[v] == "loop") != (v != base(v)) for v in var):
                 print(json.dumps({"batch": B, "mode": mname, "error": "outputs differ" if bad else "wrong kernel",
                                   "differ": bad, "kernels": kern}))
                 break
@@ -119,7 +141,12 @@ def main():
                 "wall_ms": {k: [round(x, 4) for x in v] for k, v in wall.items()},
                 "mpc_steps_per_s": {k: round(v, 1) for k, v in rate.items()},
                 "async_over_lockstep": round(rate["async"] / rate["lockstep"], 3), "faster": faster,
-                **({"async_1wg_over_async": round(rate["async_1wg"] / rate["async"], 3)} if args.fleet else {})}),
+                **({"async_1wg_over_async": round(rate["async_1wg"] / rate["async"], 3)} if args.fleet else {}),
+                **({"sig_mean_iters_per_solve": round(float(its["sig_async"].mean()), 1),
+                    "sig_async_over_sig_lockstep": round(rate["sig_async"] / rate["sig_lockstep"], 3),
+                    "sig_over_plain": {"lockstep": round(rate["sig_lockstep"] / rate["lockstep"], 3),
+                                       "async": round(rate["sig_async"] / rate["async"], 3)}}
+                   if args.signals else {})}),
                 flush=True)
         for s, _ in var.values():
             s.close()
