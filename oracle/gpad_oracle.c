@@ -356,23 +356,49 @@ static int orc_check_f64(double* u, const double* ch, const double* pD, const do
 
 static int orc_solve_f64_h(double* z, double* y, const double* ML, const double* gP, const double* G,
                            const double* g, const double* H, int n, int m, int N, double L, double tol,
-                           double tol_gap, int check_every, int schedule, int* converged);
+                           double tol_gap, int check_every, const double* th, const double* be, int* converged);
+
+/* the schedule-kind entries: the tables of orc_schedule, then the table-taking solve */
+static int orc_solve_f64_kind(double* z, double* y, const double* ML, const double* gP, const double* G,
+                              const double* g, const double* H, int n, int m, int N, double L, double tol,
+                              double tol_gap, int check_every, int schedule, int* converged) {
+    double* th = (double*)malloc(sizeof(double) * (N + 1));
+    double* be = (double*)malloc(sizeof(double) * (N + 1));
+    orc_schedule(N, schedule, th, be);
+    const int it = orc_solve_f64_h(z, y, ML, gP, G, g, H, n, m, N, L, tol, tol_gap, check_every, th, be, converged);
+    free(th);
+    free(be);
+    return it;
+}
 
 int orc_solve_f64(double* z, double* y, const double* ML, const double* gP, const double* G,
                   const double* g, int n, int m, int N, double L, double tol, double tol_gap,
                   int check_every, int schedule, int* converged) {
-    return orc_solve_f64_h(z, y, ML, gP, G, g, NULL, n, m, N, L, tol, tol_gap, check_every, schedule, converged);
+    return orc_solve_f64_kind(z, y, ML, gP, G, g, NULL, n, m, N, L, tol, tol_gap, check_every, schedule, converged);
 }
 
 int orc_solve_value_f64(double* z, double* y, const double* ML, const double* gP, const double* G,
                         const double* g, const double* H, int n, int m, int N, double L, double tol,
                         double tol_gap, int check_every, int schedule, int* converged) {
-    return orc_solve_f64_h(z, y, ML, gP, G, g, H, n, m, N, L, tol, tol_gap, check_every, schedule, converged);
+    return orc_solve_f64_kind(z, y, ML, gP, G, g, H, n, m, N, L, tol, tol_gap, check_every, schedule, converged);
+}
+
+int orc_solve_tables_f64(double* z, double* y, const double* ML, const double* gP, const double* G,
+                         const double* g, int n, int m, int N, double L, double tol, double tol_gap,
+                         int check_every, const double* theta, const double* beta, int* converged) {
+    return orc_solve_f64_h(z, y, ML, gP, G, g, NULL, n, m, N, L, tol, tol_gap, check_every, theta, beta, converged);
+}
+
+int orc_solve_value_tables_f64(double* z, double* y, const double* ML, const double* gP, const double* G,
+                               const double* g, const double* H, int n, int m, int N, double L, double tol,
+                               double tol_gap, int check_every, const double* theta, const double* beta,
+                               int* converged) {
+    return orc_solve_f64_h(z, y, ML, gP, G, g, H, n, m, N, L, tol, tol_gap, check_every, theta, beta, converged);
 }
 
 static int orc_solve_f64_h(double* z, double* y, const double* ML, const double* gP, const double* G,
                            const double* g, const double* H, int n, int m, int N, double L, double tol,
-                           double tol_gap, int check_every, int schedule, int* converged) {
+                           double tol_gap, int check_every, const double* th, const double* be, int* converged) {
     const size_t nm = (size_t)n * m;
     double* GL = (double*)malloc(sizeof(double) * (nm + 1));
     double* pD = (double*)malloc(sizeof(double) * (m + 1));
@@ -381,14 +407,11 @@ static int orc_solve_f64_h(double* z, double* y, const double* ML, const double*
     double* w = (double*)malloc(sizeof(double) * (m + 1));
     double* yp1 = (double*)malloc(sizeof(double) * (m + 1));
     double* zhat = (double*)malloc(sizeof(double) * (n + 1));
-    double* th = (double*)malloc(sizeof(double) * (N + 1));
-    double* be = (double*)malloc(sizeof(double) * (N + 1));
     double* u = (double*)malloc(sizeof(double) * (m + 1));
     double* ch = (double*)malloc(sizeof(double) * (m + 1));
     const double inv = 1.0 / L, ninv = -1.0 / L;
     for (size_t k = 0; k < nm; k++) GL[k] = inv * G[k];           /* acceldualgrad.m:22 */
     for (int i = 0; i < m; i++) pD[i] = ninv * g[i];              /* acceldualgrad.m:23 */
-    orc_schedule(N, schedule, th, be);
     if (check_every <= 0) check_every = 10;
     memcpy(yv, y, sizeof(double) * m);
     memcpy(yvm1, y, sizeof(double) * m);
@@ -430,7 +453,7 @@ static int orc_solve_f64_h(double* z, double* y, const double* ML, const double*
         }
     }
     memcpy(y, yv, sizeof(double) * m);
-    free(GL); free(pD); free(yv); free(yvm1); free(w); free(yp1); free(zhat); free(th); free(be);
+    free(GL); free(pD); free(yv); free(yvm1); free(w); free(yp1); free(zhat);
     free(u); free(ch);
     if (converged) *converged = conv;
     return it;

@@ -83,6 +83,17 @@ int orc_solve_f64(double* z, double* y, const double* ML, const double* gP, cons
                   const double* g, int n, int m, int N, double L, double tol, double tol_gap,
                   int check_every, int schedule, int* converged);
 
+/* orc_solve_f64 / orc_solve_value_f64 with caller tables (fp64, length N) in place of a schedule
+ * kind, as orc_solve_f32 takes them: theta[v] and beta[v] are used in iteration v as given.  With
+ * the tables of orc_schedule(N, kind) they return the bits of the schedule-kind entries. */
+int orc_solve_tables_f64(double* z, double* y, const double* ML, const double* gP, const double* G,
+                         const double* g, int n, int m, int N, double L, double tol, double tol_gap,
+                         int check_every, const double* theta, const double* beta, int* converged);
+int orc_solve_value_tables_f64(double* z, double* y, const double* ML, const double* gP, const double* G,
+                               const double* g, const double* H, int n, int m, int N, double L, double tol,
+                               double tol_gap, int check_every, const double* theta, const double* beta,
+                               int* converged);
+
 /* Batch of independent instances (shared ML/G when shared != 0), `threads` OpenMP
  * threads (<= 0: all).  Per-instance vectors are packed [batch][n] / [batch][m].
  * iters (optional) receives per-instance iteration counts.  Returns total iterations. */

@@ -66,6 +66,12 @@ class Oracle:
         L.orc_solve_value_f64.argtypes = [_d, _d, _d, _d, _d, _d, _d, C.c_int, C.c_int, C.c_int, C.c_double,
                                           C.c_double, C.c_double, C.c_int, C.c_int, C.POINTER(C.c_int)]
         L.orc_solve_value_f64.restype = C.c_int
+        L.orc_solve_tables_f64.argtypes = [_d, _d, _d, _d, _d, _d, C.c_int, C.c_int, C.c_int, C.c_double,
+                                           C.c_double, C.c_double, C.c_int, _d, _d, _i]
+        L.orc_solve_tables_f64.restype = C.c_int
+        L.orc_solve_value_tables_f64.argtypes = [_d, _d, _d, _d, _d, _d, _d, C.c_int, C.c_int, C.c_int, C.c_double,
+                                                 C.c_double, C.c_double, C.c_int, _d, _d, _i]
+        L.orc_solve_value_tables_f64.restype = C.c_int
         L.orc_solve_batch_f32.argtypes = [_f, _f, _f, _f, _f, _f, C.c_int, C.c_int, C.c_int, C.c_int,
                                           C.c_int, C.c_float, C.c_double, C.c_double, C.c_int, _f, _f, _i,
                                           C.c_int]
@@ -137,15 +143,17 @@ class Oracle:
 
     # -- solves -----------------------------------------------------------------
     def solve_f32(self, z0, y0, ML, M, G, g, N, L, tol=0.0, check_every=10,
-                  schedule=SCHEDULE_MATLAB, tol_gap=0.0):
+                  schedule=SCHEDULE_MATLAB, tol_gap=0.0, code=False):
         """solve(z0, y0, ML, M, G, g, N, L, tol) restated on the CPU in fp32 (tol = e_g,
         tol_gap = e_V; <= 0: = tol)."""
         MGneg, GL, pD = self.scale(ML, G, g, L)
         return self.solve_scaled_f32(z0, y0, MGneg, M, GL, pD, N, L, tol, check_every, schedule,
-                                     tol_gap=tol_gap)
+                                     tol_gap=tol_gap, code=code)
 
     def solve_scaled_f32(self, z0, y0, MGneg, gP, GL, pD, N, L, tol=0.0, check_every=10,
-                         schedule=SCHEDULE_MATLAB, theta=None, beta=None, tol_gap=0.0):
+                         schedule=SCHEDULE_MATLAB, theta=None, beta=None, tol_gap=0.0, code=False):
+        """The f32 solve on scaled operands, with caller tables when given.  The fourth value is
+        whether a test passed, or with ``code`` the termination code 0..2 (gpad_oracle.h)."""
         n, m = MGneg.shape
         z = np.array(z0, np.float32, copy=True).reshape(n)
         y = np.array(y0, np.float32, copy=True).reshape(m)
@@ -159,19 +167,35 @@ class Oracle:
                                     _fp(np.ascontiguousarray(pD, np.float32)), n, m, N,
                                     np.float32(L), float(tol), float(tol_gap), check_every, _fp(theta),
                                     _fp(beta), C.byref(conv))
-        return z, y, it, bool(conv.value)
+        return z, y, it, (conv.value if code else bool(conv.value))
+
+    @staticmethod
+    def _tables_f64(theta, beta, N):
+        """Caller fp64 tables of length >= N, contiguous (theta and beta come together)."""
+        if theta is None or beta is None:
+            raise ValueError("give both theta and beta")
+        theta = np.ascontiguousarray(theta, np.float64); beta = np.ascontiguousarray(beta, np.float64)
+        if theta.size < N or beta.size < N:
+            raise ValueError(f"theta/beta need {N} entries")
+        return theta, beta
 
     def solve_f64(self, z0, y0, ML, M, G, g, N, L, tol=0.0, check_every=10,
-                  schedule=SCHEDULE_MATLAB, tol_gap=0.0):
+                  schedule=SCHEDULE_MATLAB, tol_gap=0.0, theta=None, beta=None, code=False):
+        """fp64 solve; ``theta`` / ``beta`` (fp64 tables, length N) replace the schedule kind.  The
+        fourth value is whether a test passed, or with ``code`` the termination code."""
         ML = np.ascontiguousarray(ML, np.float64); n, m = ML.shape
         z = np.array(z0, np.float64, copy=True).reshape(n)
         y = np.array(y0, np.float64, copy=True).reshape(m)
         conv = C.c_int(0)
-        it = self.lib.orc_solve_f64(_dp(z), _dp(y), _dp(ML), _dp(np.ascontiguousarray(M, np.float64)),
-                                    _dp(np.ascontiguousarray(G, np.float64)),
-                                    _dp(np.ascontiguousarray(g, np.float64)), n, m, N, float(L),
-                                    float(tol), float(tol_gap), check_every, schedule, C.byref(conv))
-        return z, y, it, bool(conv.value)
+        args = (_dp(z), _dp(y), _dp(ML), _dp(np.ascontiguousarray(M, np.float64)),
+                _dp(np.ascontiguousarray(G, np.float64)), _dp(np.ascontiguousarray(g, np.float64)), n, m, N,
+                float(L), float(tol), float(tol_gap), check_every)
+        if theta is None and beta is None:
+            it = self.lib.orc_solve_f64(*args, schedule, C.byref(conv))
+        else:
+            theta, beta = self._tables_f64(theta, beta, N)
+            it = self.lib.orc_solve_tables_f64(*args, _dp(theta), _dp(beta), C.byref(conv))
+        return z, y, it, (conv.value if code else bool(conv.value))
 
     # -- Algorithm 1 with the value-function branches (acceldualgrad.m:73,76; f = H M) -------
     def solve_value_f32(self, z0, y0, ML, M, G, g, H, N, L, tol=0.0, check_every=10,
@@ -190,16 +214,20 @@ class Oracle:
         return z, y, it, conv.value
 
     def solve_value_f64(self, z0, y0, ML, M, G, g, H, N, L, tol=0.0, check_every=10,
-                        schedule=SCHEDULE_MATLAB, tol_gap=0.0):
+                        schedule=SCHEDULE_MATLAB, tol_gap=0.0, theta=None, beta=None):
         ML = np.ascontiguousarray(ML, np.float64); n, m = ML.shape
         z = np.array(z0, np.float64, copy=True).reshape(n)
         y = np.array(y0, np.float64, copy=True).reshape(m)
         conv = C.c_int(0)
-        it = self.lib.orc_solve_value_f64(_dp(z), _dp(y), _dp(ML), _dp(np.ascontiguousarray(M, np.float64)),
-                                          _dp(np.ascontiguousarray(G, np.float64)),
-                                          _dp(np.ascontiguousarray(g, np.float64)),
-                                          _dp(np.ascontiguousarray(H, np.float64)), n, m, N, float(L),
-                                          float(tol), float(tol_gap), check_every, schedule, C.byref(conv))
+        args = (_dp(z), _dp(y), _dp(ML), _dp(np.ascontiguousarray(M, np.float64)),
+                _dp(np.ascontiguousarray(G, np.float64)), _dp(np.ascontiguousarray(g, np.float64)),
+                _dp(np.ascontiguousarray(H, np.float64)), n, m, N, float(L), float(tol), float(tol_gap),
+                check_every)
+        if theta is None and beta is None:
+            it = self.lib.orc_solve_value_f64(*args, schedule, C.byref(conv))
+        else:
+            theta, beta = self._tables_f64(theta, beta, N)
+            it = self.lib.orc_solve_value_tables_f64(*args, _dp(theta), _dp(beta), C.byref(conv))
         return z, y, it, conv.value
 
     def solve_batch_f32(self, Z0, Y0, MGneg, GP, GL, PD, N, L, tol=0.0, check_every=10,
