@@ -393,6 +393,7 @@ int gpad_set_option(gpad_handle_t h, int option, int value) {
                 return rc;
             }
             case GPAD_OPT_LOOP_ASYNC: return set(t.loop_async, 0, 1, def.loop_async);
+            case GPAD_OPT_LOOP_PANEL: return set(t.loop_panel, 0, 1, def.loop_panel);
             default: return fail(GPAD_ERR_INVALID, "gpad_set_option: unknown option");
         }
     });
@@ -1561,9 +1562,16 @@ static int state_typed(gpad_handle_t h, T* x, T* z, T* y, const T* sg, int steps
         // GPAD_OPT_LOOP_ASYNC: the whole loop in one launch of gpad_loop_kernel, every pack stepping on
         // its own (gpad_loop.hip).  Anything it does not cover runs the lockstep loop below.
         // (per-instance matrices: its solo variant, where the resident kernel holds the shape)
-        async = loop && h->tune.loop_async && !h->flat && !h->hess_ok && N >= 1 &&
-                (d.kernel == GPAD_KERNEL_AUTO || d.kernel == GPAD_KERNEL_RESIDENT) &&
-                gpad::loop_supported(n, m, nxa, nu);
+        // GPAD_OPT_LOOP_PANEL comes first: the same loop on the MFMA panels (gpad_loop_panel.hip), shared
+        // matrices with a fragment image of at most 16 tiles; with a tolerance the iteration limit must
+        // fall on a test (the kernel's events are workgroup-uniform).
+        const bool lpanel = loop && h->tune.loop_panel && d.shared && h->frag_ok && h->frag_tiles >= 1 &&
+                            h->frag_tiles <= 16 && !h->flat && !h->hess_ok && N >= 1 &&
+                            (d.kernel == GPAD_KERNEL_AUTO || d.kernel == GPAD_KERNEL_PANEL) &&
+                            (!(tol > 0.0) || N % d.check_every == 0) && gpad::loop_panel_supported(n, m, nxa, nu);
+        async = lpanel || (loop && h->tune.loop_async && !h->flat && !h->hess_ok && N >= 1 &&
+                           (d.kernel == GPAD_KERNEL_AUTO || d.kernel == GPAD_KERNEL_RESIDENT) &&
+                           gpad::loop_supported(n, m, nxa, nu));
         if (async) {
             if ((rc = h->q64.ensure(sizeof(int)))) return rc;
             gpad::LoopArgs la{};
@@ -1613,14 +1621,21 @@ static int state_typed(gpad_handle_t h, T* x, T* z, T* y, const T* sg, int steps
             la.steps = nsolve;
             la.warm = warm ? 1 : 0;
             la.per_plant = per_plant ? 1 : 0;
-            int grid = std::min(batch, h->num_cus * gpad::loop_blocks_per_cu(la));
-            if (h->tune.duo_max_grid > 0 && h->tune.duo_max_grid < grid) grid = h->tune.duo_max_grid;
-            grid = std::min(grid, (int)gpad::kAbsmaxMaxBlocks);
+            int grid;
+            if (lpanel) {
+                a.frag = h->frag.p;
+                a.frag_tiles = h->frag_tiles;
+                grid = gpad::loop_panel_grid(n, m, batch, h->num_cus, &h->tune);
+            } else {
+                grid = std::min(batch, h->num_cus * gpad::loop_blocks_per_cu(la));
+                if (h->tune.duo_max_grid > 0 && h->tune.duo_max_grid < grid) grid = h->tune.duo_max_grid;
+                grid = std::min(grid, (int)gpad::kAbsmaxMaxBlocks);
+            }
             HIP_TRY(hipMemsetAsync(a.qctr, 0, sizeof(int), h->stream));
             HIP_TRY(hipEventRecord(h->ev0, h->stream));
-            const hipError_t e = gpad::launch_loop(la, grid, h->stream);
+            const hipError_t e = lpanel ? gpad::launch_loop_panel(la, grid, h->stream) : gpad::launch_loop(la, grid, h->stream);
             if (e != hipSuccess) return fail(GPAD_ERR_HIP, std::string("loop kernel: ") + hipGetErrorString(e));
-            kernel = GPAD_KERNEL_LOOP;
+            kernel = lpanel ? GPAD_KERNEL_LOOP_PANEL : GPAD_KERNEL_LOOP;
             h->last_phased = false;
             h->last_p64 = false;
             h->last_N = N;

@@ -31,6 +31,7 @@ struct Tuning {
     int p64_no_relay = 0;     // GPAD_OPT_P64_RELAY = 0: f64 panels without the relay layout
     int p64_no_refill = 0;    // GPAD_OPT_P64_REFILL = 0: f64 panels without column refills
     int loop_async = 0;       // GPAD_OPT_LOOP_ASYNC: gpad_closed_loop in one launch, packs step on their own
+    int loop_panel = 0;       // GPAD_OPT_LOOP_PANEL: gpad_closed_loop in one launch on the MFMA panels
 };
 
 // Device error word of a run (SolveArgs::err): kernels OR these bits in with a vector atomic;
@@ -178,6 +179,16 @@ bool loop_supported(int n, int m, int nx, int nu);
 int loop_blocks_per_cu(const LoopArgs& a);
 // persistent grid of `grid` <= min(batch, kAbsmaxMaxBlocks) workgroups
 hipError_t launch_loop(const LoopArgs& a, int grid, hipStream_t s);
+// The same loop on the f32 MFMA panels (gpad_loop_panel.hip, GPAD_OPT_LOOP_PANEL): gpad_panel_kernel<T>'s
+// workgroup (a panel of 16 packs) whose columns step to their pack's next MPC solve in place and are
+// refilled from the queue after its last step.  LoopArgs as above, plus s.frag / s.frag_tiles (the
+// fragment image of gpad_setup, 1..16 tiles: n, m <= 256); shared matrices only; with s.tol > 0,
+// s.N % s.check_every == 0.  nx: columns of the state row, nx + ns with signals bound.
+bool loop_panel_supported(int n, int m, int nx, int nu);
+// min(panels, resident workgroups), capped by Tuning::panel_max_grid and kAbsmaxMaxBlocks
+int loop_panel_grid(int n, int m, int batch, int num_cus, const Tuning* t);
+// persistent grid of `grid` <= min(ceil(batch / 16), kAbsmaxMaxBlocks) workgroups
+hipError_t launch_loop_panel(const LoopArgs& a, int grid, hipStream_t s);
 hipError_t launch_panel(const SolveArgs<float>& a, hipStream_t s, bool* supported);
 // f64 panels on the f64 MFMA pipe (gpad_panel64.hip): shared matrices, n, m <= 256, one panel of 16
 // instances per workgroup, value-function branches when a.hfrag64 is set; a.frag = the -ML | G_L

@@ -1,0 +1,506 @@
+// gpad_loop_panel.hip -- the closed loop on the f32 MFMA panels (GPAD_OPT_LOOP_PANEL, gpad_closed_loop):
+// one launch in which a panel COLUMN whose solve ends steps to its pack's next MPC solve in place.
+//
+// The asynchronous loop of gpad_loop.h is the two-slot register-resident kernel: right up to about one
+// pack per CU.  For fleets (thousands of packs) the lockstep loop runs the MFMA panels, and pays per
+// MPC step its stream operations and, with a tolerance, the whole tail of its slowest pack.  Here the
+// workgroup is gpad_panel_kernel<T>'s (gpad_panel.hip): a panel of 16 packs, wave t = row tile t of both
+// GEMMs over the fragment images gpad_setup packs, the same MFMA chains (every k-block, ascending,
+// the zero-padding blocks included) and the same epilogues and Algorithm-1 test, operation for
+// operation.  What differs is the bookkeeping: every column carries its own pack, MPC step and
+// iteration count vc, so theta / beta are per lane (theta[vc], beta[vc + 1]: the same table words,
+// hence the same bits), and at a test event the columns that finished run the step boundary of
+// gpad_loop.h in place -- counters, u = z*[0:nu], x+ = A x + B u, M(x+), g(x+), the u seed -- and go on
+// with step t + 1 while their neighbours keep iterating.  After a pack's last step the column writes
+// its results and claims the next pack from a queue counter; with none left it goes inactive, and the
+// workgroup ends when no column is active.  No workgroup waits for another: every loop is bounded by
+// N, by `steps` and by the finite queue.
+//
+// Events stay workgroup-uniform: with a tolerance the host requires N % check_every == 0, columns
+// change step only at events, so every column's vc = v (mod check_every) for the workgroup's
+// iteration counter v and the iteration limit falls on an event; with fixed N all columns of a
+// workgroup start together and reach N together.
+//
+// panel_gemm, the vector typedefs and PanelSlot are gpad_panel.h's, shared with gpad_panel.hip.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+
+#include "gpad_chain.h"
+#include "gpad_internal.h"
+#include "gpad_panel.h"
+
+namespace gpad {
+
+namespace {
+
+struct LpCol {   // a column at a step boundary, published by wave 0
+    int pack;    // the pack whose solve ended (-1: the column is not at a boundary)
+    int t;       // its MPC step
+    int refill;  // the pack the column takes at step 0 (>= batch: none left), -1: no refill
+};
+
+template <int T>
+struct __attribute__((aligned(16))) LoopPanelLds {
+    float Wl[T * 256];  // [T][64][4] w    (B of GEMM 1)
+    float Zh[T * 256];  // [T][64][4] zhat (B of GEMM 2)
+    float Gp[T * 256];  // g_P rows of tile t
+    float Pd[T * 256];  // p_D rows of tile t
+    PanelSlot slots[T];
+    LpCol col[16];
+    float gmw[16];      // per wave: max |g| at the kernel's end
+};
+
+struct OpAbsmaxNan { __device__ float operator()(float x, float y) const { return absmax_nan(x, y); } };
+
+constexpr int kLpLdsPerCu = 160 * 1024;
+constexpr int kLpTabMax = 32 * 1024;  // (static + dynamic LDS of the T = 16 kernel stay below 128 KiB)
+
+// words of dynamic LDS before the schedule tables: x rows [2][16][nxa], u rows [16][nu]
+__host__ __device__ inline int lp_state_words(int nxa, int nu) { return 32 * nxa + 16 * nu; }
+// the schedule tables (theta | beta, N + 2 words each) go to LDS when they leave the workgroups of
+// a CU resident: 32 / T workgroups for T <= 8, one above (launch_panel_t's figure)
+template <int T>
+__host__ __device__ inline bool lp_tab_in_lds(int N, int nxa, int nu) {
+    const long long tab = 8ll * ((long long)N + 2);
+    const int wgs = T <= 8 ? 32 / T : 1;
+    return tab <= kLpTabMax &&
+           (long long)sizeof(LoopPanelLds<T>) + 4ll * lp_state_words(nxa, nu) + tab <= kLpLdsPerCu / wgs;
+}
+
+}  // namespace
+
+template <int T>
+__global__ __launch_bounds__(64 * T) void gpad_loop_panel_kernel(LoopArgs la) {
+    __shared__ LoopPanelLds<T> L;
+    extern __shared__ __attribute__((aligned(16))) float lp_dyn[];
+    const SolveArgs<float>& a = la.s;
+
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int t = __builtin_amdgcn_readfirstlane(tid >> 6);  // row tile of this wave
+    const int j = lane >> 4, c = lane & 15;
+    const int n = a.n, m = a.m, N = a.N, batch = a.batch;
+    const int nx = la.nx, nxa = la.nx + la.ns, nu = la.nu, steps = la.steps;
+    const int abytes = T * T * 1024;  // one packed operand
+    const __amdgpu_buffer_rsrc_t PA1 =
+        __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(a.frag), 0, abytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t PA2 = __builtin_amdgcn_make_buffer_rsrc(
+        (void*)((const char*)a.frag + abytes), 0, abytes, 0x00020000);
+    const int voff = t * 1024 + lane * 16;
+    const int slot = t * 64 + lane;  // this lane's float4 in Wl / Zh / Gp / Pd
+    float4* Wl4 = reinterpret_cast<float4*>(L.Wl);
+    float4* Zh4 = reinterpret_cast<float4*>(L.Zh);
+    float4* Gp4 = reinterpret_cast<float4*>(L.Gp);
+    float4* Pd4 = reinterpret_cast<float4*>(L.Pd);
+    PanelSlot* slots = L.slots;
+    const bool use_tol = a.tol > 0.0;
+    // row tiles whose results nobody reads: 16t >= n in GEMM 1, 16t >= m in GEMM 2 (their packed rows
+    // are zero)
+    const bool g1 = 16 * t < n, g2 = 16 * t < m;
+    const int period = use_tol ? a.check_every : N;  // iterations between events
+
+    float* X = lp_dyn;                       // [2][16][nxa]: [x_t; s_t] of column c at [t & 1][c]
+    float* U = X + 32 * nxa;                 // [16][nu]: u = z*[0:nu] of a column at its boundary
+    float* tab = U + 16 * nu;                // theta | beta when they fit
+    const float* thp = a.theta;
+    const float* btp = a.beta;
+    if (lp_tab_in_lds<T>(N, nxa, nu)) {
+        for (int i = tid; i < N + 2; i += 64 * T) {
+            tab[i] = a.theta[i];
+            tab[N + 2 + i] = a.beta[i];
+        }
+        thp = tab;
+        btp = tab + (N + 2);
+    }
+
+    // per column (the same value in the 4 T lanes of column c)
+    int pk = 16 * blockIdx.x + c;  // pack
+    int ts = 0;                    // its MPC step
+    int vc = 0;                    // iterations of its current solve
+    bool active = pk < batch;
+    // register r <-> row 16t + 4r + j of the column's pack
+    float z[4] = {0.0f, 0.0f, 0.0f, 0.0f}, y[4] = {0.0f, 0.0f, 0.0f, 0.0f}, u[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    float star[4] = {0.0f, 0.0f, 0.0f, 0.0f};  // z* of a finished solve
+    float th = 0.0f, bn = 0.0f;
+    float gm = 0.0f;  // NaN-keeping max |g| of every g row this lane formed
+    // the start is a boundary at which every column with a pack is refilled (static start: column c
+    // of workgroup b takes pack 16 b + c; later packs are claimed from the counter, from 16 grid on)
+    bool fin = active, was_last = true, first = true;
+    if (t == 0 && j == 0) {
+        L.col[c].pack = -1;
+        L.col[c].t = 0;
+        L.col[c].refill = active ? pk : -1;
+    }
+    __syncthreads();  // L.col (and the tables) published
+    int ke = period;  // iterations to the next event
+
+    while (true) {
+        if (!first) {
+            // schedule prefetched one iteration ahead (tables hold N + 2 entries; vc < N here)
+            const float th_next = thp[vc + 1], bn_next = btp[vc + 2];
+            const bool ev = --ke == 0;
+            if (ev) ke = period;
+            const bool chk = use_tol && ev;
+            const float omt = 1.0f - th;
+            // ---- GEMM 1 + epilogue: zhat = -ML w - g_P (8b), z = (1-th) z + th zhat (8c) ----
+            {
+                f32x4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
+                if (g1) acc = panel_gemm<T>(PA1, L.Wl, voff, lane);
+                const float4 g4 = Gp4[slot];
+                const float gp[4] = {g4.x, g4.y, g4.z, g4.w};
+                float zh[4];
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    zh[r] = acc[r] - gp[r];
+                    const float zn = __builtin_fmaf(omt, z[r], th * zh[r]);
+                    if (active) z[r] = zn;
+                }
+                Zh4[slot] = make_float4(zh[0], zh[1], zh[2], zh[3]);
+            }
+            __syncthreads();
+            // ---- GEMM 2 + epilogue: y+ = [w + G_L zhat + p_D]+ (8d), next w (8a) ----------
+            float violz = -INFINITY, violh = -INFINITY, wmin = INFINITY, magh = 0.0f;
+            double gap = 0.0;
+            {
+                f32x4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
+                if (g2) acc = panel_gemm<T>(PA2, L.Zh, voff, lane);
+                const float4 w4 = Wl4[slot];
+                const float wv[4] = {w4.x, w4.y, w4.z, w4.w};
+                const float4 p4 = Pd4[slot];
+                const float pd[4] = {p4.x, p4.y, p4.z, p4.w};
+                float wn[4];
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const float cv = acc[r];
+                    const float sv = (wv[r] + pd[r]) + cv;
+                    const float yp = (__builtin_fabsf(sv) + sv) * 0.5f;
+                    wn[r] = __builtin_fmaf(bn, yp - y[r], yp);
+                    if (use_tol) {
+                        const float un = __builtin_fmaf(omt, u[r], th * cv);
+                        if (active) u[r] = un;
+                        if (chk && active && (16 * t + 4 * r + j) < m) {
+                            const float tt = cv + pd[r];
+                            violh = fmaxf(violh, tt);
+                            magh = fmaxf(magh, __builtin_fabsf(cv) + __builtin_fabsf(pd[r]));
+                            wmin = fminf(wmin, wv[r]);
+                            gap -= (double)wv[r] * (double)tt;
+                            violz = fmaxf(violz, u[r] + pd[r]);
+                        }
+                    }
+                    if (active) y[r] = yp;
+                }
+                if (active) Wl4[slot] = make_float4(wn[0], wn[1], wn[2], wn[3]);
+            }
+            th = th_next;
+            bn = bn_next;
+            if (active) ++vc;
+            __syncthreads();
+            if (!ev) continue;
+
+            // this iteration's zhat (own slot), before a verification GEMM puts z there
+            const float4 h4 = Zh4[slot];
+            const float zk[4] = {h4.x, h4.y, h4.z, h4.w};
+            // ---- Algorithm 1 test, per column: lane groups j, then row tiles through LDS ----
+            int code = 0;
+            if (chk) {
+                violz = bfly<32>(bfly<16>(violz, OpMax{}), OpMax{});
+                violh = bfly<32>(bfly<16>(violh, OpMax{}), OpMax{});
+                magh = bfly<32>(bfly<16>(magh, OpMax{}), OpMax{});
+                wmin = bfly<32>(bfly<16>(wmin, OpMin{}), OpMin{});
+                gap = bfly<32>(bfly<16>(gap, OpAdd{}), OpAdd{});
+                if (j == 0) {
+                    slots[t].violz[c] = violz;
+                    slots[t].violh[c] = violh;
+                    slots[t].magh[c] = magh;
+                    slots[t].wmin[c] = wmin;
+                    slots[t].gap[c] = gap;
+                }
+                __syncthreads();
+                int st1 = 0;
+                if (active) {
+                    double vz = -INFINITY, vh = -INFINITY, wm = INFINITY, gq = 0.0, mh = 0.0;
+#pragma unroll
+                    for (int s2 = 0; s2 < T; ++s2) {
+                        vz = fmax(vz, (double)slots[s2].violz[c]);
+                        vh = fmax(vh, (double)slots[s2].violh[c]);
+                        mh = fmax(mh, (double)slots[s2].magh[c]);
+                        wm = fmin(wm, (double)slots[s2].wmin[c]);
+                        gq += slots[s2].gap[c];
+                    }
+                    st1 = (vz * a.L <= a.tol ? 1 : 0) |
+                          ((viol_ok(vh, mh, a.L, a.tol, ViolMargin<float>::value) && (wm >= 0.0) &&
+                            (gq * a.L <= a.tol_gap)) ? 2 : 0);
+                }
+                bool verified = false;
+                if (__syncthreads_or(st1 & 1)) {  // (A) nominated somewhere: G_L z for the panel
+                    Zh4[slot] = make_float4(z[0], z[1], z[2], z[3]);
+                    __syncthreads();
+                    f32x4 cz = {0.0f, 0.0f, 0.0f, 0.0f};
+                    if (g2) cz = panel_gemm<T>(PA2, L.Zh, voff, lane);
+                    const float4 p4 = Pd4[slot];
+                    const float pd[4] = {p4.x, p4.y, p4.z, p4.w};
+                    float vv = -INFINITY, mc = 0.0f;
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        if ((st1 & 1) && (16 * t + 4 * r + j) < m) {
+                            u[r] = cz[r];  // the recursion restarts from the direct value
+                            vv = fmaxf(vv, cz[r] + pd[r]);
+                            mc = fmaxf(mc, __builtin_fabsf(cz[r]) + __builtin_fabsf(pd[r]));
+                        }
+                    }
+                    vv = bfly<32>(bfly<16>(vv, OpMax{}), OpMax{});
+                    mc = bfly<32>(bfly<16>(mc, OpMax{}), OpMax{});
+                    if (j == 0) {  // every wave finished reading the slots before the barrier above
+                        slots[t].violz[c] = vv;
+                        slots[t].magh[c] = mc;
+                    }
+                    __syncthreads();
+                    if (st1 & 1) {
+                        double vcc = -INFINITY, mcc = 0.0;
+#pragma unroll
+                        for (int s2 = 0; s2 < T; ++s2) {
+                            vcc = fmax(vcc, (double)slots[s2].violz[c]);
+                            mcc = fmax(mcc, (double)slots[s2].magh[c]);
+                        }
+                        verified = viol_ok(vcc, mcc, a.L, a.tol, ViolMargin<float>::value);
+                    }
+                }
+                code = ((st1 & 1) && verified) ? 1 : ((st1 & 2) ? 2 : 0);
+            }
+            // ---- step boundary of the columns whose solve ended ------------------------------
+            fin = active && (code != 0 || vc >= N);
+            if (!__syncthreads_or(fin ? 1 : 0)) continue;  // (also: Zh and the slots are free again)
+            was_last = ts + 1 == steps;
+            if (fin) {
+                // z*: (B) certifies zhat
+#pragma unroll
+                for (int r = 0; r < 4; ++r) star[r] = code == 2 ? zk[r] : z[r];
+                const size_t tb = (size_t)ts * (size_t)batch + (size_t)pk;  // (step, pack) row of xs / us
+                if (t == 0 && j == 0) {  // the counters of step ts: [iters[batch] | conv[batch]]
+                    a.iters[(size_t)(2 * ts) * batch + pk] = vc;
+                    a.conv[(size_t)(2 * ts + 1) * batch + pk] = code;
+                }
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int i = 16 * t + 4 * r + j;
+                    if (i < nu) {
+                        U[c * nu + i] = star[r];
+                        if (la.us) la.us[tb * nu + i] = star[r];
+                    }
+                    if (was_last) {  // the pack's results
+                        if (i < n) a.z[(size_t)pk * n + i] = star[r];
+                        if (i < m) a.y[(size_t)pk * m + i] = y[r];
+                    }
+                }
+            }
+            if (t == 0) {  // lanes 0..15 of wave 0 speak for the columns: one claim per event
+                const bool want = fin && was_last && j == 0;
+                const unsigned long long lv = __ballot(want);
+                int base = 0;
+                if (lane == 0 && lv) base = atomicAdd(a.qctr, (int)__popcll(lv));
+                base = __shfl(base, 0, 64);
+                if (j == 0) {
+                    int np = -1;
+                    if (want) {
+                        np = 16 * (int)gridDim.x + base + (int)__popcll(lv & ((1ull << lane) - 1ull));
+                        if (np > batch) np = batch;
+                    }
+                    L.col[c].pack = fin ? pk : -1;
+                    L.col[c].t = ts;
+                    L.col[c].refill = np;
+                }
+            }
+            __syncthreads();  // U, L.col published
+            // x+ = A x (+ E s_t: the row is [A E]) + B u, one fma chain (plant_step_kernel's order);
+            // next to it the next step's signals.  Work item = (column, row of the state row).
+            for (int w = tid; w < 16 * nxa; w += 64 * T) {
+                const int col = w & 15, row = w >> 4;
+                const int pc = L.col[col].pack, tc = L.col[col].t;
+                if (pc < 0) continue;
+                const bool lastc = tc + 1 == steps;
+                const float* xc = X + ((tc & 1) * 16 + col) * nxa;
+                float* xn = X + (((tc + 1) & 1) * 16 + col) * nxa;
+                if (row < nx) {
+                    const size_t pi = la.per_plant ? (size_t)pc : 0;
+                    const float* Ar = la.A + (pi * nx + row) * nxa;
+                    const float* Br = la.B + (pi * nx + row) * nu;
+                    float acc = 0.0f;
+#pragma unroll 1
+                    for (int k = 0; k < nxa; ++k) acc = __builtin_fmaf(Ar[k], xc[k], acc);
+#pragma unroll 1
+                    for (int k = 0; k < nu; ++k) acc = __builtin_fmaf(Br[k], U[col * nu + k], acc);
+                    if (la.xs) la.xs[((size_t)tc * batch + pc) * nx + row] = xc[row];
+                    if (lastc) la.x_out[(size_t)pc * nx + row] = acc;
+                    else xn[row] = acc;
+                } else if (!lastc) {
+                    xn[row] = la.S[((size_t)(tc + 1) * batch + pc) * la.ns + (row - nx)];
+                }
+            }
+            __syncthreads();  // x_{t+1} published; x_t, U and the old L.col readers done
+        }
+        first = false;
+        // ---- the columns at a boundary start their next solve ----------------------------------
+        if (fin) {
+            if (was_last) {  // the next pack from the queue, at its step 0
+                pk = L.col[c].refill;
+                ts = 0;
+                active = pk < batch;
+                if (!active) vc = 0;  // (an idle column's schedule prefetch stays inside the tables)
+            } else {
+                ts += 1;
+            }
+        }
+        for (int w = tid; w < 16 * nxa; w += 64 * T) {  // a refilled column's [x_0; S[0][pack]]
+            const int col = w & 15, row = w >> 4;
+            const int rp = L.col[col].refill;
+            if (rp < 0 || rp >= batch) continue;
+            X[col * nxa + row] = row < nx ? la.x_in[(size_t)rp * nx + row] : la.S[(size_t)rp * la.ns + (row - nx)];
+        }
+        const bool go = fin && active;  // this lane's column starts a solve
+        if (go) {  // cold: z = y = 0 (acceldualgrad.m:16-17); warm: z_{-1} = z*, y_0 = y* (a new pack: the caller's)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int i = 16 * t + 4 * r + j;
+                float zv = 0.0f, yv = 0.0f;
+                if (la.warm) {
+                    if (was_last) {
+                        if (i < n) zv = a.z[(size_t)pk * n + i];
+                        if (i < m) yv = a.y[(size_t)pk * m + i];
+                    } else {
+                        if (i < n) zv = star[r];
+                        if (i < m) yv = y[r];
+                    }
+                }
+                z[r] = zv;
+                y[r] = yv;
+            }
+        }
+        __syncthreads();  // X published
+        if (go) {
+            // M(x), g(x) of this lane's rows (affine2_kernel's order): acc = c0[i] (0 if absent), then
+            // fma(P[i][k], x[k], acc) for ascending k over the nx + ns columns
+            const float* xr = X + ((ts & 1) * 16 + c) * nxa;
+            const size_t pi = la.per_plant ? (size_t)pk : 0;
+            const float b0 = btp[0];
+            float gp[4], pd[4], w[4];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int i = 16 * t + 4 * r + j;
+                gp[r] = 0.0f;
+                pd[r] = 0.0f;
+                if (i < n) {
+                    float acc = la.M0 ? la.M0[pi * n + i] : 0.0f;
+                    const float* P = la.PM + (pi * n + i) * nxa;
+#pragma unroll 1
+                    for (int k = 0; k < nxa; ++k) acc = __builtin_fmaf(P[k], xr[k], acc);
+                    gp[r] = acc;
+                }
+                if (i < m) {
+                    float acc = la.g0 ? la.g0[pi * m + i] : 0.0f;
+                    const float* P = la.Pg + (pi * m + i) * nxa;
+#pragma unroll 1
+                    for (int k = 0; k < nxa; ++k) acc = __builtin_fmaf(P[k], xr[k], acc);
+                    gm = absmax_nan(gm, acc);
+                    pd[r] = (float)(a.gscale * (double)acc);
+                }
+                // w_0 = y_0 + beta_0 (y_0 - y_{-1}), y_{-1} = y_0
+                w[r] = __builtin_fmaf(b0, y[r] - y[r], y[r]);
+                u[r] = 0.0f;
+            }
+            Gp4[slot] = make_float4(gp[0], gp[1], gp[2], gp[3]);
+            Pd4[slot] = make_float4(pd[0], pd[1], pd[2], pd[3]);
+            Wl4[slot] = make_float4(w[0], w[1], w[2], w[3]);
+            vc = 0;
+            th = thp[0];
+            bn = btp[1];
+        }
+        if (use_tol) {  // u = G_L z_{-1}: one GEMM over the panel's z, taken by the starting columns
+            Zh4[slot] = make_float4(z[0], z[1], z[2], z[3]);
+            __syncthreads();
+            f32x4 cz = {0.0f, 0.0f, 0.0f, 0.0f};
+            if (g2) cz = panel_gemm<T>(PA2, L.Zh, voff, lane);
+            if (go) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) u[r] = cz[r];
+            }
+        }
+        fin = false;
+        if (!__syncthreads_or(active ? 1 : 0)) break;  // (also publishes Wl, Gp, Pd; Zh free)
+    }
+
+    // the run's max |g| (the certification floor): this workgroup's slot, workgroup 0 zeroes the rest
+    if (la.gmax) {
+        const float wm = wave_reduce(gm, OpAbsmaxNan{});
+        if (lane == 0) L.gmw[t] = wm;
+        __syncthreads();
+        if (tid == 0) {
+            float mx = 0.0f;
+            for (int w = 0; w < T; ++w) mx = absmax_nan(mx, L.gmw[w]);
+            la.gmax[blockIdx.x] = (double)mx;
+        }
+        if (blockIdx.x == 0)
+            for (int i = (int)gridDim.x + tid; i < kAbsmaxMaxBlocks; i += 64 * T) la.gmax[i] = 0.0;
+    }
+}
+
+// ---- host side --------------------------------------------------------------------------------
+static int lp_tiles(int n, int m) {
+    const int t = ((n > m ? n : m) + 15) / 16;
+    return t >= 1 && t <= 16 ? t : 0;
+}
+
+bool loop_panel_supported(int n, int m, int nx, int nu) {
+    return n >= 1 && m >= 1 && lp_tiles(n, m) != 0 && nx >= 1 && nx <= kLoopMaxState && nu >= 1 &&
+           nu <= kLoopMaxState && nu <= n;
+}
+
+int loop_panel_grid(int n, int m, int batch, int num_cus, const Tuning* tn) {
+    // resident workgroups, as launch_panel_t: 32 / T per CU for T <= 8, one above
+    const int T = lp_tiles(n, m);
+    const int panels = (batch + 15) / 16;
+    const int resident = T > 8 ? num_cus : num_cus * (32 / (T ? T : 1));
+    int grid = panels < resident ? panels : resident;
+    if (tn && tn->panel_max_grid > 0 && tn->panel_max_grid < grid) grid = tn->panel_max_grid;
+    if (grid > kAbsmaxMaxBlocks) grid = kAbsmaxMaxBlocks;
+    return grid < 1 ? 1 : grid;
+}
+
+template <int T>
+static hipError_t launch_loop_panel_t(const LoopArgs& a, int grid, hipStream_t st) {
+    const SolveArgs<float>& s = a.s;
+    const int nxa = a.nx + a.ns;
+    size_t dyn = sizeof(float) * (size_t)lp_state_words(nxa, a.nu);
+    if (lp_tab_in_lds<T>(s.N, nxa, a.nu)) dyn += sizeof(float) * 2 * ((size_t)s.N + 2);
+    hipLaunchKernelGGL((gpad_loop_panel_kernel<T>), dim3(grid), dim3(64 * T), dyn, st, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_loop_panel(const LoopArgs& a, int grid, hipStream_t st) {
+    const SolveArgs<float>& s = a.s;
+    const int T = lp_tiles(s.n, s.m);
+    if (!T || !s.frag || s.frag_tiles != T || s.strideA || s.strideB ||
+        !loop_panel_supported(s.n, s.m, a.nx + a.ns, a.nu) || a.nx < 1 || a.ns < 0 || (a.ns && !a.S) || !s.qctr ||
+        s.N < 1 || a.steps < 1 || s.batch < 1 || s.check_every < 1 || (s.tol > 0.0 && s.N % s.check_every != 0) ||
+        grid < 1 || grid > (s.batch + 15) / 16 || grid > kAbsmaxMaxBlocks)
+        return hipErrorInvalidValue;
+    switch (T) {
+        case 1: return launch_loop_panel_t<1>(a, grid, st);
+        case 2: return launch_loop_panel_t<2>(a, grid, st);
+        case 3: return launch_loop_panel_t<3>(a, grid, st);
+        case 4: return launch_loop_panel_t<4>(a, grid, st);
+        case 5: return launch_loop_panel_t<5>(a, grid, st);
+        case 6: return launch_loop_panel_t<6>(a, grid, st);
+        case 7: return launch_loop_panel_t<7>(a, grid, st);
+        case 8: return launch_loop_panel_t<8>(a, grid, st);
+        case 9: return launch_loop_panel_t<9>(a, grid, st);
+        case 10: return launch_loop_panel_t<10>(a, grid, st);
+        case 11: return launch_loop_panel_t<11>(a, grid, st);
+        case 12: return launch_loop_panel_t<12>(a, grid, st);
+        case 13: return launch_loop_panel_t<13>(a, grid, st);
+        case 14: return launch_loop_panel_t<14>(a, grid, st);
+        case 15: return launch_loop_panel_t<15>(a, grid, st);
+        default: return launch_loop_panel_t<16>(a, grid, st);
+    }
+}
+
+}  // namespace gpad

@@ -23,8 +23,10 @@ MEM_HOST, MEM_DEVICE = 0, 1
 DTYPE_F32, DTYPE_F64 = 0, 1
 KERNEL_AUTO, KERNEL_STREAM, KERNEL_RESIDENT, KERNEL_PANEL, KERNEL_FLAT = 0, 1, 2, 3, 4
 KERNEL_LOOP = 6  # reported only: closed_loop in one launch (OPT_LOOP_ASYNC)
+KERNEL_LOOP_PANEL = 7  # reported only: closed_loop in one launch on the MFMA panels (OPT_LOOP_PANEL)
 KERNEL_NAMES = {KERNEL_AUTO: "auto", KERNEL_STREAM: "stream", KERNEL_RESIDENT: "resident",
-                KERNEL_PANEL: "panel", KERNEL_FLAT: "flat", KERNEL_LOOP: "loop"}
+                KERNEL_PANEL: "panel", KERNEL_FLAT: "flat", KERNEL_LOOP: "loop",
+                KERNEL_LOOP_PANEL: "loop_panel"}
 
 # every symbol include/gpad.h declares (checked by tests/test_abi.py)
 EXPORTS = [
@@ -54,6 +56,7 @@ OPT_DEBUG_DROP_HANDOFF = 16  # test-only fault injection
 OPT_P64_RELAY = 18  # f64 panels: 16-wave relay layout at T = 9, 13 (default 1)
 OPT_P64_REFILL = 19  # f64 panels: refill finished columns from the batch (default 1)
 OPT_LOOP_ASYNC = 22  # closed_loop in one launch, every instance stepping on its own (default 0)
+OPT_LOOP_PANEL = 23  # closed_loop in one launch on the MFMA panels, columns stepping on their own (default 0)
 OPT_RETIRED = (5, 13, 14, 15, 17, 20, 21)  # finisher kind, solo finisher workgroups, plan finisher cost
 # (0.3); condensed panels (0.4, with the condensed operator); 17: the opt-in pair layouts measured in
 # round 4 and left out of the product (W32, TailPair); 20, 21: the panel dataflow boundaries and the
@@ -64,7 +67,8 @@ OPTIONS = {"phase_len": OPT_PHASE_LEN, "finish_thresh": OPT_FINISH_THRESH, "plan
            "flat_panel_min": OPT_FLAT_PANEL_MIN, "flat_panels": OPT_FLAT_PANELS,
            "flat_waves": OPT_FLAT_WAVES, "flat_a_lds": OPT_FLAT_A_LDS,
            "debug_drop_handoff": OPT_DEBUG_DROP_HANDOFF, "p64_relay": OPT_P64_RELAY,
-           "p64_refill": OPT_P64_REFILL, "loop_async": OPT_LOOP_ASYNC}
+           "p64_refill": OPT_P64_REFILL, "loop_async": OPT_LOOP_ASYNC,
+           "loop_panel": OPT_LOOP_PANEL}
 
 FILE_ROWMAJOR, FILE_FLIPPED, FILE_FLAT = 0, 1, 2
 

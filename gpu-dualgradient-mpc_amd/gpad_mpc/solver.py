@@ -354,6 +354,13 @@ class GpadSolver:
         nu <= min(n, 64), with one plant or per-instance maps (``setup_plant``), and any other call
         runs the lockstep loop.  Results are bit-identical.
 
+        ``set_option("loop_panel", 1)`` is the same one-launch loop for fleets on the MFMA panels
+        (``kernel == "loop_panel"``): a panel column whose solve ends steps to its instance's next
+        solve in place.  It is looked at first and applies to f32 setups with shared matrices, no
+        flat setup and no Hessian, n, m <= 256, kernel AUTO or PANEL, N >= 1, tol <= 0 or N a
+        multiple of check_every, nx (+ ns) <= 64 and nu <= min(n, 64); any other call goes on as
+        without it.  Results are bit-identical.
+
         With signals bound (``setup_signals``), ``signals`` [steps][batch][ns] is required: step t
         uses signals[t] for its QP data and for the update from x_t to x_{t+1}.  The one-launch loop
         then needs nx + ns <= 64."""

@@ -33,7 +33,8 @@ extern "C" {
                               * 0.5: options 20, 21 removed; layouts as in 0.3;
                               * 0.6: gpad_setup_plant_batch added; layouts as in 0.3.  Added since
                               * without a new minor (no layout or behaviour of 0.6 changes):
-                              * gpad_setup_signals, gpad_run_state_signals, gpad_closed_loop_signals */
+                              * gpad_setup_signals, gpad_run_state_signals, gpad_closed_loop_signals;
+                              * GPAD_OPT_LOOP_PANEL (option 23) and the reported GPAD_KERNEL_LOOP_PANEL (7) */
 
 /* status codes */
 #define GPAD_OK 0
@@ -73,6 +74,8 @@ extern "C" {
  * returns GPAD_ERR_INVALID */
 #define GPAD_KERNEL_LOOP 6     /* reported only: gpad_closed_loop in one launch (GPAD_OPT_LOOP_ASYNC);
                                 * dims.kernel = 6 returns GPAD_ERR_INVALID                           */
+#define GPAD_KERNEL_LOOP_PANEL 7 /* reported only: gpad_closed_loop in one launch on the MFMA panels
+                                * (GPAD_OPT_LOOP_PANEL); dims.kernel = 7 returns GPAD_ERR_INVALID     */
 
 typedef struct gpad_dims {
     int n;           /* primal variables, n = n_u * N                                   */
@@ -275,7 +278,18 @@ int gpad_run_state(gpad_handle_t h, const void* x, void* z0, void* y0, int N, do
  * the option were unset.  With per-instance matrices a workgroup holds one instance at a time and
  * keeps its matrix rows in registers for all `steps` steps; the grid is up to two workgroups per
  * compute unit where they fit, capped by GPAD_OPT_DUO_MAX_GRID like the shared-matrix grid.  Results are identical either way: x, z, y, xs, us and
- * every stat (per-step counts and codes included) are bit for bit those of the lockstep loop. */
+ * every stat (per-step counts and codes included) are bit for bit those of the lockstep loop.
+ *
+ * GPAD_OPT_LOOP_PANEL = 1 is the same one-launch loop for fleets, on the f32 MFMA panels (stats
+ * kernel = GPAD_KERNEL_LOOP_PANEL): a workgroup owns a panel of 16 instances, and a panel column whose
+ * solve terminates applies its plant update and affine maps in place and goes on with its next
+ * step; after an instance's last step the column takes the next instance from a queue.  It is
+ * looked at before GPAD_OPT_LOOP_ASYNC and taken for f32 matrices shared by the batch
+ * (dims.shared = 1; no flat setup, no Hessian), n, m <= 256, dims.kernel AUTO or PANEL, N >= 1,
+ * tol <= 0 or N a multiple of dims.check_every, nx <= 64 and nu <= min(n, 64), with a plant bound
+ * by gpad_setup_plant or gpad_setup_plant_batch; the grid is capped by GPAD_OPT_PANEL_MAX_GRID.  Any
+ * other call goes on as if the option were unset (GPAD_OPT_LOOP_ASYNC's rules, then lockstep).
+ * Results are bit for bit those of the lockstep loop here too. */
 int gpad_closed_loop(gpad_handle_t h, void* x, void* z, void* y, int steps, int N, double tol, int warm,
                      void* xs, void* us, gpad_stats_t* st);
 
@@ -309,7 +323,8 @@ int gpad_setup_signals(gpad_handle_t h, int ns, const void* SM, const void* Sg, 
  * dropped disturbance is worse than an error); with none bound these two return GPAD_ERR_NOT_SETUP.
  * A NULL s / S is GPAD_ERR_INVALID.  GPAD_OPT_LOOP_ASYNC applies when, in addition to
  * gpad_closed_loop's conditions, nx + ns <= 64 (the state and the signals share one 64-word row); any
- * other call runs the lockstep loop, where ns is unbounded.  Results are identical either way. */
+ * other call runs the lockstep loop, where ns is unbounded.  GPAD_OPT_LOOP_PANEL has the same extra
+ * condition, nx + ns <= 64.  Results are identical either way. */
 int gpad_run_state_signals(gpad_handle_t h, const void* x, const void* s, void* z0, void* y0, int N, double tol,
                            gpad_stats_t* st);
 int gpad_closed_loop_signals(gpad_handle_t h, void* x, void* z, void* y, const void* S, int steps, int N,
@@ -494,6 +509,10 @@ int gpad_schedule(int N, int kind, double* theta, double* beta);
 #define GPAD_OPT_LOOP_ASYNC 22     /* 1: gpad_closed_loop runs the whole loop in one launch in which
                                     * every instance steps on its own (see gpad_closed_loop) where that
                                     * kernel applies, else the lockstep loop; 0 (default): lockstep */
+#define GPAD_OPT_LOOP_PANEL 23     /* 1: gpad_closed_loop runs the whole loop in one launch on the MFMA
+                                    * panels, every panel column stepping on its own (see
+                                    * gpad_closed_loop), where that kernel applies, else as without
+                                    * the option; 0 (default): off */
 int gpad_set_option(gpad_handle_t h, int option, int value);
 
 /* Synchronise the handle's stream (for callers using device memory + async runs). */

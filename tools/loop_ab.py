@@ -4,6 +4,15 @@ tensors.  C1 plant (battery_plant(4, 10): n = 40, m = 180), 20 MPC steps, batche
 modes: eps cold / eps warm (tol 1e-4, N 3000) and fixed N = 100.
 
   python tools/loop_ab.py [--rounds 3] [--steps 20] [--batches 1 64 256 512 2048 8192] [--fleet | --signals]
+                          [--panel]
+
+--panel: a third variant, "panel" (GPAD_OPT_LOOP_PANEL, csrc/gpad_loop_panel.hip: the one-launch loop on the
+MFMA panels), alternated with lockstep and async in the same process and checked against lockstep like
+them; default batches 256 2048 8192.  `panel_over_lockstep` / `panel_over_async` are its rate over the
+others', `panel_faster` names panel or lockstep as `faster` does.  With --signals a "sig_panel" variant
+joins the two sig_ ones.  With --fleet the case is the plant/model mismatch on shared matrices (the
+controller of pack 0 -- its ML, G and PM for everyone -- against every pack's own Pg, g0, A, B): per-pack
+matrices have no panels, so the fleet proper is not a --panel case, and async_1wg is left out.
 
 --fleet: a fleet of distinct packs instead (problems.battery_fleet(4, 10, battery_fleet_caps(batch, 4,
 seed = batch)): per-pack ML, G and plant maps, setup(shared=False) + a stacked setup_plant), default
@@ -48,11 +57,14 @@ def main():
     ap.add_argument("--batches", type=int, nargs="*", default=None)
     ap.add_argument("--fleet", action="store_true")
     ap.add_argument("--signals", action="store_true")
+    ap.add_argument("--panel", action="store_true")
     args = ap.parse_args()
     if args.fleet and args.signals:
         ap.error("--fleet and --signals exclude each other")
     if args.batches is None:
-        args.batches = [1, 64, 256, 2048, 8192] if args.fleet else [1, 64, 256, 512, 2048, 8192]
+        args.batches = ([256, 2048, 8192] if args.panel else [1, 64, 256, 2048, 8192] if args.fleet else
+                        [1, 64, 256, 512, 2048, 8192])
+    mismatch = args.fleet and args.panel  # shared matrices, per-pack plant maps
     rounds = max(3, args.rounds)
     import torch
 
@@ -73,6 +85,8 @@ def main():
         X0 = torch.from_numpy((np.random.default_rng(B).random((B, nx)) - 0.5).astype(np.float32)).to(dev)
         if args.fleet:
             qp, pl = problems.battery_fleet(4, 10, problems.battery_fleet_caps(B, 4, B))
+            if mismatch:
+                qp.ML, qp.G, pl.PM = qp.ML[0], qp.G[0], np.stack([pl.PM[0]] * B)
             dML, dG, dPM, dPg, dg0, dA, dB = (t32(a) for a in (qp.ML, qp.G, pl.PM, pl.Pg, pl.g0, pl.A, pl.B))
         var = {}
         sig = None
@@ -81,14 +95,17 @@ def main():
             sig = torch.from_numpy(np.concatenate([rng.uniform(-5, 5, (steps, B, 1)),
                                                    rng.uniform(-0.1, 0.1, (steps, B, nx))],
                                                   axis=-1).astype(np.float32)).to(dev)
-        for name in ("lockstep", "async") + (("async_1wg",) if args.fleet else ()) + (
-                ("sig_lockstep", "sig_async") if args.signals else ()):
+        for name in ("lockstep", "async") + (("async_1wg",) if args.fleet and not mismatch else ()) + (
+                ("panel",) if args.panel else ()) + (("sig_lockstep", "sig_async") if args.signals else ()) + (
+                ("sig_panel",) if args.signals and args.panel else ()):
             s = gpad_mpc.GpadSolver(0)
-            s.setup(dML, dG, float(np.float32(qp.L)), n=n, m=m, batch=B, shared=not args.fleet)
+            s.setup(dML, dG, float(np.float32(qp.L)), n=n, m=m, batch=B, shared=mismatch or not args.fleet)
             s.setup_plant(dPM, dPg, g0=dg0, A=dA, B=dB)
             if name.startswith("sig_"):
                 s.setup_signals(dSM, dSg, dE)
-            s.set_option("loop_async", int(not name.endswith("lockstep")))
+            s.set_option("loop_async", int("async" in name))
+            if args.panel:  # (left alone otherwise: the tool also runs on builds older than the option)
+                s.set_option("loop_panel", int(name.endswith("panel")))
             if name == "async_1wg":
                 s.set_option("duo_max_grid", cus)
             buf = dict(x=torch.empty(B, nx, device=dev), z=torch.empty(B, n, device=dev),
@@ -115,7 +132,8 @@ def main():
                    if not torch.equal(var[base(v)][1][k].view(torch.int32), var[v][1][k].view(torch.int32))]
             if any(not np.array_equal(its[base(v)], its[v]) for v in var):
                 bad.append("iters")
-            if bad or any((kern[v] == "loop") != (v != base(v)) for v in var):
+            want = lambda v: "loop_panel" if v.endswith("panel") else "loop"  # noqa: E731
+            if bad or any((kern[v] == want(v)) != (v != base(v)) or kern[v] is None for v in var):
                 print(json.dumps({"batch": B, "mode": mname, "error": "outputs differ" if bad else "wrong kernel",
                                   "differ": bad, "kernels": kern}))
                 break
@@ -141,7 +159,14 @@ def main():
                 "wall_ms": {k: [round(x, 4) for x in v] for k, v in wall.items()},
                 "mpc_steps_per_s": {k: round(v, 1) for k, v in rate.items()},
                 "async_over_lockstep": round(rate["async"] / rate["lockstep"], 3), "faster": faster,
-                **({"async_1wg_over_async": round(rate["async_1wg"] / rate["async"], 3)} if args.fleet else {}),
+                **({"async_1wg_over_async": round(rate["async_1wg"] / rate["async"], 3)} if "async_1wg" in var else {}),
+                **({"panel_over_lockstep": round(rate["panel"] / rate["lockstep"], 3),
+                    "panel_over_async": round(rate["panel"] / rate["async"], 3),
+                    "panel_faster": ("panel" if max(ms["panel"]) < min(ms["lockstep"]) else
+                                     "lockstep" if min(ms["panel"]) > max(ms["lockstep"]) else "none")}
+                   if args.panel else {}),
+                **({"sig_panel_over_sig_lockstep": round(rate["sig_panel"] / rate["sig_lockstep"], 3)}
+                   if args.panel and args.signals else {}),
                 **({"sig_mean_iters_per_solve": round(float(its["sig_async"].mean()), 1),
                     "sig_async_over_sig_lockstep": round(rate["sig_async"] / rate["sig_lockstep"], 3),
                     "sig_over_plain": {"lockstep": round(rate["sig_lockstep"] / rate["lockstep"], 3),
