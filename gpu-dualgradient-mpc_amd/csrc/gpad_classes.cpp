@@ -1,0 +1,584 @@
+// gpad_classes.cpp -- the class binding: a fleet made of K plant classes (SKUs, capacity bins, ageing
+// bins) on the shared-matrix engines (include/gpad.h gpad_setup_classes).
+//
+// A fleet bound with dims.shared = 0 carries one matrix pair per pack and has no MFMA engine; a fleet
+// of a few pack types needs only K pairs.  The binding composes what exists, as gpad_group.cpp does for
+// devices: the parent handle keeps, per non-empty class, one child libgpad handle on the same device
+// and the same stream, bound through the public C-ABI with gpad_setup (shared = 1, batch = the class
+// size, GPAD_MEM_DEVICE; the caller's dtype, schedule, check_every, kernel and tol_gap).  Every class
+// so picks its own engine for its own size -- panel pairs, phased compaction, finisher, the one-launch
+// loops -- and no solve kernel knows about classes.
+//
+// Data path of a call, the same for host and device callers:
+//   (host callers) inputs staged to a device workspace in the caller's order
+//   gather  : rows -> a class-sorted device workspace, class k's rows one contiguous slice (one launch)
+//   solve   : child k works on its slice in place; the children run one after the other on the
+//             handle's stream (a loop: class 0's `steps` steps, then class 1's ...).  Classes are
+//             independent, so the order changes no result.
+//   scatter : sorted rows -> the caller's order (one launch), trajectories from each class's
+//             [steps][count_k][len] block (one launch); (host callers) copied out.
+// Per-step counts and codes are placed by the host from each child's gpad_last_stats.
+//
+// The per-instance arithmetic is that of the engines, which is the oracle's whatever the engine, so the
+// results are bit for bit those of the shared = 0 binding of the same fleet.
+//
+// Not in this file: classes running concurrently on several streams (each class pays its own tail per
+// call), exogenous signals, per-pack true plants under a class binding, Hessian branches.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <string>
+#include <vector>
+
+#include "../../include/gpad.h"
+#include "gpad_abi.h"
+#include "gpad_classes.h"
+#include "gpad_internal.h"
+
+namespace {
+
+int cfail(int code, const std::string& msg) { return gpad::set_last_error(code, msg); }
+
+#define C_HIP(expr)                                                                                   \
+    do {                                                                                              \
+        hipError_t _e = (expr);                                                                       \
+        if (_e != hipSuccess)                                                                         \
+            return cfail(_e == hipErrorOutOfMemory ? GPAD_ERR_NOMEM : GPAD_ERR_HIP,                   \
+                         std::string(#expr) + ": " + hipGetErrorName(_e) + " (code " +                \
+                             std::to_string((int)_e) + "): " + hipGetErrorString(_e));                \
+    } while (0)
+
+size_t esz(int dtype) { return dtype == GPAD_DTYPE_F64 ? sizeof(double) : sizeof(float); }
+
+struct Buf {
+    void* p = nullptr;
+    size_t bytes = 0;
+    int ensure(size_t want) {
+        if (want <= bytes && p) return GPAD_OK;
+        release();
+        if (want == 0) return GPAD_OK;
+        const hipError_t e = hipMalloc(&p, want);
+        if (e != hipSuccess) {
+            p = nullptr;
+            return cfail(e == hipErrorOutOfMemory ? GPAD_ERR_NOMEM : GPAD_ERR_HIP,
+                         "class binding: hipMalloc(" + std::to_string(want) + " bytes): " + hipGetErrorString(e));
+        }
+        bytes = want;
+        return GPAD_OK;
+    }
+    void release() {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        bytes = 0;
+    }
+};
+
+}  // namespace
+
+namespace gpad {
+
+struct ClassBinding {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    gpad_dims_t dims{};               // the caller's: the whole batch, the caller's memory kind
+    int K = 0;
+    std::vector<int> perm, offsets;   // class_order
+    std::vector<gpad_handle_t> child; // [K]; null for an empty class
+    int major = 0;                    // the class with the most instances (ties: the lowest): stats kernel
+    Buf idx;                          // device: perm[batch] | pos_off[batch] | pos_cnt[batch]
+    Buf sorted, stage;                // class-sorted workspace; host callers' staging in caller order
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    bool timed = false;
+    bool plant = false, plant_dyn = false;
+    int nx = 0, nu = 0;
+    int last_steps = 0;               // solves per instance of the last run (0: no run yet)
+    std::vector<int> it, cd;          // one child's counts and codes on their way to the caller
+
+    int count(int k) const { return offsets[k + 1] - offsets[k]; }
+    const int* d_perm() const { return (const int*)idx.p; }
+    const int* d_pos_off() const { return (const int*)idx.p + dims.batch; }
+    const int* d_pos_cnt() const { return (const int*)idx.p + 2 * (size_t)dims.batch; }
+};
+
+bool class_order(const int* class_of, int batch, int K, int* perm, int* offsets) {
+    std::vector<int> cnt((size_t)K + 1, 0);
+    for (int b = 0; b < batch; ++b) {
+        if (class_of[b] < 0 || class_of[b] >= K) return false;
+        ++cnt[(size_t)class_of[b] + 1];
+    }
+    for (int k = 0; k < K; ++k) cnt[(size_t)k + 1] += cnt[k];
+    for (int k = 0; k <= K; ++k) offsets[k] = cnt[k];
+    for (int b = 0; b < batch; ++b) perm[cnt[class_of[b]]++] = b;  // ascending b inside a class: stable
+    return true;
+}
+
+void classes_free(ClassBinding* cb) {
+    if (!cb) return;
+    (void)hipSetDevice(cb->device);
+    for (gpad_handle_t c : cb->child)
+        if (c) (void)gpad_destroy(c);  // (synchronises the stream first)
+    cb->idx.release();
+    cb->sorted.release();
+    cb->stage.release();
+    if (cb->ev0) (void)hipEventDestroy(cb->ev0);
+    if (cb->ev1) (void)hipEventDestroy(cb->ev1);
+    delete cb;
+}
+
+// the parent's options on a new child (gpad_set_option calls made before the binding)
+static int apply_tuning(gpad_handle_t c, const Tuning& t) {
+    const Tuning def{};
+    const int opts[][2] = {{GPAD_OPT_PHASE_LEN, t.phase_len},
+                           {GPAD_OPT_FINISH_THRESH, t.finish_thresh == def.finish_thresh ? GPAD_OPT_DEFAULT : t.finish_thresh},
+                           {GPAD_OPT_PLAN, t.plan},
+                           {GPAD_OPT_PHASED, t.phased},
+                           {GPAD_OPT_LPT, t.lpt},
+                           {GPAD_OPT_PANEL_MAX_GRID, t.panel_max_grid},
+                           {GPAD_OPT_DUO_MAX_GRID, t.duo_max_grid},
+                           {GPAD_OPT_FLAT_PANEL_MIN, t.flat_panel_min == def.flat_panel_min ? GPAD_OPT_DEFAULT : t.flat_panel_min},
+                           {GPAD_OPT_FLAT_PANELS, t.flat_panels},
+                           {GPAD_OPT_FLAT_WAVES, t.flat_waves},
+                           {GPAD_OPT_FLAT_A_LDS, t.flat_a_lds},
+                           {GPAD_OPT_DEBUG_DROP_HANDOFF, t.debug_drop_handoff},
+                           {GPAD_OPT_P64_RELAY, 1 - t.p64_no_relay},
+                           {GPAD_OPT_P64_REFILL, 1 - t.p64_no_refill},
+                           {GPAD_OPT_LOOP_ASYNC, t.loop_async},
+                           {GPAD_OPT_LOOP_PANEL, t.loop_panel}};
+    for (const auto& o : opts) {
+        const int rc = gpad_set_option(c, o[0], o[1]);
+        if (rc) return rc;
+    }
+    return GPAD_OK;
+}
+
+static int setup_body(ClassBinding* cb, const Tuning& tune, const void* ML, const void* G, double L) {
+    const gpad_dims_t& d = cb->dims;
+    const int batch = d.batch, K = cb->K;
+    C_HIP(hipEventCreate(&cb->ev0));
+    C_HIP(hipEventCreate(&cb->ev1));
+    // perm | pos_off | pos_cnt on the device
+    std::vector<int> host_idx(3 * (size_t)batch);
+    cb->major = 0;
+    for (int k = 0; k < K; ++k) {
+        if (cb->count(k) > cb->count(cb->major)) cb->major = k;
+        for (int pos = cb->offsets[k]; pos < cb->offsets[k + 1]; ++pos) {
+            host_idx[(size_t)batch + pos] = cb->offsets[k];
+            host_idx[2 * (size_t)batch + pos] = cb->count(k);
+        }
+    }
+    std::copy(cb->perm.begin(), cb->perm.end(), host_idx.begin());
+    int rc = cb->idx.ensure(sizeof(int) * host_idx.size());
+    if (rc) return rc;
+    C_HIP(hipMemcpyAsync(cb->idx.p, host_idx.data(), sizeof(int) * host_idx.size(), hipMemcpyHostToDevice, cb->stream));
+    C_HIP(hipStreamSynchronize(cb->stream));
+    // the K matrix pairs on the device: the children are GPAD_MEM_DEVICE handles
+    const size_t mat = (size_t)d.n * d.m * esz(d.dtype);
+    const char* dML = (const char*)ML;
+    const char* dG = (const char*)G;
+    Buf up;
+    if (d.memory == GPAD_MEM_HOST) {
+        if ((rc = up.ensure(2 * mat * K))) return rc;
+        hipError_t e = hipMemcpyAsync(up.p, ML, mat * K, hipMemcpyHostToDevice, cb->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync((char*)up.p + mat * K, G, mat * K, hipMemcpyHostToDevice, cb->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(cb->stream);
+        if (e != hipSuccess) {
+            up.release();
+            return cfail(GPAD_ERR_HIP, std::string("gpad_setup_classes: matrix upload: ") + hipGetErrorString(e));
+        }
+        dML = (const char*)up.p;
+        dG = dML + mat * K;
+    }
+    cb->child.assign((size_t)K, nullptr);
+    for (int k = 0; k < K && !rc; ++k) {
+        if (cb->count(k) == 0) continue;
+        gpad_dims_t cd = d;
+        cd.batch = cb->count(k);
+        cd.shared = 1;
+        cd.memory = GPAD_MEM_DEVICE;
+        if ((rc = gpad_create(&cb->child[k], cb->device, cb->stream))) break;
+        if ((rc = gpad_setup(cb->child[k], &cd, dML + mat * k, dG + mat * k, L))) break;  // (synchronises)
+        rc = apply_tuning(cb->child[k], tune);
+    }
+    up.release();
+    return rc;
+}
+
+int classes_setup(ClassBinding** out, int device, hipStream_t stream, const Tuning& tune, const gpad_dims_t* dims,
+                  int K, const int* class_of, const void* ML, const void* G, double L) {
+    *out = nullptr;
+    if (!dims) return cfail(GPAD_ERR_INVALID, "gpad_setup_classes: null dims");
+    if (dims->n <= 0 || dims->m <= 0 || dims->batch <= 0)
+        return cfail(GPAD_ERR_INVALID, "gpad_setup_classes: dims: n, m, batch must be positive");
+    if (dims->shared != 1)
+        return cfail(GPAD_ERR_INVALID, "gpad_setup_classes: dims.shared must be 1 (matrices are shared inside a class)");
+    if (dims->dtype != GPAD_DTYPE_F32 && dims->dtype != GPAD_DTYPE_F64)
+        return cfail(GPAD_ERR_INVALID, "gpad_setup_classes: dims: bad dtype");
+    if (dims->memory != GPAD_MEM_HOST && dims->memory != GPAD_MEM_DEVICE)
+        return cfail(GPAD_ERR_INVALID, "gpad_setup_classes: dims: bad memory kind");
+    if (K < 1 || K > dims->batch) return cfail(GPAD_ERR_INVALID, "gpad_setup_classes: need 1 <= K <= dims.batch");
+    if (!class_of || !ML || !G) return cfail(GPAD_ERR_INVALID, "gpad_setup_classes: null argument");
+    if (!(L > 0.0) || !std::isfinite(L)) return cfail(GPAD_ERR_INVALID, "gpad_setup_classes: L must be > 0");
+    ClassBinding* cb = new ClassBinding();
+    cb->device = device;
+    cb->stream = stream;
+    cb->dims = *dims;
+    cb->K = K;
+    cb->perm.resize((size_t)dims->batch);
+    cb->offsets.resize((size_t)K + 1);
+    if (!class_order(class_of, dims->batch, K, cb->perm.data(), cb->offsets.data())) {
+        classes_free(cb);
+        return cfail(GPAD_ERR_INVALID, "gpad_setup_classes: class_of holds an id outside 0..K-1");
+    }
+    const int rc = setup_body(cb, tune, ML, G, L);  // (the rest of dims is validated by the children's gpad_setup)
+    if (rc) {
+        classes_free(cb);
+        return rc;
+    }
+    *out = cb;
+    return GPAD_OK;
+}
+
+int classes_set_stream(ClassBinding* cb, hipStream_t stream) {
+    for (gpad_handle_t c : cb->child) {
+        if (!c) continue;
+        const int rc = gpad_set_stream(c, stream);
+        if (rc) return rc;
+    }
+    cb->stream = stream;
+    return GPAD_OK;
+}
+
+int classes_set_option(ClassBinding* cb, int option, int value) {
+    for (gpad_handle_t c : cb->child) {
+        if (!c) continue;
+        const int rc = gpad_set_option(c, option, value);
+        if (rc) return rc;
+    }
+    return GPAD_OK;
+}
+
+int classes_setup_plant(ClassBinding* cb, bool per_class, int nx, int nu, const void* PM, const void* M0,
+                        const void* Pg, const void* g0, const void* A, const void* B) {
+    const char* fn = per_class ? "gpad_setup_plant_classes" : "gpad_setup_plant";
+    if (nx <= 0 || nu < 0 || !PM || !Pg) return cfail(GPAD_ERR_INVALID, std::string(fn) + ": bad arguments");
+    if ((A == nullptr) != (B == nullptr) || (A && nu == 0))
+        return cfail(GPAD_ERR_INVALID, std::string(fn) + ": give A and B together (nu >= 1)");
+    const gpad_dims_t& d = cb->dims;
+    if (nu > d.n) return cfail(GPAD_ERR_INVALID, std::string(fn) + ": nu > n");
+    const size_t es = esz(d.dtype), copies = per_class ? (size_t)cb->K : 1;
+    const void* src[6] = {PM, M0, Pg, g0, A, B};
+    const size_t elems[6] = {(size_t)d.n * nx, (size_t)d.n, (size_t)d.m * nx, (size_t)d.m, (size_t)nx * nx,
+                             (size_t)nx * nu};
+    const char* dev[6];
+    Buf up;
+    if (d.memory == GPAD_MEM_HOST) {  // the children take device pointers
+        size_t total = 0;
+        for (int i = 0; i < 6; ++i) total += src[i] ? elems[i] * copies : 0;
+        int rc = up.ensure(es * total);
+        if (rc) return rc;
+        size_t off = 0;
+        hipError_t e = hipSuccess;
+        for (int i = 0; i < 6 && e == hipSuccess; ++i) {
+            dev[i] = src[i] ? (const char*)up.p + es * off : nullptr;
+            if (!src[i] || elems[i] == 0) continue;
+            e = hipMemcpyAsync((char*)up.p + es * off, src[i], es * elems[i] * copies, hipMemcpyHostToDevice, cb->stream);
+            off += elems[i] * copies;
+        }
+        if (e == hipSuccess) e = hipStreamSynchronize(cb->stream);
+        if (e != hipSuccess) {
+            up.release();
+            return cfail(GPAD_ERR_HIP, std::string(fn) + ": map upload: " + hipGetErrorString(e));
+        }
+    } else {
+        for (int i = 0; i < 6; ++i) dev[i] = (const char*)src[i];
+    }
+    cb->plant = false;  // (a failed rebinding leaves none)
+    int rc = GPAD_OK;
+    for (int k = 0; k < cb->K && !rc; ++k) {
+        if (!cb->child[k]) continue;
+        const void* a[6];
+        for (int i = 0; i < 6; ++i) a[i] = dev[i] ? dev[i] + (per_class ? es * elems[i] * k : 0) : nullptr;
+        rc = gpad_setup_plant(cb->child[k], nx, nu, a[0], a[1], a[2], a[3], a[4], a[5]);  // (synchronises)
+    }
+    up.release();
+    if (rc) return rc;
+    cb->plant = true;
+    cb->plant_dyn = A != nullptr;
+    cb->nx = nx;
+    cb->nu = nu;
+    return GPAD_OK;
+}
+
+// The stats of the last run from every child (each call synchronises the stream and reports that child's
+// device error word); counts and codes placed in the caller's order.
+int classes_last_stats(ClassBinding* cb, gpad_stats_t* st) {
+    if (cb->last_steps <= 0) return cfail(GPAD_ERR_NOT_SETUP, "gpad_last_stats: no run yet");
+    const int batch = cb->dims.batch, steps = cb->last_steps;
+    st->iterations = 0;
+    st->converged = 0;
+    st->total_iterations = 0;
+    st->kernel = 0;
+    st->kernel_ms = 0.0;
+    st->tol_floor = 0.0;
+    st->flags = 0;
+    int first_err = GPAD_OK;
+    std::string first_msg;
+    for (int k = 0; k < cb->K; ++k) {
+        if (!cb->child[k]) continue;
+        const int cnt = cb->count(k), off = cb->offsets[k];
+        gpad_stats_t cs{};
+        if (st->iters) {
+            cb->it.resize((size_t)steps * cnt);
+            cs.iters = cb->it.data();
+        }
+        if (st->codes) {
+            cb->cd.resize((size_t)steps * cnt);
+            cs.codes = cb->cd.data();
+        }
+        const int rc = gpad_last_stats(cb->child[k], &cs);
+        if (rc && rc != GPAD_ERR_DEVICE) return rc;
+        if (rc && !first_err) {  // every child is still asked: each reports (and clears) its own word
+            first_err = rc;
+            first_msg = gpad_last_error();
+        }
+        st->iterations = std::max(st->iterations, cs.iterations);
+        st->converged += cs.converged;
+        st->total_iterations += cs.total_iterations;
+        if (std::isnan(cs.tol_floor) || cs.tol_floor > st->tol_floor) st->tol_floor = cs.tol_floor;
+        st->flags |= cs.flags;
+        if (k == cb->major) st->kernel = cs.kernel;
+        for (int t = 0; t < steps; ++t)
+            for (int i = 0; i < cnt; ++i) {
+                const size_t to = (size_t)t * batch + cb->perm[(size_t)off + i], from = (size_t)t * cnt + i;
+                if (st->iters) st->iters[to] = cb->it[from];
+                if (st->codes) st->codes[to] = cb->cd[from];
+            }
+    }
+    float ms = 0.0f;
+    if (cb->timed && hipEventElapsedTime(&ms, cb->ev0, cb->ev1) == hipSuccess) st->kernel_ms = ms;
+    if (first_err) return cfail(first_err, "class binding: " + first_msg);
+    return GPAD_OK;
+}
+
+int classes_sync(ClassBinding* cb) {
+    int first_err = GPAD_OK;
+    std::string first_msg;
+    for (gpad_handle_t c : cb->child) {
+        if (!c) continue;
+        const int rc = gpad_sync(c);
+        if (rc && rc != GPAD_ERR_DEVICE) return rc;
+        if (rc && !first_err) {
+            first_err = rc;
+            first_msg = gpad_last_error();
+        }
+    }
+    if (first_err) return cfail(first_err, "class binding: " + first_msg);
+    return GPAD_OK;
+}
+
+int classes_accumulate(ClassBinding* cb, long long* acc) {
+    if (cb->last_steps <= 0) return cfail(GPAD_ERR_NOT_SETUP, "gpad_accumulate_iterations: no run yet");
+    for (gpad_handle_t c : cb->child) {
+        if (!c) continue;
+        const int rc = gpad_accumulate_iterations(c, acc);
+        if (rc) return rc;
+    }
+    return GPAD_OK;
+}
+
+// after the device work of a call is enqueued: stats (synchronous), or a sync for host callers
+static int finish_call(ClassBinding* cb, gpad_stats_t* st) {
+    if (st) return classes_last_stats(cb, st);
+    if (cb->dims.memory == GPAD_MEM_HOST) return classes_sync(cb);
+    return GPAD_OK;
+}
+
+template <typename T>
+static int run_typed(ClassBinding* cb, T* z, T* y, const T* M, const T* g, int N, double tol, gpad_stats_t* st) {
+    const gpad_dims_t& d = cb->dims;
+    const size_t batch = (size_t)d.batch, zn = batch * d.n, yn = batch * d.m;
+    const bool host = d.memory == GPAD_MEM_HOST;
+    int rc = cb->sorted.ensure(sizeof(T) * 2 * (zn + yn));
+    if (rc) return rc;
+    T* sz = (T*)cb->sorted.p;
+    T* sy = sz + zn;
+    T* sM = sy + yn;
+    T* sg = sM + zn;
+    T *cz = z, *cy = y;  // the caller-order arrays on the device
+    const T *cM = M, *cg = g;
+    if (host) {
+        if ((rc = cb->stage.ensure(sizeof(T) * 2 * (zn + yn)))) return rc;
+        T* b = (T*)cb->stage.p;
+        cz = b;
+        cy = b + zn;
+        T* wM = b + zn + yn;
+        T* wg = wM + zn;
+        C_HIP(hipMemcpyAsync(cz, z, sizeof(T) * zn, hipMemcpyHostToDevice, cb->stream));
+        C_HIP(hipMemcpyAsync(cy, y, sizeof(T) * yn, hipMemcpyHostToDevice, cb->stream));
+        C_HIP(hipMemcpyAsync(wM, M, sizeof(T) * zn, hipMemcpyHostToDevice, cb->stream));
+        C_HIP(hipMemcpyAsync(wg, g, sizeof(T) * yn, hipMemcpyHostToDevice, cb->stream));
+        cM = wM;
+        cg = wg;
+    }
+    C_HIP(hipEventRecord(cb->ev0, cb->stream));
+    RowMove<T> in{};
+    in.count = 4;
+    const T* isrc[4] = {cz, cy, cM, cg};
+    T* idst[4] = {sz, sy, sM, sg};
+    const int ilen[4] = {d.n, d.m, d.n, d.m};
+    for (int a = 0; a < 4; ++a) {
+        in.src[a] = isrc[a];
+        in.dst[a] = idst[a];
+        in.len[a] = ilen[a];
+    }
+    C_HIP(launch_class_gather<T>(in, cb->d_perm(), d.batch, cb->stream));
+    cb->last_steps = 1;
+    cb->timed = false;
+    for (int k = 0; k < cb->K; ++k) {
+        if (!cb->child[k]) continue;
+        const size_t off = (size_t)cb->offsets[k];
+        if ((rc = gpad_run(cb->child[k], sz + off * d.n, sy + off * d.m, sM + off * d.n, sg + off * d.m, N, tol,
+                           nullptr)))
+            return rc;
+    }
+    RowMove<T> out{};
+    out.count = 2;
+    out.src[0] = sz;
+    out.dst[0] = cz;
+    out.len[0] = d.n;
+    out.src[1] = sy;
+    out.dst[1] = cy;
+    out.len[1] = d.m;
+    C_HIP(launch_class_scatter<T>(out, cb->d_perm(), d.batch, cb->stream));
+    C_HIP(hipEventRecord(cb->ev1, cb->stream));
+    cb->timed = true;
+    if (host) {
+        C_HIP(hipMemcpyAsync(z, cz, sizeof(T) * zn, hipMemcpyDeviceToHost, cb->stream));
+        C_HIP(hipMemcpyAsync(y, cy, sizeof(T) * yn, hipMemcpyDeviceToHost, cb->stream));
+    }
+    return finish_call(cb, st);
+}
+
+int classes_run(ClassBinding* cb, void* z, void* y, const void* M, const void* g, int N, double tol,
+                gpad_stats_t* st) {
+    if (!z || !y || !M || !g) return cfail(GPAD_ERR_INVALID, "gpad_run: null vector");
+    if (N < 0) return cfail(GPAD_ERR_INVALID, "gpad_run: N < 0");
+    if (!(tol <= 0.0) && !std::isfinite(tol)) return cfail(GPAD_ERR_INVALID, "gpad_run: bad tol");
+    if (cb->dims.dtype == GPAD_DTYPE_F64)
+        return run_typed<double>(cb, (double*)z, (double*)y, (const double*)M, (const double*)g, N, tol, st);
+    return run_typed<float>(cb, (float*)z, (float*)y, (const float*)M, (const float*)g, N, tol, st);
+}
+
+template <typename T>
+static int state_typed(ClassBinding* cb, T* x, T* z, T* y, int steps, int N, double tol, int warm, T* xs, T* us,
+                       gpad_stats_t* st) {
+    const gpad_dims_t& d = cb->dims;
+    const int nx = cb->nx, nu = cb->nu;
+    const bool loop = steps > 0, host = d.memory == GPAD_MEM_HOST;
+    const bool zy_in = !loop || warm;  // a cold loop starts every step from z = y = 0: nothing to bring in
+    const size_t batch = (size_t)d.batch, zn = batch * d.n, yn = batch * d.m, xn = batch * nx;
+    const size_t xsn = loop && xs ? (size_t)steps * xn : 0, usn = loop && us ? (size_t)steps * batch * nu : 0;
+    const size_t elems = xn + zn + yn + xsn + usn;
+    int rc = cb->sorted.ensure(sizeof(T) * elems);
+    if (rc) return rc;
+    T* sx = (T*)cb->sorted.p;
+    T* sz = sx + xn;
+    T* sy = sz + zn;
+    T* sxs = xsn ? sy + yn : nullptr;
+    T* sus = usn ? sy + yn + xsn : nullptr;
+    T *cx = x, *cz = z, *cy = y, *cxs = xs, *cus = us;  // the caller-order arrays on the device
+    if (host) {
+        if ((rc = cb->stage.ensure(sizeof(T) * elems))) return rc;
+        cx = (T*)cb->stage.p;
+        cz = cx + xn;
+        cy = cz + zn;
+        cxs = xsn ? cy + yn : nullptr;
+        cus = usn ? cy + yn + xsn : nullptr;
+        C_HIP(hipMemcpyAsync(cx, x, sizeof(T) * xn, hipMemcpyHostToDevice, cb->stream));
+        if (zy_in) {
+            C_HIP(hipMemcpyAsync(cz, z, sizeof(T) * zn, hipMemcpyHostToDevice, cb->stream));
+            C_HIP(hipMemcpyAsync(cy, y, sizeof(T) * yn, hipMemcpyHostToDevice, cb->stream));
+        }
+    }
+    C_HIP(hipEventRecord(cb->ev0, cb->stream));
+    RowMove<T> in{};
+    in.count = zy_in ? 3 : 1;
+    in.src[0] = cx;
+    in.dst[0] = sx;
+    in.len[0] = nx;
+    in.src[1] = cz;
+    in.dst[1] = sz;
+    in.len[1] = d.n;
+    in.src[2] = cy;
+    in.dst[2] = sy;
+    in.len[2] = d.m;
+    C_HIP(launch_class_gather<T>(in, cb->d_perm(), d.batch, cb->stream));
+    cb->last_steps = loop ? steps : 1;
+    cb->timed = false;
+    for (int k = 0; k < cb->K; ++k) {
+        if (!cb->child[k]) continue;
+        const size_t off = (size_t)cb->offsets[k];
+        T *kx = sx + off * nx, *kz = sz + off * d.n, *ky = sy + off * d.m;
+        if (loop)  // class k's trajectories: one contiguous [steps][count_k][len] block
+            rc = gpad_closed_loop(cb->child[k], kx, kz, ky, steps, N, tol, warm, sxs ? sxs + (size_t)steps * off * nx : nullptr,
+                                  sus ? sus + (size_t)steps * off * nu : nullptr, nullptr);
+        else
+            rc = gpad_run_state(cb->child[k], kx, kz, ky, N, tol, nullptr);
+        if (rc) return rc;
+    }
+    RowMove<T> out{};
+    out.count = 0;
+    auto add = [&](const T* src, T* dst, int len) {
+        out.src[out.count] = src;
+        out.dst[out.count] = dst;
+        out.len[out.count] = len;
+        ++out.count;
+    };
+    if (loop) add(sx, cx, nx);  // (gpad_run_state leaves x alone)
+    add(sz, cz, d.n);
+    add(sy, cy, d.m);
+    C_HIP(launch_class_scatter<T>(out, cb->d_perm(), d.batch, cb->stream));
+    if (xsn || usn) {
+        TrajMove<T> tr{};
+        tr.count = 0;
+        if (xsn) {
+            tr.src[tr.count] = sxs;
+            tr.dst[tr.count] = cxs;
+            tr.len[tr.count++] = nx;
+        }
+        if (usn) {
+            tr.src[tr.count] = sus;
+            tr.dst[tr.count] = cus;
+            tr.len[tr.count++] = nu;
+        }
+        C_HIP(launch_class_traj_scatter<T>(tr, cb->d_perm(), cb->d_pos_off(), cb->d_pos_cnt(), d.batch, steps,
+                                           cb->stream));
+    }
+    C_HIP(hipEventRecord(cb->ev1, cb->stream));
+    cb->timed = true;
+    if (host) {
+        if (loop) C_HIP(hipMemcpyAsync(x, cx, sizeof(T) * xn, hipMemcpyDeviceToHost, cb->stream));
+        C_HIP(hipMemcpyAsync(z, cz, sizeof(T) * zn, hipMemcpyDeviceToHost, cb->stream));
+        C_HIP(hipMemcpyAsync(y, cy, sizeof(T) * yn, hipMemcpyDeviceToHost, cb->stream));
+        if (xsn) C_HIP(hipMemcpyAsync(xs, cxs, sizeof(T) * xsn, hipMemcpyDeviceToHost, cb->stream));
+        if (usn) C_HIP(hipMemcpyAsync(us, cus, sizeof(T) * usn, hipMemcpyDeviceToHost, cb->stream));
+    }
+    return finish_call(cb, st);
+}
+
+int classes_state(ClassBinding* cb, void* x, void* z, void* y, int steps, int N, double tol, int warm, void* xs,
+                  void* us, gpad_stats_t* st) {
+    const std::string where = steps > 0 ? "gpad_closed_loop" : "gpad_run_state";
+    if (!cb->plant) return cfail(GPAD_ERR_NOT_SETUP, where + ": call gpad_setup_plant after gpad_setup_classes");
+    if (steps > 0 && !cb->plant_dyn) return cfail(GPAD_ERR_NOT_SETUP, where + ": plant bound without A, B");
+    if (!x || !z || !y) return cfail(GPAD_ERR_INVALID, where + ": null vector");
+    if (N < 0 || steps < 0) return cfail(GPAD_ERR_INVALID, where + ": N, steps must be >= 0");
+    if (!(tol <= 0.0) && !std::isfinite(tol)) return cfail(GPAD_ERR_INVALID, where + ": bad tol");
+    if (cb->dims.dtype == GPAD_DTYPE_F64)
+        return state_typed<double>(cb, (double*)x, (double*)z, (double*)y, steps, N, tol, warm, (double*)xs,
+                                   (double*)us, st);
+    return state_typed<float>(cb, (float*)x, (float*)z, (float*)y, steps, N, tol, warm, (float*)xs, (float*)us, st);
+}
+
+}  // namespace gpad

@@ -1,0 +1,69 @@
+// gpad_classes.h -- the class binding (gpad_setup_classes, include/gpad.h): a fleet of K plant classes
+// solved class by class as shared-matrix sub-batches.  Shared by gpad_host.cpp (the entry points branch
+// here at their top), gpad_classes.cpp (the runtime) and gpad_classes.hip (the row permutations).
+//
+// Not here: classes running concurrently on several streams (they run one after the other on the
+// handle's stream), exogenous signals, per-pack true plants under a class binding, Hessian branches.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include "../../include/gpad.h"
+#include "gpad_internal.h"
+
+namespace gpad {
+
+// ---- gpad_classes.hip: row permutations between the caller's order and the class-sorted order ------
+constexpr int kClassMoveArrays = 4;
+// One launch moves up to four [batch][len] arrays.  perm[pos] = the caller's instance at sorted
+// position pos.  gather: dst[pos][:] = src[perm[pos]][:];  scatter: dst[perm[pos]][:] = src[pos][:].
+template <typename T>
+struct RowMove {
+    const T* src[kClassMoveArrays];
+    T* dst[kClassMoveArrays];
+    int len[kClassMoveArrays];
+    int count;  // arrays in use
+};
+template <typename T>
+hipError_t launch_class_gather(const RowMove<T>& mv, const int* perm, int batch, hipStream_t s);
+template <typename T>
+hipError_t launch_class_scatter(const RowMove<T>& mv, const int* perm, int batch, hipStream_t s);
+// Trajectories: every class wrote its own contiguous [steps][count_k][len] block, class k's at element
+// steps * offsets[k] * len of src; dst is the caller's [steps][batch][len].  pos_off[pos] / pos_cnt[pos]:
+// offsets[k] and count_k of the class that sorted position pos belongs to.  Up to two arrays (xs, us).
+template <typename T>
+struct TrajMove {
+    const T* src[2];
+    T* dst[2];
+    int len[2];
+    int count;
+};
+template <typename T>
+hipError_t launch_class_traj_scatter(const TrajMove<T>& mv, const int* perm, const int* pos_off,
+                                     const int* pos_cnt, int batch, int steps, hipStream_t s);
+
+// ---- gpad_classes.cpp -------------------------------------------------------------------------------
+// Host only: perm / offsets of the class-sorted order (gpad_class_order); false on an id outside 0..K-1
+bool class_order(const int* class_of, int batch, int K, int* perm, int* offsets);
+
+// The binding owns one child handle per non-empty class (same device, same stream, shared = 1,
+// GPAD_MEM_DEVICE), perm / offsets on host and device, and the workspaces.  Every function returns a
+// GPAD_* status with gpad_last_error set.
+int classes_setup(ClassBinding** out, int device, hipStream_t stream, const Tuning& tune, const gpad_dims_t* dims,
+                  int K, const int* class_of, const void* ML, const void* G, double L);
+void classes_free(ClassBinding* cb);
+int classes_set_stream(ClassBinding* cb, hipStream_t stream);
+int classes_set_option(ClassBinding* cb, int option, int value);
+// per_class: every non-NULL map holds K copies (gpad_setup_plant_classes), else one for every class
+int classes_setup_plant(ClassBinding* cb, bool per_class, int nx, int nu, const void* PM, const void* M0,
+                        const void* Pg, const void* g0, const void* A, const void* B);
+int classes_run(ClassBinding* cb, void* z, void* y, const void* M, const void* g, int N, double tol,
+                gpad_stats_t* st);
+// steps == 0: gpad_run_state; steps >= 1: gpad_closed_loop
+int classes_state(ClassBinding* cb, void* x, void* z, void* y, int steps, int N, double tol, int warm, void* xs,
+                  void* us, gpad_stats_t* st);
+int classes_last_stats(ClassBinding* cb, gpad_stats_t* st);
+int classes_accumulate(ClassBinding* cb, long long* acc);
+int classes_sync(ClassBinding* cb);
+
+}  // namespace gpad

@@ -21,6 +21,7 @@
 
 #include "../../include/gpad.h"
 #include "gpad_abi.h"
+#include "gpad_classes.h"
 #include "gpad_internal.h"
 
 namespace {
@@ -196,6 +197,8 @@ struct gpad_handle_s {
     int num_cus = 256;
     bool timed = false;
     gpad::Tuning tune;                  // gpad_set_option
+    gpad::ClassBinding* cls = nullptr;  // gpad_setup_classes: the class binding (gpad_classes.cpp), which then
+                                        // serves the handle's runs; null: none
     bool failed_run = false;            // the last run's device error was reported (fetch_status
                                         // clears the device word): later stats calls for that
                                         // run keep returning GPAD_ERR_DEVICE until the next run
@@ -248,6 +251,18 @@ static int status_error(gpad_handle_t h, const RunStatus& rs) {
                                      ((rs.err & gpad::kDevErrHandoff) ? ": a chain hand-off wait expired "
                                                                         "(the run's results are invalid)"
                                                                       : ""));
+}
+
+// gpad_setup / gpad_setup_scaled / gpad_setup_flat (and gpad_destroy) end a class binding and free what it held
+static void end_classes(gpad_handle_t h) {
+    gpad::classes_free(h->cls);
+    h->cls = nullptr;
+}
+
+// entry points a class-bound handle does not serve
+static int no_classes(const char* fn) {
+    return fail(GPAD_ERR_UNSUPPORTED, std::string(fn) + ": not available on a handle with a class binding "
+                                                        "(gpad_setup_classes)");
 }
 
 extern "C" {
@@ -311,6 +326,7 @@ int gpad_destroy(gpad_handle_t h) {
         if (!h) return GPAD_OK;
         (void)hipSetDevice(h->device);
         (void)hipStreamSynchronize(h->stream);
+        end_classes(h);
         h->MGt.release();
         h->GLt.release();
         h->GLx.release();
@@ -345,57 +361,66 @@ int gpad_set_stream(gpad_handle_t h, void* stream) {
         HIP_TRY(hipSetDevice(h->device));
         HIP_TRY(hipStreamSynchronize(h->stream));  // work queued on the old stream completes first
         h->stream = static_cast<hipStream_t>(stream);
+        if (h->cls) return gpad::classes_set_stream(h->cls, h->stream);
         return GPAD_OK;
     });
+}
+
+// the handle's own option (a class binding's children each get the call forwarded, gpad_set_option below)
+static int set_own_option(gpad_handle_t h, int option, int value) {
+    gpad::Tuning& t = h->tune;
+    const gpad::Tuning def{};
+    auto set = [&](int& field, int lo, int hi, int dflt) -> int {
+        if (value == GPAD_OPT_DEFAULT) {
+            field = dflt;
+            return GPAD_OK;
+        }
+        if (value < lo || value > hi) return fail(GPAD_ERR_INVALID, "gpad_set_option: value out of range");
+        field = value;
+        return GPAD_OK;
+    };
+    const int big = 1 << 30;
+    switch (option) {
+        case GPAD_OPT_PHASE_LEN: return set(t.phase_len, 0, big, def.phase_len);
+        case GPAD_OPT_FINISH_THRESH: return set(t.finish_thresh, 0, big, def.finish_thresh);
+        case GPAD_OPT_PLAN: h->plan.nph = 0; h->plan_key = 0; return set(t.plan, 0, 1, def.plan);
+        case GPAD_OPT_PHASED: return set(t.phased, 0, 2, def.phased);
+        case GPAD_OPT_LPT: return set(t.lpt, 0, 1, def.lpt);
+        case GPAD_OPT_PANEL_MAX_GRID: return set(t.panel_max_grid, 0, big, def.panel_max_grid);
+        case GPAD_OPT_DUO_MAX_GRID: return set(t.duo_max_grid, 0, big, def.duo_max_grid);
+        case GPAD_OPT_FLAT_PANEL_MIN: return set(t.flat_panel_min, 0, big, def.flat_panel_min);
+        case GPAD_OPT_FLAT_PANELS: return set(t.flat_panels, 0, 4, def.flat_panels);
+        case GPAD_OPT_FLAT_WAVES:
+            if (value != GPAD_OPT_DEFAULT && value != 0 && value != 8 && value != 16)
+                return fail(GPAD_ERR_INVALID, "gpad_set_option: flat waves must be 0, 8 or 16");
+            return set(t.flat_waves, 0, 16, def.flat_waves);
+        case GPAD_OPT_FLAT_A_LDS: return set(t.flat_a_lds, 0, 1, def.flat_a_lds);
+        case GPAD_OPT_DEBUG_DROP_HANDOFF: return set(t.debug_drop_handoff, 0, 1, def.debug_drop_handoff);
+        case GPAD_OPT_P64_REFILL: {
+            int on = 1 - t.p64_no_refill;
+            const int rc = set(on, 0, 1, 1);
+            t.p64_no_refill = 1 - on;
+            return rc;
+        }
+        case GPAD_OPT_P64_RELAY: {
+            int on = 1 - t.p64_no_relay;
+            const int rc = set(on, 0, 1, 1);
+            t.p64_no_relay = 1 - on;
+            return rc;
+        }
+        case GPAD_OPT_LOOP_ASYNC: return set(t.loop_async, 0, 1, def.loop_async);
+        case GPAD_OPT_LOOP_PANEL: return set(t.loop_panel, 0, 1, def.loop_panel);
+        default: return fail(GPAD_ERR_INVALID, "gpad_set_option: unknown option");
+    }
 }
 
 int gpad_set_option(gpad_handle_t h, int option, int value) {
     return gpad::abi_guard("gpad_set_option", [&]() -> int {
         if (!h) return fail(GPAD_ERR_INVALID, "gpad_set_option: null handle");
-        gpad::Tuning& t = h->tune;
-        const gpad::Tuning def{};
-        auto set = [&](int& field, int lo, int hi, int dflt) -> int {
-            if (value == GPAD_OPT_DEFAULT) {
-                field = dflt;
-                return GPAD_OK;
-            }
-            if (value < lo || value > hi) return fail(GPAD_ERR_INVALID, "gpad_set_option: value out of range");
-            field = value;
-            return GPAD_OK;
-        };
-        const int big = 1 << 30;
-        switch (option) {
-            case GPAD_OPT_PHASE_LEN: return set(t.phase_len, 0, big, def.phase_len);
-            case GPAD_OPT_FINISH_THRESH: return set(t.finish_thresh, 0, big, def.finish_thresh);
-            case GPAD_OPT_PLAN: h->plan.nph = 0; h->plan_key = 0; return set(t.plan, 0, 1, def.plan);
-            case GPAD_OPT_PHASED: return set(t.phased, 0, 2, def.phased);
-            case GPAD_OPT_LPT: return set(t.lpt, 0, 1, def.lpt);
-            case GPAD_OPT_PANEL_MAX_GRID: return set(t.panel_max_grid, 0, big, def.panel_max_grid);
-            case GPAD_OPT_DUO_MAX_GRID: return set(t.duo_max_grid, 0, big, def.duo_max_grid);
-            case GPAD_OPT_FLAT_PANEL_MIN: return set(t.flat_panel_min, 0, big, def.flat_panel_min);
-            case GPAD_OPT_FLAT_PANELS: return set(t.flat_panels, 0, 4, def.flat_panels);
-            case GPAD_OPT_FLAT_WAVES:
-                if (value != GPAD_OPT_DEFAULT && value != 0 && value != 8 && value != 16)
-                    return fail(GPAD_ERR_INVALID, "gpad_set_option: flat waves must be 0, 8 or 16");
-                return set(t.flat_waves, 0, 16, def.flat_waves);
-            case GPAD_OPT_FLAT_A_LDS: return set(t.flat_a_lds, 0, 1, def.flat_a_lds);
-            case GPAD_OPT_DEBUG_DROP_HANDOFF: return set(t.debug_drop_handoff, 0, 1, def.debug_drop_handoff);
-            case GPAD_OPT_P64_REFILL: {
-                int on = 1 - t.p64_no_refill;
-                const int rc = set(on, 0, 1, 1);
-                t.p64_no_refill = 1 - on;
-                return rc;
-            }
-            case GPAD_OPT_P64_RELAY: {
-                int on = 1 - t.p64_no_relay;
-                const int rc = set(on, 0, 1, 1);
-                t.p64_no_relay = 1 - on;
-                return rc;
-            }
-            case GPAD_OPT_LOOP_ASYNC: return set(t.loop_async, 0, 1, def.loop_async);
-            case GPAD_OPT_LOOP_PANEL: return set(t.loop_panel, 0, 1, def.loop_panel);
-            default: return fail(GPAD_ERR_INVALID, "gpad_set_option: unknown option");
-        }
+        const int rc = set_own_option(h, option, value);
+        if (rc || !h->cls) return rc;
+        HIP_TRY(hipSetDevice(h->device));
+        return gpad::classes_set_option(h->cls, option, value);  // every class applies it by its own rules
     });
 }
 
@@ -403,6 +428,7 @@ int gpad_sync(gpad_handle_t h) {
     return gpad::abi_guard("gpad_sync", [&]() -> int {
         if (!h) return fail(GPAD_ERR_INVALID, "gpad_sync: null handle");
         HIP_TRY(hipSetDevice(h->device));
+        if (h->cls) return gpad::classes_sync(h->cls);
         RunStatus& rs = h->h_status;
         int rc = fetch_status(h, &rs);
         if (rc) return rc;
@@ -444,6 +470,7 @@ static int setup_impl(gpad_handle_t h, const gpad_dims_t* d, const void* A, cons
     if (!A || !B) return fail(GPAD_ERR_INVALID, "gpad_setup: null matrix");
     if (!(L > 0.0) || !std::isfinite(L)) return fail(GPAD_ERR_INVALID, "gpad_setup: L must be > 0");
     HIP_TRY(hipSetDevice(h->device));
+    end_classes(h);
     h->ready = false;
     h->flat = false;
     h->ns = 0;  // (a new problem unbinds the signals)
@@ -539,6 +566,7 @@ int gpad_setup_scaled(gpad_handle_t h, const gpad_dims_t* d, const void* MGneg, 
 int gpad_setup_hessian(gpad_handle_t h, const void* H) {
     return gpad::abi_guard("gpad_setup_hessian", [&]() -> int {
         if (!h) return fail(GPAD_ERR_INVALID, "gpad_setup_hessian: null handle");
+        if (h->cls) return no_classes("gpad_setup_hessian");
         if (!h->ready) return fail(GPAD_ERR_NOT_SETUP, "gpad_setup_hessian: call gpad_setup first");
         if (h->flat) return fail(GPAD_ERR_UNSUPPORTED, "gpad_setup_hessian: not on the flat battery path");
         h->hess_ok = false;
@@ -588,6 +616,7 @@ int gpad_setup_flat(gpad_handle_t h, const gpad_dims_t* d, int n_u, const float*
         if (n_u <= 0 || d->n % n_u != 0 || d->m < 4 * d->n)
             return fail(GPAD_ERR_INVALID, "gpad_setup_flat: need n = n_u*N and m >= 4 n_u N");
         HIP_TRY(hipSetDevice(h->device));
+        end_classes(h);
         h->ready = false;
         h->flat = false;
         h->ns = 0;
@@ -801,6 +830,10 @@ static int collect_stats(gpad_handle_t h, gpad_stats_t* st) {
 int gpad_accumulate_iterations(gpad_handle_t h, long long* acc) {
     return gpad::abi_guard("gpad_accumulate_iterations", [&]() -> int {
         if (!h || !acc) return fail(GPAD_ERR_INVALID, "gpad_accumulate_iterations: null argument");
+        if (h->cls) {
+            HIP_TRY(hipSetDevice(h->device));
+            return gpad::classes_accumulate(h->cls, acc);
+        }
         if (h->last_batch <= 0) return fail(GPAD_ERR_NOT_SETUP, "gpad_accumulate_iterations: no run yet");
         HIP_TRY(hipSetDevice(h->device));
         // counters: [steps][iters[batch] | conv[batch]]; each solve's iteration block in turn
@@ -814,6 +847,10 @@ int gpad_accumulate_iterations(gpad_handle_t h, long long* acc) {
 int gpad_last_stats(gpad_handle_t h, gpad_stats_t* st) {
     return gpad::abi_guard("gpad_last_stats", [&]() -> int {
         if (!h || !st) return fail(GPAD_ERR_INVALID, "gpad_last_stats: null argument");
+        if (h->cls) {
+            HIP_TRY(hipSetDevice(h->device));
+            return gpad::classes_last_stats(h->cls, st);
+        }
         if (h->last_batch <= 0) return fail(GPAD_ERR_NOT_SETUP, "gpad_last_stats: no run yet");
         HIP_TRY(hipSetDevice(h->device));
         return collect_stats(h, st);
@@ -823,6 +860,7 @@ int gpad_last_stats(gpad_handle_t h, gpad_stats_t* st) {
 int gpad_phase_plan(gpad_handle_t h, int* ends, int* fins, int cap, double* cost_us) {
     return gpad::abi_guard("gpad_phase_plan", [&]() -> int {
         if (!h) return fail(GPAD_ERR_INVALID, "gpad_phase_plan: null handle");
+        if (h->cls) return 0;  // (every class plans for itself)
         const int n = h->plan.nph;
         for (int i = 0; i < n && i < cap; ++i) {
             if (ends) ends[i] = h->plan.ends[i];
@@ -837,6 +875,7 @@ int gpad_last_phases(gpad_handle_t h, int* ends, int* fins, int* counts, int cap
     return gpad::abi_guard("gpad_last_phases", [&]() -> int {
         if (!h || cap < 0) return fail(GPAD_ERR_INVALID, "gpad_last_phases: bad argument");
         if (prior) *prior = 0;
+        if (h->cls) return 0;
         if (!h->last_phased || !h->pwork.p || h->flat) return 0;  // not phased: no plan, no prior
         if (prior) *prior = h->last_prior ? 1 : 0;
         const int k = std::min(cap, h->last_phases.nph);
@@ -857,6 +896,7 @@ int gpad_last_phases(gpad_handle_t h, int* ends, int* fins, int* counts, int cap
 int gpad_phase_counts(gpad_handle_t h, int* counts, int cap) {
     return gpad::abi_guard("gpad_phase_counts", [&]() -> int {
         if (!h || !counts || cap < 0) return fail(GPAD_ERR_INVALID, "gpad_phase_counts: bad argument");
+        if (h->cls) return 0;
         if (!h->last_phased || !h->pwork.p) return 0;
         HIP_TRY(hipSetDevice(h->device));
         const int k = cap < gpad::kPanelMaxPhases ? cap : gpad::kPanelMaxPhases;
@@ -1179,6 +1219,11 @@ static int run_impl(gpad_handle_t h, void* z0, void* y0, const void* M, const vo
                     double tol, const void* theta, const void* beta, bool scaled_vec,
                     gpad_stats_t* st) {
     if (!h) return fail(GPAD_ERR_INVALID, "gpad_run: null handle");
+    if (h->cls) {
+        if (scaled_vec) return no_classes("gpad_run_scaled");
+        HIP_TRY(hipSetDevice(h->device));
+        return gpad::classes_run(h->cls, z0, y0, M, g, N, tol, st);
+    }
     if (!h->ready) return fail(GPAD_ERR_NOT_SETUP, "gpad_run: call gpad_setup first");
     if (!z0 || !y0 || !M || !g) return fail(GPAD_ERR_INVALID, "gpad_run: null vector");
     if (N < 0) return fail(GPAD_ERR_INVALID, "gpad_run: N < 0");
@@ -1383,6 +1428,11 @@ static int setup_plant_impl(gpad_handle_t h, int nx, int nu, const void* PM, con
                             const void* g0, const void* A, const void* B, bool per_instance, const char* fn) {
     const std::string where(fn);
     if (!h) return fail(GPAD_ERR_INVALID, where + ": null handle");
+    if (h->cls) {
+        if (per_instance) return no_classes(fn);
+        HIP_TRY(hipSetDevice(h->device));
+        return gpad::classes_setup_plant(h->cls, false, nx, nu, PM, M0, Pg, g0, A, B);  // the same maps for every class
+    }
     if (!h->ready) return fail(GPAD_ERR_NOT_SETUP, where + ": call gpad_setup first");
     if (nx <= 0 || nu < 0 || !PM || !Pg) return fail(GPAD_ERR_INVALID, where + ": bad arguments");
     if ((A == nullptr) != (B == nullptr) || (A && nu == 0))
@@ -1435,6 +1485,52 @@ extern "C" int gpad_setup_plant_batch(gpad_handle_t h, int nx, int nu, const voi
     });
 }
 
+// ---- class binding (gpad_classes.cpp) ---------------------------------------------------------------
+extern "C" int gpad_class_order(const int* class_of, int batch, int K, int* perm, int* offsets) {
+    return gpad::abi_guard("gpad_class_order", [&]() -> int {
+        if (!class_of || !perm || !offsets) return fail(GPAD_ERR_INVALID, "gpad_class_order: null argument");
+        if (batch < 1 || K < 1) return fail(GPAD_ERR_INVALID, "gpad_class_order: batch and K must be >= 1");
+        if (!gpad::class_order(class_of, batch, K, perm, offsets))
+            return fail(GPAD_ERR_INVALID, "gpad_class_order: class_of holds an id outside 0..K-1");
+        return GPAD_OK;
+    });
+}
+
+extern "C" int gpad_setup_classes(gpad_handle_t h, const gpad_dims_t* dims, int K, const int* class_of,
+                                  const void* ML, const void* G, double L) {
+    return gpad::abi_guard("gpad_setup_classes", [&]() -> int {
+        if (!h) return fail(GPAD_ERR_INVALID, "gpad_setup_classes: null handle");
+        HIP_TRY(hipSetDevice(h->device));
+        gpad::ClassBinding* cb = nullptr;
+        const int rc = gpad::classes_setup(&cb, h->device, h->stream, h->tune, dims, K, class_of, ML, G, L);
+        if (rc) return rc;  // (the handle keeps what it had)
+        end_classes(h);
+        // the handle's own problem, plant and signals are unbound: the binding serves every run from here on
+        h->ready = false;
+        h->flat = false;
+        h->hess_ok = false;
+        h->shadow_ok = false;
+        h->plant_ready = false;
+        h->ns = 0;
+        h->plan.nph = 0;
+        h->plan_pending = false;
+        h->last_phased = false;
+        h->last_batch = 0;
+        h->cls = cb;
+        return GPAD_OK;
+    });
+}
+
+extern "C" int gpad_setup_plant_classes(gpad_handle_t h, int nx, int nu, const void* PM, const void* M0,
+                                        const void* Pg, const void* g0, const void* A, const void* B) {
+    return gpad::abi_guard("gpad_setup_plant_classes", [&]() -> int {
+        if (!h) return fail(GPAD_ERR_INVALID, "gpad_setup_plant_classes: null handle");
+        if (!h->cls) return fail(GPAD_ERR_NOT_SETUP, "gpad_setup_plant_classes: call gpad_setup_classes first");
+        HIP_TRY(hipSetDevice(h->device));
+        return gpad::classes_setup_plant(h->cls, true, nx, nu, PM, M0, Pg, g0, A, B);
+    });
+}
+
 static bool plant_bound(gpad_handle_t h) {
     return h->plant_ready && h->plant_n == h->dims.n && h->plant_m == h->dims.m && h->plant_dtype == h->dims.dtype &&
            !(h->plant_batch && h->plant_batch != h->dims.batch);
@@ -1477,6 +1573,7 @@ static int setup_signals_typed(gpad_handle_t h, int ns, const T* SM, const T* Sg
 extern "C" int gpad_setup_signals(gpad_handle_t h, int ns, const void* SM, const void* Sg, const void* E) {
     return gpad::abi_guard("gpad_setup_signals", [&]() -> int {
         if (!h) return fail(GPAD_ERR_INVALID, "gpad_setup_signals: null handle");
+        if (h->cls) return no_classes("gpad_setup_signals");
         if (!h->ready || !plant_bound(h))
             return fail(GPAD_ERR_NOT_SETUP, "gpad_setup_signals: call gpad_setup_plant first");
         if (ns < 0) return fail(GPAD_ERR_INVALID, "gpad_setup_signals: ns < 0");
@@ -1697,6 +1794,11 @@ static int state_typed(gpad_handle_t h, T* x, T* z, T* y, const T* sg, int steps
 static int state_impl(gpad_handle_t h, void* x, void* z, void* y, const void* sg, bool with_sig, int steps, int N,
                       double tol, int warm, void* xs, void* us, gpad_stats_t* st, const char* where) {
     if (!h) return fail(GPAD_ERR_INVALID, std::string(where) + ": null handle");
+    if (h->cls) {
+        if (with_sig) return no_classes(where);
+        HIP_TRY(hipSetDevice(h->device));
+        return gpad::classes_state(h->cls, x, z, y, steps, N, tol, warm, xs, us, st);
+    }
     if (!h->ready) return fail(GPAD_ERR_NOT_SETUP, std::string(where) + ": call gpad_setup first");
     if (!plant_bound(h))
         return fail(GPAD_ERR_NOT_SETUP, std::string(where) + ": call gpad_setup_plant after gpad_setup");

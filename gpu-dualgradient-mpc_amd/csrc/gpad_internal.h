@@ -12,6 +12,11 @@ namespace gpad {
 // gpad_last_error() detail for the calling thread; returns code (gpad_host.cpp)
 int set_last_error(int code, const std::string& msg);
 
+// The class binding of a handle (gpad_setup_classes): per-class child handles, the class-sorted order
+// and its workspaces.  Opaque to gpad_host.cpp, whose gpad_handle_s holds the pointer and whose entry
+// points branch to gpad_classes.h's functions at their top; defined in gpad_classes.cpp.
+struct ClassBinding;
+
 // Schedule / launch tuning of a handle (gpad_set_option, include/gpad.h GPAD_OPT_*): for tests,
 // diagnostics and A/B tools.  None of these changes results -- only launch boundaries, grid
 // sizes, work-queue order and where operands are staged.

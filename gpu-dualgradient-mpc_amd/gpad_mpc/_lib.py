@@ -44,6 +44,7 @@ EXPORTS = [
     "gpad_setup_hessian", "gpad_release_cached", "gpad_phase_counts", "gpad_last_phases",
     "gpad_group_rccl_library",
     "gpad_setup_signals", "gpad_run_state_signals", "gpad_closed_loop_signals",
+    "gpad_class_order", "gpad_setup_classes", "gpad_setup_plant_classes",
 ]
 GROUP_RCCL, GROUP_PEER = 1, 2
 
@@ -191,6 +192,12 @@ def load(path: str | None = None) -> C.CDLL:
         L.gpad_run_state_signals.argtypes = [vp, cvp, cvp, vp, vp, i, d, C.POINTER(Stats)]
         L.gpad_closed_loop_signals.argtypes = [vp, vp, vp, vp, cvp, i, i, d, i, vp, vp, C.POINTER(Stats)]
         for name in ("gpad_setup_signals", "gpad_run_state_signals", "gpad_closed_loop_signals"):
+            getattr(L, name).restype = i
+    if hasattr(L, "gpad_setup_classes"):  # (added within 0.6; absent from older builds under GPAD_LIB_TOLERANT)
+        L.gpad_class_order.argtypes = [C.POINTER(i), i, i, C.POINTER(i), C.POINTER(i)]
+        L.gpad_setup_classes.argtypes = [vp, C.POINTER(Dims), i, C.POINTER(i), cvp, cvp, d]
+        L.gpad_setup_plant_classes.argtypes = [vp, i, i, cvp, cvp, cvp, cvp, cvp, cvp]
+        for name in ("gpad_class_order", "gpad_setup_classes", "gpad_setup_plant_classes"):
             getattr(L, name).restype = i
     L.gpad_datafile_read.argtypes = [C.c_char_p, i, C.POINTER(DataFile)]
     L.gpad_datafile_write.argtypes = [C.c_char_p, i, C.POINTER(DataFile)]

@@ -246,6 +246,24 @@ def battery_fleet(n_u: int, N: int, caps, **limits):
     return qp, plant
 
 
+def expand_classes(qp: QP, plant: Plant, class_of):
+    """The per-instance stacks of the ``shared=False`` binding from per-class stacks: ``qp`` / ``plant``
+    stacked over K classes (as ``battery_fleet(n_u, N, class_caps)`` returns them) and ``class_of``
+    [batch] ints in 0..K-1 -> (QP, Plant) stacked over the batch, instance b holding the arrays of class
+    class_of[b].  L is the same scalar.  This is the fleet a class binding (``setup_classes``) equals
+    bit for bit."""
+    co = np.asarray(class_of).reshape(-1)
+    K = qp.ML.shape[0]
+    if co.size == 0 or co.min() < 0 or co.max() >= K:
+        raise ValueError(f"class_of must hold ids in 0..{K - 1}")
+    take = lambda a: None if a is None else np.ascontiguousarray(np.asarray(a)[co])  # noqa: E731
+    eq = QP(ML=take(qp.ML), M=take(qp.M), G=take(qp.G), g=take(qp.g), L=qp.L, H=take(qp.H), q=take(qp.q),
+            meta=dict(qp.meta or {}, classes=K, class_of=co.copy()))
+    ep = Plant(PM=take(plant.PM), Pg=take(plant.Pg), A=take(plant.A), B=take(plant.B), M0=take(plant.M0),
+               g0=take(plant.g0), SM=take(plant.SM), Sg=take(plant.Sg), E=take(plant.E))
+    return eq, ep
+
+
 def flatten_battery(qp: QP, n_u: int, N: int, L: float | None = None):
     """The reference's "flat" battery data (ENABLE_FLATTEN_MATRICES; seq_functions.cpp:5-43) from
     the full problem, valid for equal cell capacities: with H = kron(Hs, I_{n_u}), column k of

@@ -67,6 +67,7 @@ class GpadSolver:
         check(self.lib.gpad_create(C.byref(self.h), device, C.c_void_p(stream or 0)), "gpad_create")
         self._device = device
         self.dims = None
+        self._classes = 0  # K of a class binding (setup_classes), 0: none
 
     def last_phases(self) -> dict:
         """The phases the last phased panel solve launched (include/gpad.h gpad_last_phases): ends,
@@ -137,6 +138,36 @@ class GpadSolver:
                          tol_gap=float(tol_gap))
         fn = self.lib.gpad_setup_scaled if scaled else self.lib.gpad_setup
         check(fn(self.h, C.byref(self.dims), _ptr(ML), _ptr(G), float(L)), "gpad_setup")
+        self._classes = 0
+
+    def setup_classes(self, ML, G, L: float, class_of, *, n: int, m: int, batch: int | None = None,
+                      schedule: int = _lib.SCHEDULE_MATLAB, check_every: int = 10,
+                      kernel: int = _lib.KERNEL_AUTO, tol_gap: float = 0.0) -> None:
+        """Bind a fleet of K plant classes (gpad_setup_classes): ML (K, n, m), G (K, m, n), one L, and
+        ``class_of`` [batch] host ints in 0..K-1 (``batch`` defaults to its length).  Packs of one class
+        are solved together as a shared-matrix sub-batch, each class on the engine its own size picks;
+        every array of ``run`` / ``run_state`` / ``closed_loop`` stays in the caller's instance order and
+        the results are bit for bit those of ``setup(..., shared=False)`` on the expanded fleet
+        (``problems.expand_classes``).  A stacked ``setup_plant`` then takes one copy of every map per
+        class.  A later ``setup`` / ``setup_flat`` ends the binding."""
+        if ML.ndim != 3 or G.ndim != 3 or G.shape[0] != ML.shape[0]:
+            raise ValueError("setup_classes: ML must be (K, n, m) and G (K, m, n)")
+        co = np.ascontiguousarray(np.asarray(class_of).reshape(-1), np.int32)
+        if batch is None:
+            batch = co.size
+        if co.size != batch:
+            raise ValueError(f"setup_classes: class_of has {co.size} entries, batch is {batch}")
+        mem = _lib.MEM_DEVICE if _is_torch(ML) else _lib.MEM_HOST
+        if _is_torch(ML) and not ML.is_cuda:
+            raise ValueError("torch inputs must live on the GPU (use numpy for host memory)")
+        dims = Dims(n=n, m=m, batch=batch, shared=1, dtype=_dtype_code(ML), memory=mem, schedule=schedule,
+                    check_every=check_every, kernel=kernel, tol_gap=float(tol_gap))
+        self._classes = 0
+        check(self.lib.gpad_setup_classes(self.h, C.byref(dims), int(ML.shape[0]),
+                                          co.ctypes.data_as(C.POINTER(C.c_int)), _ptr(ML), _ptr(G), float(L)),
+              "gpad_setup_classes")
+        self.dims = dims
+        self._classes = int(ML.shape[0])
 
     def setup_flat(self, MGf, GLf, L: float, *, n_u: int, batch: int = 1,
                    schedule: int = _lib.SCHEDULE_MATLAB, check_every: int = 10,
@@ -151,6 +182,7 @@ class GpadSolver:
                          schedule=schedule, check_every=check_every, kernel=kernel, tol_gap=float(tol_gap))
         check(self.lib.gpad_setup_flat(self.h, C.byref(self.dims), int(n_u), _ptr(MGf), _ptr(GLf),
                                        float(L)), "gpad_setup_flat")
+        self._classes = 0
 
     def setup_hessian(self, H) -> None:
         """gpad_setup_hessian: bind the QP Hessian (same dtype / memory kind as ``setup``) so
@@ -292,12 +324,17 @@ class GpadSolver:
         A stacked PM (batch, n, nx) binds per-instance maps (gpad_setup_plant_batch): every array
         given must then carry the leading batch axis.  That serves a fleet of distinct plants
         (``setup(..., shared=False)``) and one controller against per-instance true plants
-        (``shared=True``) alike."""
+        (``shared=True``) alike.
+
+        After ``setup_classes`` a stacked PM leads with K instead, one copy of every map given per class
+        (gpad_setup_plant_classes), and a 2-d PM binds the same maps for every class."""
         stacked = PM.ndim == 3
         arrays = dict(PM=PM, Pg=Pg, M0=M0, g0=g0, A=A, B=B)
         if stacked:
             batch = PM.shape[0]
-            if self.dims is not None and batch != self.dims.batch:
+            if self._classes and batch != self._classes:
+                raise ValueError(f"setup_plant: PM is stacked for {batch} classes, setup_classes bound {self._classes}")
+            if not self._classes and self.dims is not None and batch != self.dims.batch:
                 raise ValueError(f"setup_plant: PM is stacked for {batch} instances, the setup has {self.dims.batch}")
             for name, a in arrays.items():
                 want = 2 if name in ("M0", "g0") else 3
@@ -307,7 +344,8 @@ class GpadSolver:
         nx = PM.shape[-1]
         nu = 0 if B is None else B.shape[-1]
         opt = lambda a: _ptr(a) if a is not None else None  # noqa: E731
-        fn = "gpad_setup_plant_batch" if stacked else "gpad_setup_plant"
+        fn = "gpad_setup_plant" if not stacked else ("gpad_setup_plant_classes" if self._classes
+                                                     else "gpad_setup_plant_batch")
         check(getattr(self.lib, fn)(self.h, nx, nu, _ptr(PM), opt(M0), _ptr(Pg), opt(g0), opt(A), opt(B)), fn)
 
     def setup_signals(self, SM=None, Sg=None, E=None, *, ns: int | None = None) -> None:

@@ -34,7 +34,8 @@ extern "C" {
                               * 0.6: gpad_setup_plant_batch added; layouts as in 0.3.  Added since
                               * without a new minor (no layout or behaviour of 0.6 changes):
                               * gpad_setup_signals, gpad_run_state_signals, gpad_closed_loop_signals;
-                              * GPAD_OPT_LOOP_PANEL (option 23) and the reported GPAD_KERNEL_LOOP_PANEL (7) */
+                              * GPAD_OPT_LOOP_PANEL (option 23) and the reported GPAD_KERNEL_LOOP_PANEL (7);
+                              * gpad_class_order, gpad_setup_classes, gpad_setup_plant_classes */
 
 /* status codes */
 #define GPAD_OK 0
@@ -329,6 +330,57 @@ int gpad_run_state_signals(gpad_handle_t h, const void* x, const void* s, void* 
                            gpad_stats_t* st);
 int gpad_closed_loop_signals(gpad_handle_t h, void* x, void* z, void* y, const void* S, int steps, int N,
                              double tol, int warm, void* xs, void* us, gpad_stats_t* st);
+
+/* ---- fleets of a few plant classes: per-class matrices on the shared-matrix engines ----------------
+ * A fleet of 8192 packs rarely has 8192 distinct plants: it has a handful of types (SKUs, capacity
+ * bins, ageing bins).  Bound with dims.shared = 0 such a fleet carries a matrix pair per pack and runs
+ * the kernels for distinct matrices (no MFMA panels); a class binding carries K pairs and solves the
+ * packs of one class together as a shared-matrix sub-batch, so every class runs on the engines of
+ * dims.shared = 1 -- panel pairs, phased compaction, finisher, the one-launch loops -- each class
+ * picking its own engine for its own size.  Results are bit for bit those of the dims.shared = 0 binding
+ * of the same fleet (ML, G of instance b = those of class class_of[b]; gpad_setup_plant_batch with the
+ * maps of class class_of[b]).
+ *
+ * On a class-bound handle
+ *   - gpad_run, gpad_run_state, gpad_closed_loop, gpad_last_stats, gpad_accumulate_iterations, gpad_sync,
+ *     gpad_set_stream and gpad_set_option work unchanged for the caller, whose arrays stay in the
+ *     caller's instance order (the library permutes rows to and from a class-sorted workspace on the
+ *     device).  gpad_set_stream and gpad_set_option are forwarded to every class, GPAD_OPT_LOOP_ASYNC
+ *     and GPAD_OPT_LOOP_PANEL included, which each class then applies by its own rules (a class that
+ *     does not qualify runs the lockstep loop).  The plain gpad_setup_plant binds the same maps for
+ *     every class.
+ *   - gpad_setup_hessian, gpad_setup_plant_batch, gpad_setup_signals (and the _signals runs) and
+ *     gpad_run_scaled return GPAD_ERR_UNSUPPORTED, gpad_last_error naming the class binding.
+ *   - the phase diagnostics (gpad_phase_plan, gpad_phase_counts, gpad_last_phases) return 0.
+ *   - a later gpad_setup, gpad_setup_scaled or gpad_setup_flat ends the binding and frees everything
+ *     it held; a later gpad_setup_classes replaces it.
+ * Stats: iterations = max over the classes, converged and total_iterations = sums, tol_floor = max,
+ * flags OR-ed, iters / codes [steps][batch] in the caller's order, kernel = the kernel of the class
+ * with the most instances (ties: the lowest class), kernel_ms = events on the handle's stream around the
+ * whole call, row permutations included.  A GPAD_ERR_DEVICE of any class is returned, and stays sticky
+ * as on any handle.
+ * The classes run one after the other on the handle's stream (a loop: class 0's `steps` steps, then
+ * class 1's); they are independent, so the order changes no result.  Not provided: classes running
+ * concurrently on several streams, signals, per-pack true plants under a class binding, Hessian
+ * branches. */
+
+/* host only, no device work (for tests/tools, like gpad_plan_phases): the class-sorted order.
+ * perm[batch]: sorted position -> instance, classes ascending, instances ascending inside a class
+ * (stable); offsets[K + 1]: class k occupies positions offsets[k] .. offsets[k+1]-1.
+ * GPAD_ERR_INVALID: NULL, batch < 1, K < 1, an id outside 0..K-1. */
+int gpad_class_order(const int* class_of, int batch, int K, int* perm, int* offsets);
+
+/* gpad_setup for a fleet of K plant classes: ML [K][n][m], G [K][m][n] (dims.dtype / dims.memory),
+ * class_of [batch] HOST ints in 0..K-1 (as theta/beta: host whatever dims.memory says), one L.
+ * dims.shared must be 1 (matrices are shared inside a class); 1 <= K <= dims.batch; a class may be empty. */
+int gpad_setup_classes(gpad_handle_t h, const gpad_dims_t* dims, int K, const int* class_of,
+                       const void* ML, const void* G, double L);
+
+/* gpad_setup_plant with one copy of every non-NULL map per class: PM [K][n][nx], M0 [K][n], Pg [K][m][nx],
+ * g0 [K][m], A [K][nx][nx], B [K][nx][nu]; instance b uses copy class_of[b].  GPAD_ERR_NOT_SETUP unless
+ * the handle is class-bound. */
+int gpad_setup_plant_classes(gpad_handle_t h, int nx, int nu, const void* PM, const void* M0,
+                             const void* Pg, const void* g0, const void* A, const void* B);
 
 /* ---- reference data-file boundary (main.cu:29-67 readData) ------------------------------
  * Text file: "n_u N m num_iterations L", then M_G (n*m), g_P (n), G_L (n*m), p_D (m),

@@ -5,6 +5,7 @@ modes: eps cold / eps warm (tol 1e-4, N 3000) and fixed N = 100.
 
   python tools/loop_ab.py [--rounds 3] [--steps 20] [--batches 1 64 256 512 2048 8192] [--fleet | --signals]
                           [--panel]
+  python tools/loop_ab.py --classes K [--rounds 3] [--steps 20] [--batches 256 2048 8192]
 
 --panel: a third variant, "panel" (GPAD_OPT_LOOP_PANEL, csrc/gpad_loop_panel.hip: the one-launch loop on the
 MFMA panels), alternated with lockstep and async in the same process and checked against lockstep like
@@ -25,6 +26,16 @@ problems.battery_plant_signals(4, 10) (gpad_setup_signals: s = [i_load, r_1 .. r
 references U(-0.1, 0.1) per step and pack, seeded by the batch), each checked against the other; the
 plain variants run unchanged beside them, and `sig_over_plain` is the rate with signals over the rate
 without, per loop kind (informational: the signals change the QPs, so also the iteration counts).
+
+--classes K: a fleet of K plant classes (problems.battery_fleet(4, 10, battery_fleet_caps(K, 4, seed = K)),
+class_of[b] = b % K; default batches 256 2048 8192).  Variant "fleet" is the dims.shared = 0 binding of the
+expanded fleet (problems.expand_classes; setup(shared=False) + a stacked setup_plant, lockstep) -- the path
+a fleet of classes had to take before the class binding; "classes" is the class binding
+(setup_classes, csrc/gpad_classes.cpp) with the options off, "classes_panel" and "classes_async" the
+same with loop_panel = 1 and loop_async = 1.  With K = 1 a fifth variant, "shared", is the plain
+shared-matrix handle (lockstep): `classes_over_shared` is then the price of the row permutations and
+the child handle.  Every variant's outputs are compared with "fleet" bit for bit first; each line has
+the rates, `<variant>_over_fleet` and `<variant>_faster` ("none" inside the spread of the rounds).
 
 Per batch and mode the two variants' x, z, y, xs, us and per-step iteration counts are compared first
 (that run is also each variant's warm-up); a mismatch aborts the batch.  Then `rounds` rounds
@@ -50,6 +61,101 @@ MODES = {"eps_cold": dict(N=3000, tol=1e-4, warm=False), "eps_warm": dict(N=3000
          "fixed_100": dict(N=100, tol=0.0, warm=False)}
 
 
+def classes_ab(args):
+    """--classes K: the shared = 0 fleet against the class binding (module docstring)."""
+    import torch
+
+    import gpad_mpc
+    from gpad_mpc import problems
+    K, steps, rounds = args.classes, args.steps, max(3, args.rounds)
+    dev = torch.device("cuda:0")
+    qp, pl = problems.battery_fleet(4, 10, problems.battery_fleet_caps(K, 4, K))
+    n, m, nx, nu = qp.n, qp.m, pl.nx, pl.nu
+    L = float(np.float32(qp.L))
+    t32 = lambda a: torch.from_numpy(np.ascontiguousarray(np.asarray(a, np.float64).astype(np.float32))).to(dev)  # noqa: E731
+    cls = {k: t32(a) for k, a in dict(ML=qp.ML, G=qp.G, PM=pl.PM, Pg=pl.Pg, g0=pl.g0, A=pl.A, B=pl.B).items()}
+    print(json.dumps({"plant": f"battery_fleet(4, 10), {K} classes, class_of[b] = b % {K}", "n": n, "m": m,
+                      "steps": steps, "rounds": rounds, "device": torch.cuda.get_device_name(0),
+                      "cus": torch.cuda.get_device_properties(0).multi_processor_count}))
+    names = ("fleet", "classes", "classes_panel", "classes_async") + (("shared",) if K == 1 else ())
+    want = {"classes_panel": "loop_panel", "classes_async": "loop"}
+    for B in args.batches:
+        class_of = np.arange(B, dtype=np.int32) % K
+        X0 = torch.from_numpy((np.random.default_rng(B).random((B, nx)) - 0.5).astype(np.float32)).to(dev)
+        idx = torch.from_numpy(class_of.astype(np.int64)).to(dev)
+        var = {}
+        for name in names:
+            s = gpad_mpc.GpadSolver(0)
+            if name == "fleet":  # expand_classes on the device: instance b holds the arrays of class b % K
+                f = {k: a[idx].contiguous() for k, a in cls.items()}
+                s.setup(f["ML"], f["G"], L, n=n, m=m, batch=B, shared=False)
+                s.setup_plant(f["PM"], f["Pg"], g0=f["g0"], A=f["A"], B=f["B"])
+                del f
+            elif name == "shared":
+                s.setup(cls["ML"][0], cls["G"][0], L, n=n, m=m, batch=B, shared=True)
+                s.setup_plant(cls["PM"][0], cls["Pg"][0], g0=cls["g0"][0], A=cls["A"][0], B=cls["B"][0])
+            else:
+                s.setup_classes(cls["ML"], cls["G"], L, class_of, n=n, m=m)
+                s.setup_plant(cls["PM"], cls["Pg"], g0=cls["g0"], A=cls["A"], B=cls["B"])
+                s.set_options(loop_panel=int(name == "classes_panel"), loop_async=int(name == "classes_async"))
+            buf = dict(x=torch.empty(B, nx, device=dev), z=torch.empty(B, n, device=dev),
+                       y=torch.empty(B, m, device=dev), xs=torch.empty(steps, B, nx, device=dev),
+                       us=torch.empty(steps, B, nu, device=dev))
+            var[name] = (s, buf)
+
+        def enqueue(name, mode, **kw):
+            s, b = var[name]
+            b["x"].copy_(X0)
+            b["z"].zero_()
+            b["y"].zero_()
+            torch.cuda.synchronize()
+            return s.closed_loop(b["x"], b["z"], b["y"], steps, mode["N"], mode["tol"], warm=mode["warm"],
+                                 xs=b["xs"], us=b["us"], **kw)
+
+        for mname, mode in MODES.items():
+            its, kern = {}, {}
+            for name in var:  # the output check, and each variant's warm-up
+                its[name] = np.zeros(steps * B, np.int32)
+                kern[name] = enqueue(name, mode, iters=its[name])["kernel"]
+            bad = [f"{v}.{k}" for k in ("x", "z", "y", "xs", "us") for v in var if v != "fleet"
+                   if not torch.equal(var["fleet"][1][k].view(torch.int32), var[v][1][k].view(torch.int32))]
+            bad += [f"{v}.iters" for v in var if not np.array_equal(its["fleet"], its[v])]
+            if bad or any(kern[v] is None or (kern[v] in ("loop", "loop_panel")) != (v in want) or
+                          (v in want and kern[v] != want[v]) for v in var):
+                print(json.dumps({"batch": B, "mode": mname, "error": "outputs differ" if bad else "wrong kernel",
+                                  "differ": bad, "kernels": kern}))
+                break
+            ms = {k: [] for k in var}
+            wall = {k: [] for k in var}
+            for _ in range(rounds):
+                for name in var:
+                    s = var[name][0]
+                    t0 = time.perf_counter()
+                    enqueue(name, mode, stats=False)
+                    s.sync()
+                    wall[name].append((time.perf_counter() - t0) * 1e3)
+                    ms[name].append(s.last_stats()["kernel_ms"])
+            med = {k: float(np.median(v)) for k, v in ms.items()}
+            rate = {k: B * steps / (med[k] / 1e3) for k in var}
+            faster = lambda v, ref: (v if max(ms[v]) < min(ms[ref]) else  # noqa: E731
+                                     ref if min(ms[v]) > max(ms[ref]) else "none")
+            print(json.dumps({
+                "batch": B, "classes": K, "mode": mname, "kernels": kern,
+                "mean_iters_per_solve": round(float(its["fleet"].mean()), 1),
+                "max_iters_per_solve": int(its["fleet"].max()),
+                "kernel_ms": {k: [round(x, 4) for x in v] for k, v in ms.items()},
+                "wall_ms": {k: [round(x, 4) for x in v] for k, v in wall.items()},
+                "median_ms": {k: round(v, 4) for k, v in med.items()},
+                "mpc_steps_per_s": {k: round(v, 1) for k, v in rate.items()},
+                **{f"{v}_over_fleet": round(rate[v] / rate["fleet"], 3) for v in var if v != "fleet"},
+                **{f"{v}_faster": faster(v, "fleet") for v in var if v not in ("fleet", "shared")},
+                **({"classes_over_shared": round(rate["classes"] / rate["shared"], 3),
+                    "classes_vs_shared_faster": faster("classes", "shared")} if "shared" in var else {})}),
+                flush=True)
+        for s, _ in var.values():
+            s.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=3)
@@ -58,7 +164,14 @@ def main():
     ap.add_argument("--fleet", action="store_true")
     ap.add_argument("--signals", action="store_true")
     ap.add_argument("--panel", action="store_true")
+    ap.add_argument("--classes", type=int, default=0, metavar="K")
     args = ap.parse_args()
+    if args.classes:
+        if args.fleet or args.signals or args.panel or args.classes < 1:
+            ap.error("--classes K >= 1 stands alone")
+        if args.batches is None:
+            args.batches = [256, 2048, 8192]
+        return classes_ab(args)
     if args.fleet and args.signals:
         ap.error("--fleet and --signals exclude each other")
     if args.batches is None:
