@@ -24,57 +24,10 @@
 //
 // Not in this file: classes running concurrently on several streams (each class pays its own tail per
 // call), exogenous signals, per-pack true plants under a class binding, Hessian branches.
-#include <hip/hip_runtime.h>
-
 #include <algorithm>
 #include <cmath>
-#include <string>
-#include <vector>
 
-#include "../../include/gpad.h"
-#include "gpad_abi.h"
-#include "gpad_classes.h"
-#include "gpad_internal.h"
-
-namespace {
-
-int cfail(int code, const std::string& msg) { return gpad::set_last_error(code, msg); }
-
-#define C_HIP(expr)                                                                                   \
-    do {                                                                                              \
-        hipError_t _e = (expr);                                                                       \
-        if (_e != hipSuccess)                                                                         \
-            return cfail(_e == hipErrorOutOfMemory ? GPAD_ERR_NOMEM : GPAD_ERR_HIP,                   \
-                         std::string(#expr) + ": " + hipGetErrorName(_e) + " (code " +                \
-                             std::to_string((int)_e) + "): " + hipGetErrorString(_e));                \
-    } while (0)
-
-size_t esz(int dtype) { return dtype == GPAD_DTYPE_F64 ? sizeof(double) : sizeof(float); }
-
-struct Buf {
-    void* p = nullptr;
-    size_t bytes = 0;
-    int ensure(size_t want) {
-        if (want <= bytes && p) return GPAD_OK;
-        release();
-        if (want == 0) return GPAD_OK;
-        const hipError_t e = hipMalloc(&p, want);
-        if (e != hipSuccess) {
-            p = nullptr;
-            return cfail(e == hipErrorOutOfMemory ? GPAD_ERR_NOMEM : GPAD_ERR_HIP,
-                         "class binding: hipMalloc(" + std::to_string(want) + " bytes): " + hipGetErrorString(e));
-        }
-        bytes = want;
-        return GPAD_OK;
-    }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        bytes = 0;
-    }
-};
-
-}  // namespace
+#include "gpad_host.h"
 
 namespace gpad {
 
@@ -86,8 +39,8 @@ struct ClassBinding {
     std::vector<int> perm, offsets;   // class_order
     std::vector<gpad_handle_t> child; // [K]; null for an empty class
     int major = 0;                    // the class with the most instances (ties: the lowest): stats kernel
-    Buf idx;                          // device: perm[batch] | pos_off[batch] | pos_cnt[batch]
-    Buf sorted, stage;                // class-sorted workspace; host callers' staging in caller order
+    DevBuf idx;                          // device: perm[batch] | pos_off[batch] | pos_cnt[batch]
+    DevBuf sorted, stage;                // class-sorted workspace; host callers' staging in caller order
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     bool timed = false;
     bool plant = false, plant_dyn = false;
@@ -129,24 +82,9 @@ void classes_free(ClassBinding* cb) {
 // the parent's options on a new child (gpad_set_option calls made before the binding)
 static int apply_tuning(gpad_handle_t c, const Tuning& t) {
     const Tuning def{};
-    const int opts[][2] = {{GPAD_OPT_PHASE_LEN, t.phase_len},
-                           {GPAD_OPT_FINISH_THRESH, t.finish_thresh == def.finish_thresh ? GPAD_OPT_DEFAULT : t.finish_thresh},
-                           {GPAD_OPT_PLAN, t.plan},
-                           {GPAD_OPT_PHASED, t.phased},
-                           {GPAD_OPT_LPT, t.lpt},
-                           {GPAD_OPT_PANEL_MAX_GRID, t.panel_max_grid},
-                           {GPAD_OPT_DUO_MAX_GRID, t.duo_max_grid},
-                           {GPAD_OPT_FLAT_PANEL_MIN, t.flat_panel_min == def.flat_panel_min ? GPAD_OPT_DEFAULT : t.flat_panel_min},
-                           {GPAD_OPT_FLAT_PANELS, t.flat_panels},
-                           {GPAD_OPT_FLAT_WAVES, t.flat_waves},
-                           {GPAD_OPT_FLAT_A_LDS, t.flat_a_lds},
-                           {GPAD_OPT_DEBUG_DROP_HANDOFF, t.debug_drop_handoff},
-                           {GPAD_OPT_P64_RELAY, 1 - t.p64_no_relay},
-                           {GPAD_OPT_P64_REFILL, 1 - t.p64_no_refill},
-                           {GPAD_OPT_LOOP_ASYNC, t.loop_async},
-                           {GPAD_OPT_LOOP_PANEL, t.loop_panel}};
-    for (const auto& o : opts) {
-        const int rc = gpad_set_option(c, o[0], o[1]);
+    for (const OptionSpec& o : kOptions) {  // (a member at its default goes as GPAD_OPT_DEFAULT: -1 is no value)
+        const int v = t.*o.field;
+        const int rc = gpad_set_option(c, o.id, v == def.*o.field ? GPAD_OPT_DEFAULT : o.inverted ? 1 - v : v);
         if (rc) return rc;
     }
     return GPAD_OK;
@@ -155,8 +93,8 @@ static int apply_tuning(gpad_handle_t c, const Tuning& t) {
 static int setup_body(ClassBinding* cb, const Tuning& tune, const void* ML, const void* G, double L) {
     const gpad_dims_t& d = cb->dims;
     const int batch = d.batch, K = cb->K;
-    C_HIP(hipEventCreate(&cb->ev0));
-    C_HIP(hipEventCreate(&cb->ev1));
+    HIP_TRY(hipEventCreate(&cb->ev0));
+    HIP_TRY(hipEventCreate(&cb->ev1));
     // perm | pos_off | pos_cnt on the device
     std::vector<int> host_idx(3 * (size_t)batch);
     cb->major = 0;
@@ -170,13 +108,13 @@ static int setup_body(ClassBinding* cb, const Tuning& tune, const void* ML, cons
     std::copy(cb->perm.begin(), cb->perm.end(), host_idx.begin());
     int rc = cb->idx.ensure(sizeof(int) * host_idx.size());
     if (rc) return rc;
-    C_HIP(hipMemcpyAsync(cb->idx.p, host_idx.data(), sizeof(int) * host_idx.size(), hipMemcpyHostToDevice, cb->stream));
-    C_HIP(hipStreamSynchronize(cb->stream));
+    HIP_TRY(hipMemcpyAsync(cb->idx.p, host_idx.data(), sizeof(int) * host_idx.size(), hipMemcpyHostToDevice, cb->stream));
+    HIP_TRY(hipStreamSynchronize(cb->stream));
     // the K matrix pairs on the device: the children are GPAD_MEM_DEVICE handles
-    const size_t mat = (size_t)d.n * d.m * esz(d.dtype);
+    const size_t mat = (size_t)d.n * d.m * esize(d.dtype);
     const char* dML = (const char*)ML;
     const char* dG = (const char*)G;
-    Buf up;
+    DevBuf up;
     if (d.memory == GPAD_MEM_HOST) {
         if ((rc = up.ensure(2 * mat * K))) return rc;
         hipError_t e = hipMemcpyAsync(up.p, ML, mat * K, hipMemcpyHostToDevice, cb->stream);
@@ -184,7 +122,7 @@ static int setup_body(ClassBinding* cb, const Tuning& tune, const void* ML, cons
         if (e == hipSuccess) e = hipStreamSynchronize(cb->stream);
         if (e != hipSuccess) {
             up.release();
-            return cfail(GPAD_ERR_HIP, std::string("gpad_setup_classes: matrix upload: ") + hipGetErrorString(e));
+            return fail(GPAD_ERR_HIP, std::string("gpad_setup_classes: matrix upload: ") + hipGetErrorString(e));
         }
         dML = (const char*)up.p;
         dG = dML + mat * K;
@@ -207,18 +145,18 @@ static int setup_body(ClassBinding* cb, const Tuning& tune, const void* ML, cons
 int classes_setup(ClassBinding** out, int device, hipStream_t stream, const Tuning& tune, const gpad_dims_t* dims,
                   int K, const int* class_of, const void* ML, const void* G, double L) {
     *out = nullptr;
-    if (!dims) return cfail(GPAD_ERR_INVALID, "gpad_setup_classes: null dims");
+    if (!dims) return fail(GPAD_ERR_INVALID, "gpad_setup_classes: null dims");
     if (dims->n <= 0 || dims->m <= 0 || dims->batch <= 0)
-        return cfail(GPAD_ERR_INVALID, "gpad_setup_classes: dims: n, m, batch must be positive");
+        return fail(GPAD_ERR_INVALID, "gpad_setup_classes: dims: n, m, batch must be positive");
     if (dims->shared != 1)
-        return cfail(GPAD_ERR_INVALID, "gpad_setup_classes: dims.shared must be 1 (matrices are shared inside a class)");
+        return fail(GPAD_ERR_INVALID, "gpad_setup_classes: dims.shared must be 1 (matrices are shared inside a class)");
     if (dims->dtype != GPAD_DTYPE_F32 && dims->dtype != GPAD_DTYPE_F64)
-        return cfail(GPAD_ERR_INVALID, "gpad_setup_classes: dims: bad dtype");
+        return fail(GPAD_ERR_INVALID, "gpad_setup_classes: dims: bad dtype");
     if (dims->memory != GPAD_MEM_HOST && dims->memory != GPAD_MEM_DEVICE)
-        return cfail(GPAD_ERR_INVALID, "gpad_setup_classes: dims: bad memory kind");
-    if (K < 1 || K > dims->batch) return cfail(GPAD_ERR_INVALID, "gpad_setup_classes: need 1 <= K <= dims.batch");
-    if (!class_of || !ML || !G) return cfail(GPAD_ERR_INVALID, "gpad_setup_classes: null argument");
-    if (!(L > 0.0) || !std::isfinite(L)) return cfail(GPAD_ERR_INVALID, "gpad_setup_classes: L must be > 0");
+        return fail(GPAD_ERR_INVALID, "gpad_setup_classes: dims: bad memory kind");
+    if (K < 1 || K > dims->batch) return fail(GPAD_ERR_INVALID, "gpad_setup_classes: need 1 <= K <= dims.batch");
+    if (!class_of || !ML || !G) return fail(GPAD_ERR_INVALID, "gpad_setup_classes: null argument");
+    if (!(L > 0.0) || !std::isfinite(L)) return fail(GPAD_ERR_INVALID, "gpad_setup_classes: L must be > 0");
     ClassBinding* cb = new ClassBinding();
     cb->device = device;
     cb->stream = stream;
@@ -228,7 +166,7 @@ int classes_setup(ClassBinding** out, int device, hipStream_t stream, const Tuni
     cb->offsets.resize((size_t)K + 1);
     if (!class_order(class_of, dims->batch, K, cb->perm.data(), cb->offsets.data())) {
         classes_free(cb);
-        return cfail(GPAD_ERR_INVALID, "gpad_setup_classes: class_of holds an id outside 0..K-1");
+        return fail(GPAD_ERR_INVALID, "gpad_setup_classes: class_of holds an id outside 0..K-1");
     }
     const int rc = setup_body(cb, tune, ML, G, L);  // (the rest of dims is validated by the children's gpad_setup)
     if (rc) {
@@ -261,17 +199,17 @@ int classes_set_option(ClassBinding* cb, int option, int value) {
 int classes_setup_plant(ClassBinding* cb, bool per_class, int nx, int nu, const void* PM, const void* M0,
                         const void* Pg, const void* g0, const void* A, const void* B) {
     const char* fn = per_class ? "gpad_setup_plant_classes" : "gpad_setup_plant";
-    if (nx <= 0 || nu < 0 || !PM || !Pg) return cfail(GPAD_ERR_INVALID, std::string(fn) + ": bad arguments");
+    if (nx <= 0 || nu < 0 || !PM || !Pg) return fail(GPAD_ERR_INVALID, std::string(fn) + ": bad arguments");
     if ((A == nullptr) != (B == nullptr) || (A && nu == 0))
-        return cfail(GPAD_ERR_INVALID, std::string(fn) + ": give A and B together (nu >= 1)");
+        return fail(GPAD_ERR_INVALID, std::string(fn) + ": give A and B together (nu >= 1)");
     const gpad_dims_t& d = cb->dims;
-    if (nu > d.n) return cfail(GPAD_ERR_INVALID, std::string(fn) + ": nu > n");
-    const size_t es = esz(d.dtype), copies = per_class ? (size_t)cb->K : 1;
+    if (nu > d.n) return fail(GPAD_ERR_INVALID, std::string(fn) + ": nu > n");
+    const size_t es = esize(d.dtype), copies = per_class ? (size_t)cb->K : 1;
     const void* src[6] = {PM, M0, Pg, g0, A, B};
     const size_t elems[6] = {(size_t)d.n * nx, (size_t)d.n, (size_t)d.m * nx, (size_t)d.m, (size_t)nx * nx,
                              (size_t)nx * nu};
     const char* dev[6];
-    Buf up;
+    DevBuf up;
     if (d.memory == GPAD_MEM_HOST) {  // the children take device pointers
         size_t total = 0;
         for (int i = 0; i < 6; ++i) total += src[i] ? elems[i] * copies : 0;
@@ -288,7 +226,7 @@ int classes_setup_plant(ClassBinding* cb, bool per_class, int nx, int nu, const 
         if (e == hipSuccess) e = hipStreamSynchronize(cb->stream);
         if (e != hipSuccess) {
             up.release();
-            return cfail(GPAD_ERR_HIP, std::string(fn) + ": map upload: " + hipGetErrorString(e));
+            return fail(GPAD_ERR_HIP, std::string(fn) + ": map upload: " + hipGetErrorString(e));
         }
     } else {
         for (int i = 0; i < 6; ++i) dev[i] = (const char*)src[i];
@@ -313,7 +251,7 @@ int classes_setup_plant(ClassBinding* cb, bool per_class, int nx, int nu, const 
 // The stats of the last run from every child (each call synchronises the stream and reports that child's
 // device error word); counts and codes placed in the caller's order.
 int classes_last_stats(ClassBinding* cb, gpad_stats_t* st) {
-    if (cb->last_steps <= 0) return cfail(GPAD_ERR_NOT_SETUP, "gpad_last_stats: no run yet");
+    if (cb->last_steps <= 0) return fail(GPAD_ERR_NOT_SETUP, "gpad_last_stats: no run yet");
     const int batch = cb->dims.batch, steps = cb->last_steps;
     st->iterations = 0;
     st->converged = 0;
@@ -357,7 +295,7 @@ int classes_last_stats(ClassBinding* cb, gpad_stats_t* st) {
     }
     float ms = 0.0f;
     if (cb->timed && hipEventElapsedTime(&ms, cb->ev0, cb->ev1) == hipSuccess) st->kernel_ms = ms;
-    if (first_err) return cfail(first_err, "class binding: " + first_msg);
+    if (first_err) return fail(first_err, "class binding: " + first_msg);
     return GPAD_OK;
 }
 
@@ -373,12 +311,12 @@ int classes_sync(ClassBinding* cb) {
             first_msg = gpad_last_error();
         }
     }
-    if (first_err) return cfail(first_err, "class binding: " + first_msg);
+    if (first_err) return fail(first_err, "class binding: " + first_msg);
     return GPAD_OK;
 }
 
 int classes_accumulate(ClassBinding* cb, long long* acc) {
-    if (cb->last_steps <= 0) return cfail(GPAD_ERR_NOT_SETUP, "gpad_accumulate_iterations: no run yet");
+    if (cb->last_steps <= 0) return fail(GPAD_ERR_NOT_SETUP, "gpad_accumulate_iterations: no run yet");
     for (gpad_handle_t c : cb->child) {
         if (!c) continue;
         const int rc = gpad_accumulate_iterations(c, acc);
@@ -414,14 +352,14 @@ static int run_typed(ClassBinding* cb, T* z, T* y, const T* M, const T* g, int N
         cy = b + zn;
         T* wM = b + zn + yn;
         T* wg = wM + zn;
-        C_HIP(hipMemcpyAsync(cz, z, sizeof(T) * zn, hipMemcpyHostToDevice, cb->stream));
-        C_HIP(hipMemcpyAsync(cy, y, sizeof(T) * yn, hipMemcpyHostToDevice, cb->stream));
-        C_HIP(hipMemcpyAsync(wM, M, sizeof(T) * zn, hipMemcpyHostToDevice, cb->stream));
-        C_HIP(hipMemcpyAsync(wg, g, sizeof(T) * yn, hipMemcpyHostToDevice, cb->stream));
+        HIP_TRY(hipMemcpyAsync(cz, z, sizeof(T) * zn, hipMemcpyHostToDevice, cb->stream));
+        HIP_TRY(hipMemcpyAsync(cy, y, sizeof(T) * yn, hipMemcpyHostToDevice, cb->stream));
+        HIP_TRY(hipMemcpyAsync(wM, M, sizeof(T) * zn, hipMemcpyHostToDevice, cb->stream));
+        HIP_TRY(hipMemcpyAsync(wg, g, sizeof(T) * yn, hipMemcpyHostToDevice, cb->stream));
         cM = wM;
         cg = wg;
     }
-    C_HIP(hipEventRecord(cb->ev0, cb->stream));
+    HIP_TRY(hipEventRecord(cb->ev0, cb->stream));
     RowMove<T> in{};
     in.count = 4;
     const T* isrc[4] = {cz, cy, cM, cg};
@@ -432,7 +370,7 @@ static int run_typed(ClassBinding* cb, T* z, T* y, const T* M, const T* g, int N
         in.dst[a] = idst[a];
         in.len[a] = ilen[a];
     }
-    C_HIP(launch_class_gather<T>(in, cb->d_perm(), d.batch, cb->stream));
+    HIP_TRY(launch_class_gather<T>(in, cb->d_perm(), d.batch, cb->stream));
     cb->last_steps = 1;
     cb->timed = false;
     for (int k = 0; k < cb->K; ++k) {
@@ -450,21 +388,21 @@ static int run_typed(ClassBinding* cb, T* z, T* y, const T* M, const T* g, int N
     out.src[1] = sy;
     out.dst[1] = cy;
     out.len[1] = d.m;
-    C_HIP(launch_class_scatter<T>(out, cb->d_perm(), d.batch, cb->stream));
-    C_HIP(hipEventRecord(cb->ev1, cb->stream));
+    HIP_TRY(launch_class_scatter<T>(out, cb->d_perm(), d.batch, cb->stream));
+    HIP_TRY(hipEventRecord(cb->ev1, cb->stream));
     cb->timed = true;
     if (host) {
-        C_HIP(hipMemcpyAsync(z, cz, sizeof(T) * zn, hipMemcpyDeviceToHost, cb->stream));
-        C_HIP(hipMemcpyAsync(y, cy, sizeof(T) * yn, hipMemcpyDeviceToHost, cb->stream));
+        HIP_TRY(hipMemcpyAsync(z, cz, sizeof(T) * zn, hipMemcpyDeviceToHost, cb->stream));
+        HIP_TRY(hipMemcpyAsync(y, cy, sizeof(T) * yn, hipMemcpyDeviceToHost, cb->stream));
     }
     return finish_call(cb, st);
 }
 
 int classes_run(ClassBinding* cb, void* z, void* y, const void* M, const void* g, int N, double tol,
                 gpad_stats_t* st) {
-    if (!z || !y || !M || !g) return cfail(GPAD_ERR_INVALID, "gpad_run: null vector");
-    if (N < 0) return cfail(GPAD_ERR_INVALID, "gpad_run: N < 0");
-    if (!(tol <= 0.0) && !std::isfinite(tol)) return cfail(GPAD_ERR_INVALID, "gpad_run: bad tol");
+    if (!z || !y || !M || !g) return fail(GPAD_ERR_INVALID, "gpad_run: null vector");
+    if (N < 0) return fail(GPAD_ERR_INVALID, "gpad_run: N < 0");
+    if (!(tol <= 0.0) && !std::isfinite(tol)) return fail(GPAD_ERR_INVALID, "gpad_run: bad tol");
     if (cb->dims.dtype == GPAD_DTYPE_F64)
         return run_typed<double>(cb, (double*)z, (double*)y, (const double*)M, (const double*)g, N, tol, st);
     return run_typed<float>(cb, (float*)z, (float*)y, (const float*)M, (const float*)g, N, tol, st);
@@ -495,13 +433,13 @@ static int state_typed(ClassBinding* cb, T* x, T* z, T* y, int steps, int N, dou
         cy = cz + zn;
         cxs = xsn ? cy + yn : nullptr;
         cus = usn ? cy + yn + xsn : nullptr;
-        C_HIP(hipMemcpyAsync(cx, x, sizeof(T) * xn, hipMemcpyHostToDevice, cb->stream));
+        HIP_TRY(hipMemcpyAsync(cx, x, sizeof(T) * xn, hipMemcpyHostToDevice, cb->stream));
         if (zy_in) {
-            C_HIP(hipMemcpyAsync(cz, z, sizeof(T) * zn, hipMemcpyHostToDevice, cb->stream));
-            C_HIP(hipMemcpyAsync(cy, y, sizeof(T) * yn, hipMemcpyHostToDevice, cb->stream));
+            HIP_TRY(hipMemcpyAsync(cz, z, sizeof(T) * zn, hipMemcpyHostToDevice, cb->stream));
+            HIP_TRY(hipMemcpyAsync(cy, y, sizeof(T) * yn, hipMemcpyHostToDevice, cb->stream));
         }
     }
-    C_HIP(hipEventRecord(cb->ev0, cb->stream));
+    HIP_TRY(hipEventRecord(cb->ev0, cb->stream));
     RowMove<T> in{};
     in.count = zy_in ? 3 : 1;
     in.src[0] = cx;
@@ -513,7 +451,7 @@ static int state_typed(ClassBinding* cb, T* x, T* z, T* y, int steps, int N, dou
     in.src[2] = cy;
     in.dst[2] = sy;
     in.len[2] = d.m;
-    C_HIP(launch_class_gather<T>(in, cb->d_perm(), d.batch, cb->stream));
+    HIP_TRY(launch_class_gather<T>(in, cb->d_perm(), d.batch, cb->stream));
     cb->last_steps = loop ? steps : 1;
     cb->timed = false;
     for (int k = 0; k < cb->K; ++k) {
@@ -538,7 +476,7 @@ static int state_typed(ClassBinding* cb, T* x, T* z, T* y, int steps, int N, dou
     if (loop) add(sx, cx, nx);  // (gpad_run_state leaves x alone)
     add(sz, cz, d.n);
     add(sy, cy, d.m);
-    C_HIP(launch_class_scatter<T>(out, cb->d_perm(), d.batch, cb->stream));
+    HIP_TRY(launch_class_scatter<T>(out, cb->d_perm(), d.batch, cb->stream));
     if (xsn || usn) {
         TrajMove<T> tr{};
         tr.count = 0;
@@ -552,17 +490,17 @@ static int state_typed(ClassBinding* cb, T* x, T* z, T* y, int steps, int N, dou
             tr.dst[tr.count] = cus;
             tr.len[tr.count++] = nu;
         }
-        C_HIP(launch_class_traj_scatter<T>(tr, cb->d_perm(), cb->d_pos_off(), cb->d_pos_cnt(), d.batch, steps,
+        HIP_TRY(launch_class_traj_scatter<T>(tr, cb->d_perm(), cb->d_pos_off(), cb->d_pos_cnt(), d.batch, steps,
                                            cb->stream));
     }
-    C_HIP(hipEventRecord(cb->ev1, cb->stream));
+    HIP_TRY(hipEventRecord(cb->ev1, cb->stream));
     cb->timed = true;
     if (host) {
-        if (loop) C_HIP(hipMemcpyAsync(x, cx, sizeof(T) * xn, hipMemcpyDeviceToHost, cb->stream));
-        C_HIP(hipMemcpyAsync(z, cz, sizeof(T) * zn, hipMemcpyDeviceToHost, cb->stream));
-        C_HIP(hipMemcpyAsync(y, cy, sizeof(T) * yn, hipMemcpyDeviceToHost, cb->stream));
-        if (xsn) C_HIP(hipMemcpyAsync(xs, cxs, sizeof(T) * xsn, hipMemcpyDeviceToHost, cb->stream));
-        if (usn) C_HIP(hipMemcpyAsync(us, cus, sizeof(T) * usn, hipMemcpyDeviceToHost, cb->stream));
+        if (loop) HIP_TRY(hipMemcpyAsync(x, cx, sizeof(T) * xn, hipMemcpyDeviceToHost, cb->stream));
+        HIP_TRY(hipMemcpyAsync(z, cz, sizeof(T) * zn, hipMemcpyDeviceToHost, cb->stream));
+        HIP_TRY(hipMemcpyAsync(y, cy, sizeof(T) * yn, hipMemcpyDeviceToHost, cb->stream));
+        if (xsn) HIP_TRY(hipMemcpyAsync(xs, cxs, sizeof(T) * xsn, hipMemcpyDeviceToHost, cb->stream));
+        if (usn) HIP_TRY(hipMemcpyAsync(us, cus, sizeof(T) * usn, hipMemcpyDeviceToHost, cb->stream));
     }
     return finish_call(cb, st);
 }
@@ -570,11 +508,11 @@ static int state_typed(ClassBinding* cb, T* x, T* z, T* y, int steps, int N, dou
 int classes_state(ClassBinding* cb, void* x, void* z, void* y, int steps, int N, double tol, int warm, void* xs,
                   void* us, gpad_stats_t* st) {
     const std::string where = steps > 0 ? "gpad_closed_loop" : "gpad_run_state";
-    if (!cb->plant) return cfail(GPAD_ERR_NOT_SETUP, where + ": call gpad_setup_plant after gpad_setup_classes");
-    if (steps > 0 && !cb->plant_dyn) return cfail(GPAD_ERR_NOT_SETUP, where + ": plant bound without A, B");
-    if (!x || !z || !y) return cfail(GPAD_ERR_INVALID, where + ": null vector");
-    if (N < 0 || steps < 0) return cfail(GPAD_ERR_INVALID, where + ": N, steps must be >= 0");
-    if (!(tol <= 0.0) && !std::isfinite(tol)) return cfail(GPAD_ERR_INVALID, where + ": bad tol");
+    if (!cb->plant) return fail(GPAD_ERR_NOT_SETUP, where + ": call gpad_setup_plant after gpad_setup_classes");
+    if (steps > 0 && !cb->plant_dyn) return fail(GPAD_ERR_NOT_SETUP, where + ": plant bound without A, B");
+    if (!x || !z || !y) return fail(GPAD_ERR_INVALID, where + ": null vector");
+    if (N < 0 || steps < 0) return fail(GPAD_ERR_INVALID, where + ": N, steps must be >= 0");
+    if (!(tol <= 0.0) && !std::isfinite(tol)) return fail(GPAD_ERR_INVALID, where + ": bad tol");
     if (cb->dims.dtype == GPAD_DTYPE_F64)
         return state_typed<double>(cb, (double*)x, (double*)z, (double*)y, steps, N, tol, warm, (double*)xs,
                                    (double*)us, st);

@@ -1,5 +1,5 @@
 // gpad_classes.h -- the class binding (gpad_setup_classes, include/gpad.h): a fleet of K plant classes
-// solved class by class as shared-matrix sub-batches.  Shared by gpad_host.cpp (the entry points branch
+// solved class by class as shared-matrix sub-batches.  Shared by the host runtime (gpad_host.h; the entry points branch
 // here at their top), gpad_classes.cpp (the runtime) and gpad_classes.hip (the row permutations).
 //
 // Not here: classes running concurrently on several streams (they run one after the other on the

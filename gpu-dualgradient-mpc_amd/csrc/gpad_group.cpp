@@ -16,7 +16,6 @@
 // A device listed twice (one GPU standing in for several, e.g. the 1-GPU test box) has no RCCL
 // clique (RCCL refuses duplicate devices): the same moves are then peer copies
 // (hipMemcpyPeerAsync), ordered by events exactly where the RCCL calls are.
-#include <hip/hip_runtime.h>
 #include <dlfcn.h>
 #include <rccl/rccl.h>  // types only: librccl is loaded on first use (current_rccl() below), not linked
 
@@ -25,24 +24,11 @@
 #include <cstring>
 #include <memory>
 #include <mutex>
-#include <string>
-#include <vector>
 
-#include "../../include/gpad.h"
-#include "gpad_abi.h"
-#include "gpad_internal.h"
+#include "gpad_host.h"
 
 namespace {
 
-int gfail(int code, const std::string& msg) { return gpad::set_last_error(code, msg); }
-
-#define G_HIP(expr)                                                                                   \
-    do {                                                                                              \
-        hipError_t _e = (expr);                                                                       \
-        if (_e != hipSuccess)                                                                         \
-            return gfail(_e == hipErrorOutOfMemory ? GPAD_ERR_NOMEM : GPAD_ERR_HIP,                   \
-                         std::string(#expr) + ": " + hipGetErrorString(_e));                          \
-    } while (0)
 // RCCL entry points, resolved from librccl on the first group over distinct devices, so that
 // single-GPU users of libgpad (gpad_solve, the handle API) never need RCCL installed.  Without it a
 // group falls back to the peer-copy transport (gpad_group_transport reports which).
@@ -101,10 +87,8 @@ std::shared_ptr<const Rccl> current_rccl(unsigned* gen = nullptr) {
     do {                                                                                              \
         ncclResult_t _r = g->r->expr;                                                                 \
         if (_r != ncclSuccess)                                                                        \
-            return gfail(GPAD_ERR_HIP, std::string("nccl" #expr) + ": " + g->r->GetErrorString(_r));   \
+            return fail(GPAD_ERR_HIP, std::string("nccl" #expr) + ": " + g->r->GetErrorString(_r));   \
     } while (0)
-
-size_t esz(int dtype) { return dtype == GPAD_DTYPE_F64 ? sizeof(double) : sizeof(float); }
 
 }  // namespace
 
@@ -120,10 +104,8 @@ struct gpad_group_s {
     double L = 0.0;
     bool ready = false;
     std::vector<int> start, count;   // shard of device d: [start, start + count)
-    std::vector<void*> vec;          // per device: M | g | z | y of its shard (device memory)
-    std::vector<size_t> vec_bytes;
-    std::vector<void*> mat;          // per device: raw ML | G before packing
-    std::vector<size_t> mat_bytes;
+    std::vector<DevBuf> vec;         // per device: M | g | z | y of its shard (device memory)
+    std::vector<DevBuf> mat;         // per device: raw ML | G before packing
     hipStream_t caller = nullptr;    // the caller's stream on devices[0] (gpad_group_set_stream;
                                      // NULL = the device's null stream)
     hipEvent_t caller_ev = nullptr;  // recorded on it before the group touches device buffers
@@ -136,8 +118,8 @@ int release(gpad_group_s* g) {
         (void)hipSetDevice(g->dev[d]);
         if (d < (int)g->st.size() && g->st[d]) (void)hipStreamSynchronize(g->st[d]);
         if (d < (int)g->h.size() && g->h[d]) gpad_destroy(g->h[d]);
-        if (d < (int)g->vec.size() && g->vec[d]) (void)hipFree(g->vec[d]);
-        if (d < (int)g->mat.size() && g->mat[d]) (void)hipFree(g->mat[d]);
+        if (d < (int)g->vec.size()) g->vec[d].release();
+        if (d < (int)g->mat.size()) g->mat[d].release();
         if (d < (int)g->ev.size() && g->ev[d]) (void)hipEventDestroy(g->ev[d]);
         if (d < (int)g->st.size() && g->st[d]) (void)hipStreamDestroy(g->st[d]);
     }
@@ -150,16 +132,11 @@ int release(gpad_group_s* g) {
     return GPAD_OK;
 }
 
-int ensure(gpad_group_s* g, std::vector<void*>& bufs, std::vector<size_t>& sizes, int d, size_t want) {
-    if (sizes[d] >= want && bufs[d]) return GPAD_OK;
-    G_HIP(hipSetDevice(g->dev[d]));
-    if (bufs[d]) (void)hipFree(bufs[d]);
-    bufs[d] = nullptr;
-    sizes[d] = 0;
-    if (want == 0) return GPAD_OK;
-    G_HIP(hipMalloc(&bufs[d], want));
-    sizes[d] = want;
-    return GPAD_OK;
+// device d's buffer b (the allocation is made on that device)
+int ensure(gpad_group_s* g, DevBuf& b, int d, size_t want) {
+    if (want <= b.bytes && b.p) return GPAD_OK;
+    HIP_TRY(hipSetDevice(g->dev[d]));
+    return b.ensure(want);
 }
 
 // Root -> device d moves: (dst on device d, src on the root) pairs, all in one RCCL group (or
@@ -182,13 +159,13 @@ int scatter(gpad_group_s* g, const std::vector<Move>& mv) {
         G_NCCL(GroupEnd());
         return GPAD_OK;
     }
-    G_HIP(hipSetDevice(g->dev[0]));
+    HIP_TRY(hipSetDevice(g->dev[0]));
     for (const Move& x : mv)
-        G_HIP(hipMemcpyPeerAsync(x.dst, g->dev[x.d], x.src, g->dev[0], x.bytes, g->st[0]));
-    G_HIP(hipEventRecord(g->ev[0], g->st[0]));
+        HIP_TRY(hipMemcpyPeerAsync(x.dst, g->dev[x.d], x.src, g->dev[0], x.bytes, g->st[0]));
+    HIP_TRY(hipEventRecord(g->ev[0], g->st[0]));
     for (int d = 1; d < g->ndev; ++d) {
-        G_HIP(hipSetDevice(g->dev[d]));
-        G_HIP(hipStreamWaitEvent(g->st[d], g->ev[0], 0));
+        HIP_TRY(hipSetDevice(g->dev[d]));
+        HIP_TRY(hipStreamWaitEvent(g->st[d], g->ev[0], 0));
     }
     return GPAD_OK;
 }
@@ -206,14 +183,14 @@ int gather(gpad_group_s* g, const std::vector<Move>& mv) {
         return GPAD_OK;
     }
     for (int d = 1; d < g->ndev; ++d) {  // the root copies once every shard's solve is done
-        G_HIP(hipSetDevice(g->dev[d]));
-        G_HIP(hipEventRecord(g->ev[d], g->st[d]));
-        G_HIP(hipSetDevice(g->dev[0]));
-        G_HIP(hipStreamWaitEvent(g->st[0], g->ev[d], 0));
+        HIP_TRY(hipSetDevice(g->dev[d]));
+        HIP_TRY(hipEventRecord(g->ev[d], g->st[d]));
+        HIP_TRY(hipSetDevice(g->dev[0]));
+        HIP_TRY(hipStreamWaitEvent(g->st[0], g->ev[d], 0));
     }
-    G_HIP(hipSetDevice(g->dev[0]));
+    HIP_TRY(hipSetDevice(g->dev[0]));
     for (const Move& x : mv)
-        G_HIP(hipMemcpyPeerAsync(x.dst, g->dev[0], x.src, g->dev[x.d], x.bytes, g->st[0]));
+        HIP_TRY(hipMemcpyPeerAsync(x.dst, g->dev[0], x.src, g->dev[x.d], x.bytes, g->st[0]));
     return GPAD_OK;
 }
 
@@ -221,19 +198,19 @@ int gather(gpad_group_s* g, const std::vector<Move>& mv) {
 // streams are non-blocking, so every one of them first waits for the work queued there so far
 // (else a producer kernel still in flight could race with the scatter or the root's solve).
 int order_after_caller(gpad_group_s* g) {
-    G_HIP(hipSetDevice(g->dev[0]));
-    G_HIP(hipEventRecord(g->caller_ev, g->caller));
+    HIP_TRY(hipSetDevice(g->dev[0]));
+    HIP_TRY(hipEventRecord(g->caller_ev, g->caller));
     for (int d = 0; d < g->ndev; ++d) {
-        G_HIP(hipSetDevice(g->dev[d]));
-        G_HIP(hipStreamWaitEvent(g->st[d], g->caller_ev, 0));
+        HIP_TRY(hipSetDevice(g->dev[d]));
+        HIP_TRY(hipStreamWaitEvent(g->st[d], g->caller_ev, 0));
     }
     return GPAD_OK;
 }
 
 int sync_all(gpad_group_s* g) {
     for (int d = 0; d < g->ndev; ++d) {
-        G_HIP(hipSetDevice(g->dev[d]));
-        G_HIP(hipStreamSynchronize(g->st[d]));
+        HIP_TRY(hipSetDevice(g->dev[d]));
+        HIP_TRY(hipStreamSynchronize(g->st[d]));
     }
     return GPAD_OK;
 }
@@ -244,30 +221,28 @@ extern "C" {
 
 int gpad_group_create(gpad_group_t* out, int ndev, const int* devices) {
     return gpad::abi_guard("gpad_group_create", [&]() -> int {
-        if (!out || ndev <= 0 || !devices) return gfail(GPAD_ERR_INVALID, "gpad_group_create: bad arguments");
+        if (!out || ndev <= 0 || !devices) return fail(GPAD_ERR_INVALID, "gpad_group_create: bad arguments");
         *out = nullptr;
         int visible = 0;
         if (hipGetDeviceCount(&visible) != hipSuccess || visible <= 0)
-            return gfail(GPAD_ERR_NO_DEVICE, "gpad_group_create: no HIP device visible");
+            return fail(GPAD_ERR_NO_DEVICE, "gpad_group_create: no HIP device visible");
         for (int d = 0; d < ndev; ++d)
             if (devices[d] < 0 || devices[d] >= visible)
-                return gfail(GPAD_ERR_INVALID, "gpad_group_create: bad device index");
+                return fail(GPAD_ERR_INVALID, "gpad_group_create: bad device index");
         auto* g = new gpad_group_s;
         g->ndev = ndev;
         g->dev.assign(devices, devices + ndev);
         g->h.assign(ndev, nullptr);
         g->st.assign(ndev, nullptr);
         g->ev.assign(ndev, nullptr);
-        g->vec.assign(ndev, nullptr);
-        g->vec_bytes.assign(ndev, 0);
-        g->mat.assign(ndev, nullptr);
-        g->mat_bytes.assign(ndev, 0);
+        g->vec.assign(ndev, DevBuf{});
+        g->mat.assign(ndev, DevBuf{});
         for (int d = 0; d < ndev; ++d) {
             int rc;
             if (hipSetDevice(g->dev[d]) != hipSuccess || hipStreamCreateWithFlags(&g->st[d], hipStreamNonBlocking) != hipSuccess ||
                 hipEventCreateWithFlags(&g->ev[d], hipEventDisableTiming) != hipSuccess) {
                 release(g);
-                return gfail(GPAD_ERR_HIP, "gpad_group_create: stream/event creation failed");
+                return fail(GPAD_ERR_HIP, "gpad_group_create: stream/event creation failed");
             }
             if ((rc = gpad_create(&g->h[d], g->dev[d], g->st[d]))) {
                 release(g);
@@ -277,7 +252,7 @@ int gpad_group_create(gpad_group_t* out, int ndev, const int* devices) {
         if (hipSetDevice(g->dev[0]) != hipSuccess ||
             hipEventCreateWithFlags(&g->caller_ev, hipEventDisableTiming) != hipSuccess) {
             release(g);
-            return gfail(GPAD_ERR_HIP, "gpad_group_create: event creation failed");
+            return fail(GPAD_ERR_HIP, "gpad_group_create: event creation failed");
         }
         std::vector<int> sorted(g->dev);
         std::sort(sorted.begin(), sorted.end());
@@ -289,7 +264,7 @@ int gpad_group_create(gpad_group_t* out, int ndev, const int* devices) {
             if (r != ncclSuccess) {
                 g->comm.clear();
                 release(g);
-                return gfail(GPAD_ERR_HIP, std::string("ncclCommInitAll: ") + g->r->GetErrorString(r));
+                return fail(GPAD_ERR_HIP, std::string("ncclCommInitAll: ") + g->r->GetErrorString(r));
             }
         }
         *out = g;
@@ -313,7 +288,7 @@ int gpad_group_rccl_library(const char* path, int force_rccl) {
             ++g_rccl_gen;
         }
         if (!r->ok)
-            return gfail(GPAD_ERR_UNSUPPORTED, std::string("gpad_group_rccl_library: cannot load the RCCL entry points from ") +
+            return fail(GPAD_ERR_UNSUPPORTED, std::string("gpad_group_rccl_library: cannot load the RCCL entry points from ") +
                                                    (path ? path : "librccl") + " (groups use peer copies)");
         return GPAD_OK;
     });
@@ -321,14 +296,14 @@ int gpad_group_rccl_library(const char* path, int force_rccl) {
 
 int gpad_group_transport(gpad_group_t g) {
     return gpad::abi_guard("gpad_group_transport", [&]() -> int {
-        if (!g) return gfail(GPAD_ERR_INVALID, "gpad_group_transport: null group");
+        if (!g) return fail(GPAD_ERR_INVALID, "gpad_group_transport: null group");
         return g->comm.empty() ? GPAD_GROUP_PEER : GPAD_GROUP_RCCL;
     });
 }
 
 int gpad_group_set_stream(gpad_group_t g, void* hip_stream) {
     return gpad::abi_guard("gpad_group_set_stream", [&]() -> int {
-        if (!g) return gfail(GPAD_ERR_INVALID, "gpad_group_set_stream: null group");
+        if (!g) return fail(GPAD_ERR_INVALID, "gpad_group_set_stream: null group");
         g->caller = static_cast<hipStream_t>(hip_stream);
         return GPAD_OK;
     });
@@ -336,9 +311,9 @@ int gpad_group_set_stream(gpad_group_t g, void* hip_stream) {
 
 int gpad_group_setup(gpad_group_t g, const gpad_dims_t* dims, const void* ML, const void* G, double L) {
     return gpad::abi_guard("gpad_group_setup", [&]() -> int {
-        if (!g || !dims || !ML || !G) return gfail(GPAD_ERR_INVALID, "gpad_group_setup: bad arguments");
+        if (!g || !dims || !ML || !G) return fail(GPAD_ERR_INVALID, "gpad_group_setup: bad arguments");
         if (dims->batch < 1 || dims->n <= 0 || dims->m <= 0)
-            return gfail(GPAD_ERR_INVALID, "gpad_group_setup: dims: n, m, batch must be positive");
+            return fail(GPAD_ERR_INVALID, "gpad_group_setup: dims: n, m, batch must be positive");
         g->ready = false;
         const int nd = g->ndev, B = dims->batch;
         g->start.assign(nd, 0);
@@ -349,7 +324,7 @@ int gpad_group_setup(gpad_group_t g, const gpad_dims_t* dims, const void* ML, co
             s += g->count[d];
         }
         const bool host = dims->memory == GPAD_MEM_HOST;
-        const size_t es = esz(dims->dtype), nm = (size_t)dims->n * dims->m * es;
+        const size_t es = esize(dims->dtype), nm = (size_t)dims->n * dims->m * es;
         std::vector<Move> mv;
         std::vector<const void*> mlp(nd), gp(nd);
         int rc;
@@ -359,11 +334,11 @@ int gpad_group_setup(gpad_group_t g, const gpad_dims_t* dims, const void* ML, co
             const size_t per = dims->shared ? nm : nm * (size_t)c;  // each of ML and G
             const size_t off = dims->shared ? 0 : nm * (size_t)g->start[d];
             if (g->count[d] == 0 && !dims->shared) {  // more devices than instances: an idle shard
-                if ((rc = ensure(g, g->mat, g->mat_bytes, d, 2 * per))) return rc;
-                G_HIP(hipSetDevice(g->dev[d]));
-                G_HIP(hipMemsetAsync(g->mat[d], 0, 2 * per, g->st[d]));
-                mlp[d] = g->mat[d];
-                gp[d] = (char*)g->mat[d] + per;
+                if ((rc = ensure(g, g->mat[d], d, 2 * per))) return rc;
+                HIP_TRY(hipSetDevice(g->dev[d]));
+                HIP_TRY(hipMemsetAsync(g->mat[d].p, 0, 2 * per, g->st[d]));
+                mlp[d] = g->mat[d].p;
+                gp[d] = (char*)g->mat[d].p + per;
                 continue;
             }
             if (!host && d == 0) {  // the root's shard reads the caller's buffers in place
@@ -371,15 +346,15 @@ int gpad_group_setup(gpad_group_t g, const gpad_dims_t* dims, const void* ML, co
                 gp[d] = (const char*)G + off;
                 continue;
             }
-            if ((rc = ensure(g, g->mat, g->mat_bytes, d, 2 * per))) return rc;
-            void* dml = g->mat[d];
-            void* dg = (char*)g->mat[d] + per;
+            if ((rc = ensure(g, g->mat[d], d, 2 * per))) return rc;
+            void* dml = g->mat[d].p;
+            void* dg = (char*)g->mat[d].p + per;
             mlp[d] = dml;
             gp[d] = dg;
             if (host) {
-                G_HIP(hipSetDevice(g->dev[d]));
-                G_HIP(hipMemcpyAsync(dml, (const char*)ML + off, per, hipMemcpyHostToDevice, g->st[d]));
-                G_HIP(hipMemcpyAsync(dg, (const char*)G + off, per, hipMemcpyHostToDevice, g->st[d]));
+                HIP_TRY(hipSetDevice(g->dev[d]));
+                HIP_TRY(hipMemcpyAsync(dml, (const char*)ML + off, per, hipMemcpyHostToDevice, g->st[d]));
+                HIP_TRY(hipMemcpyAsync(dg, (const char*)G + off, per, hipMemcpyHostToDevice, g->st[d]));
             } else if (!dims->shared || g->comm.empty()) {
                 mv.push_back({d, dml, (const char*)ML + off, per});
                 mv.push_back({d, dg, (const char*)G + off, per});
@@ -411,12 +386,12 @@ int gpad_group_setup(gpad_group_t g, const gpad_dims_t* dims, const void* ML, co
 int gpad_group_run(gpad_group_t g, void* z0, void* y0, const void* M, const void* gv, int N, double tol,
                    gpad_stats_t* st) {
     return gpad::abi_guard("gpad_group_run", [&]() -> int {
-        if (!g) return gfail(GPAD_ERR_INVALID, "gpad_group_run: null group");
-        if (!g->ready) return gfail(GPAD_ERR_NOT_SETUP, "gpad_group_run: call gpad_group_setup first");
-        if (!z0 || !y0 || !M || !gv) return gfail(GPAD_ERR_INVALID, "gpad_group_run: null vector");
+        if (!g) return fail(GPAD_ERR_INVALID, "gpad_group_run: null group");
+        if (!g->ready) return fail(GPAD_ERR_NOT_SETUP, "gpad_group_run: call gpad_group_setup first");
+        if (!z0 || !y0 || !M || !gv) return fail(GPAD_ERR_INVALID, "gpad_group_run: null vector");
         const gpad_dims_t& D = g->dims;
         const bool host = D.memory == GPAD_MEM_HOST;
-        const size_t es = esz(D.dtype), nb = (size_t)D.n * es, mb = (size_t)D.m * es;
+        const size_t es = esize(D.dtype), nb = (size_t)D.n * es, mb = (size_t)D.m * es;
         const int nd = g->ndev;
         std::vector<char*> Mp(nd), gp(nd), zp(nd), yp(nd);
         std::vector<Move> in, out;
@@ -431,18 +406,18 @@ int gpad_group_run(gpad_group_t g, void* z0, void* y0, const void* M, const void
                 yp[d] = (char*)y0;
                 continue;
             }
-            if ((rc = ensure(g, g->vec, g->vec_bytes, d, std::max<size_t>(1, 2 * c * (nb + mb))))) return rc;
-            Mp[d] = (char*)g->vec[d];
+            if ((rc = ensure(g, g->vec[d], d, std::max<size_t>(1, 2 * c * (nb + mb))))) return rc;
+            Mp[d] = (char*)g->vec[d].p;
             gp[d] = Mp[d] + c * nb;
             zp[d] = gp[d] + c * mb;
             yp[d] = zp[d] + c * nb;
             if (c == 0) continue;
             if (host) {
-                G_HIP(hipSetDevice(g->dev[d]));
-                G_HIP(hipMemcpyAsync(Mp[d], (const char*)M + s0 * nb, c * nb, hipMemcpyHostToDevice, g->st[d]));
-                G_HIP(hipMemcpyAsync(gp[d], (const char*)gv + s0 * mb, c * mb, hipMemcpyHostToDevice, g->st[d]));
-                G_HIP(hipMemcpyAsync(zp[d], (const char*)z0 + s0 * nb, c * nb, hipMemcpyHostToDevice, g->st[d]));
-                G_HIP(hipMemcpyAsync(yp[d], (const char*)y0 + s0 * mb, c * mb, hipMemcpyHostToDevice, g->st[d]));
+                HIP_TRY(hipSetDevice(g->dev[d]));
+                HIP_TRY(hipMemcpyAsync(Mp[d], (const char*)M + s0 * nb, c * nb, hipMemcpyHostToDevice, g->st[d]));
+                HIP_TRY(hipMemcpyAsync(gp[d], (const char*)gv + s0 * mb, c * mb, hipMemcpyHostToDevice, g->st[d]));
+                HIP_TRY(hipMemcpyAsync(zp[d], (const char*)z0 + s0 * nb, c * nb, hipMemcpyHostToDevice, g->st[d]));
+                HIP_TRY(hipMemcpyAsync(yp[d], (const char*)y0 + s0 * mb, c * mb, hipMemcpyHostToDevice, g->st[d]));
             } else {
                 in.push_back({d, Mp[d], (const char*)M + s0 * nb, c * nb});
                 in.push_back({d, gp[d], (const char*)gv + s0 * mb, c * mb});
@@ -462,9 +437,9 @@ int gpad_group_run(gpad_group_t g, void* z0, void* y0, const void* M, const void
             for (int d = 0; d < nd; ++d) {
                 const size_t c = (size_t)g->count[d], s0 = (size_t)g->start[d];
                 if (c == 0) continue;
-                G_HIP(hipSetDevice(g->dev[d]));
-                G_HIP(hipMemcpyAsync((char*)z0 + s0 * nb, zp[d], c * nb, hipMemcpyDeviceToHost, g->st[d]));
-                G_HIP(hipMemcpyAsync((char*)y0 + s0 * mb, yp[d], c * mb, hipMemcpyDeviceToHost, g->st[d]));
+                HIP_TRY(hipSetDevice(g->dev[d]));
+                HIP_TRY(hipMemcpyAsync((char*)z0 + s0 * nb, zp[d], c * nb, hipMemcpyDeviceToHost, g->st[d]));
+                HIP_TRY(hipMemcpyAsync((char*)y0 + s0 * mb, yp[d], c * mb, hipMemcpyDeviceToHost, g->st[d]));
             }
         }
         if ((rc = sync_all(g))) return rc;
@@ -526,7 +501,7 @@ int gpad_solve_sharded(int ndev, const int* devices, void* z0, void* y0, const v
                        gpad_stats_t* st) {
     return gpad::abi_guard("gpad_solve_sharded", [&]() -> int {
         ShardCache& cache = t_shard_cache;
-        if (ndev <= 0 || !devices) return gfail(GPAD_ERR_INVALID, "gpad_solve_sharded: bad device list");
+        if (ndev <= 0 || !devices) return fail(GPAD_ERR_INVALID, "gpad_solve_sharded: bad device list");
         std::vector<int> want(devices, devices + ndev);
         unsigned gen = 0;
         (void)current_rccl(&gen);

@@ -1,5 +1,5 @@
 // gpad_internal.h -- device-side argument blocks and kernel launchers shared by the
-// HIP kernels (gpad_kernels.hip, gpad_panel.hip) and the host runtime (gpad_host.cpp).
+// HIP kernels (gpad_kernels.hip, gpad_panel.hip) and the host runtime (gpad_host.h and its units).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -13,7 +13,7 @@ namespace gpad {
 int set_last_error(int code, const std::string& msg);
 
 // The class binding of a handle (gpad_setup_classes): per-class child handles, the class-sorted order
-// and its workspaces.  Opaque to gpad_host.cpp, whose gpad_handle_s holds the pointer and whose entry
+// and its workspaces.  Opaque to gpad_host.h, whose gpad_handle_s holds the pointer and whose entry
 // points branch to gpad_classes.h's functions at their top; defined in gpad_classes.cpp.
 struct ClassBinding;
 
@@ -127,7 +127,7 @@ struct SolveArgs {
                            // solve's counts, longest first: LPT over the columns), or null (0..batch-1)
     const struct PanelPlan* plan;  // panel phases: host-side plan from the previous solve (or null)
     struct PanelPlan* used;        // panel phases: host-side record of the phases launched (or null)
-    const Tuning* tune;    // host-side tuning options (never null on a launch from gpad_host.cpp)
+    const Tuning* tune;    // host-side tuning options (never null on a launch from the host runtime)
     const T* Hq;           // QP Hessian H, k-major [n][ldn] (gpad_setup_hessian), or null: enables the
                            // value-function branches of the test (stream kernel only)
     long long strideHq;    // elements between consecutive instances' H images (0 = shared)

@@ -1,0 +1,356 @@
+// gpad_setup.cpp -- binding a problem to a handle: the packed device copies of the constant matrices
+// (k-major -ML and G/L, the MFMA fragment images), the Hessian, the flat battery form, the theta/beta
+// table and the one-time QP precompute.  Replaces the set-up half of the reference's host driver
+// (main.cu:79-203: file read, 9 cudaMallocs, H2D copies).
+#include <algorithm>
+#include <cmath>
+
+#include "gpad_host.h"
+
+int validate_dims(const gpad_dims_t* d) {
+    if (!d) return fail(GPAD_ERR_INVALID, "null dims");
+    if (d->n <= 0 || d->m <= 0 || d->batch <= 0)
+        return fail(GPAD_ERR_INVALID, "dims: n, m, batch must be positive");
+    if (d->dtype != GPAD_DTYPE_F32 && d->dtype != GPAD_DTYPE_F64)
+        return fail(GPAD_ERR_INVALID, "dims: bad dtype");
+    if (d->memory != GPAD_MEM_HOST && d->memory != GPAD_MEM_DEVICE)
+        return fail(GPAD_ERR_INVALID, "dims: bad memory kind");
+    if (d->schedule != GPAD_SCHEDULE_MATLAB && d->schedule != GPAD_SCHEDULE_PAPER)
+        return fail(GPAD_ERR_INVALID, "dims: bad schedule");
+    if (d->kernel < GPAD_KERNEL_AUTO || d->kernel > GPAD_KERNEL_PANEL)
+        return fail(GPAD_ERR_INVALID, "dims: bad kernel");
+    if (!std::isfinite(d->tol_gap)) return fail(GPAD_ERR_INVALID, "dims: tol_gap must be finite");
+    if (d->reserved != 0) return fail(GPAD_ERR_INVALID, "dims: reserved must be 0");
+    return GPAD_OK;
+}
+
+void unbind_problem(gpad_handle_t h) {
+    end_classes(h);
+    h->ready = false;
+    h->flat = false;
+    h->ns = 0;
+    h->shadow_ok = false;
+    h->hess_ok = false;
+    h->frag64_ok = false;
+    h->hfrag64_ok = false;
+    h->plan.nph = 0;
+    h->p64_order_batch = 0;  // (the previous counts order nothing)
+    h->flat_vpred = 0;
+    h->plan_pending = false;
+    h->last_phased = false;
+}
+
+static int setup_impl(gpad_handle_t h, const gpad_dims_t* d, const void* A, const void* B, double L,
+                      bool scaled) {
+    if (!h) return fail(GPAD_ERR_INVALID, "gpad_setup: null handle");
+    int rc = validate_dims(d);
+    if (rc) return rc;
+    if (!A || !B) return fail(GPAD_ERR_INVALID, "gpad_setup: null matrix");
+    if (!(L > 0.0) || !std::isfinite(L)) return fail(GPAD_ERR_INVALID, "gpad_setup: L must be > 0");
+    HIP_TRY(hipSetDevice(h->device));
+    unbind_problem(h);
+    h->dims = *d;
+    if (h->dims.check_every <= 0) h->dims.check_every = 10;
+    h->L = L;
+    h->scaled = scaled;
+    const int n = d->n, m = d->m;
+    h->ldn = round4(n);
+    h->ldm = round4(m);
+    const size_t es = esize(d->dtype);
+    const int nmats = d->shared ? 1 : d->batch;
+    const size_t a_elems = (size_t)m * h->ldn, b_elems = (size_t)n * h->ldm;
+    if ((rc = h->MGt.ensure(es * a_elems * nmats))) return rc;
+    if ((rc = h->GLt.ensure(es * b_elems * nmats))) return rc;
+    const size_t raw = (size_t)n * m * nmats * es;
+    const void* dA = A;
+    const void* dB = B;
+    if (d->memory == GPAD_MEM_HOST) {
+        if ((rc = h->stage.ensure(2 * raw))) return rc;
+        HIP_TRY(hipMemcpyAsync(h->stage.p, A, raw, hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(hipMemcpyAsync((char*)h->stage.p + raw, B, raw, hipMemcpyHostToDevice, h->stream));
+        dA = h->stage.p;
+        dB = (char*)h->stage.p + raw;
+    }
+    // -ML -> k-major [m][ldn];  G/L -> k-major [n][ldm]   (acceldualgrad.m:20,22)
+    const double sa = scaled ? 1.0 : -1.0;
+    const double sb = scaled ? 1.0 : 1.0 / L;
+    const long long in_stride = d->shared ? 0 : (long long)n * m;
+    if (d->dtype == GPAD_DTYPE_F32) {
+        HIP_TRY(gpad::launch_pack_kmajor<float>((const float*)dA, (float*)h->MGt.p, n, m, h->ldn, sa,
+                                                nmats, in_stride, (long long)a_elems, h->stream));
+        HIP_TRY(gpad::launch_pack_kmajor<float>((const float*)dB, (float*)h->GLt.p, m, n, h->ldm, sb,
+                                                nmats, in_stride, (long long)b_elems, h->stream));
+    } else {
+        HIP_TRY(gpad::launch_pack_kmajor<double>((const double*)dA, (double*)h->MGt.p, n, m, h->ldn, sa,
+                                                 nmats, in_stride, (long long)a_elems, h->stream));
+        HIP_TRY(gpad::launch_pack_kmajor<double>((const double*)dB, (double*)h->GLt.p, m, n, h->ldm, sb,
+                                                 nmats, in_stride, (long long)b_elems, h->stream));
+    }
+    // f64 panels: -ML | G_L in the f64 MFMA fragment layout (gpad_panel64.hip)
+    if (d->shared && d->dtype == GPAD_DTYPE_F64 && gpad::panel64_supported(n, m)) {
+        const int T = gpad::panel64_tiles(n, m);
+        const size_t ob = gpad::panel64_frag_bytes(n, m);
+        if ((rc = h->frag64.ensure(2 * ob))) return rc;
+        HIP_TRY(gpad::launch_pack_panel64((const double*)dA, n, m, sa, T, h->frag64.p, h->stream));
+        HIP_TRY(gpad::launch_pack_panel64((const double*)dB, m, n, sb, T, (char*)h->frag64.p + ob, h->stream));
+        h->frag64_tiles = T;
+        h->frag64_ok = true;
+    }
+    // fragment image for the MFMA panel kernel (shared f32 matrices only); the buffer is kept
+    // across setups and only grows
+    h->frag_ok = false;
+    h->frag_tiles = 0;
+    if (d->shared && d->dtype == GPAD_DTYPE_F32) {
+        const size_t fb = gpad::panel_frag_bytes(n, m, d->batch);
+        if (fb > 0) {
+            if ((rc = h->frag.ensure(fb))) return rc;
+            HIP_TRY(gpad::launch_pack_panel((const float*)dA, (const float*)dB, n, m, d->batch,
+                                            (float)sa, sb, h->frag.p, h->stream));
+            h->frag_tiles = gpad::panel_tiles(n, m, d->batch);
+            h->frag_ok = true;
+        }
+    }
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (d->memory == GPAD_MEM_HOST && !h->keep_stage) h->stage.release();
+    h->ready = true;
+    return GPAD_OK;
+}
+
+static void host_schedule(int N, int kind, double* theta, double* beta) {
+    // acceldualgrad.m:18,27,55-56 (MATLAB: beta lagged one iteration) / paper eq. (8e)
+    double th = 1.0, thm1 = 1.0, b = 0.0;
+    for (int v = 0; v < N; ++v) {
+        const double thn = (std::sqrt(std::pow(th, 4.0) + 4.0 * std::pow(th, 2.0)) - std::pow(th, 2.0)) / 2.0;
+        theta[v] = th;
+        if (kind == GPAD_SCHEDULE_PAPER) {
+            beta[v] = th * (1.0 / thm1 - 1.0);
+        } else {
+            beta[v] = b;
+            b = th * (1.0 / thm1 - 1.0);
+        }
+        thm1 = th;
+        th = thn;
+    }
+}
+
+int ensure_schedule(gpad_handle_t h, int N, const void* theta_in, const void* beta_in) {
+    const int dt = h->dims.dtype;
+    const size_t es = esize(dt);
+    const bool custom = theta_in != nullptr || beta_in != nullptr;
+    if (!custom && h->sched_len >= N + 2 && h->sched_kind == h->dims.schedule && h->sched_dtype == dt)
+        return GPAD_OK;
+    const int len = N + 2;  // kernels prefetch theta[v+1], beta[v+2]
+    std::vector<double> th(len, 0.0), be(len, 0.0);
+    host_schedule(N, h->dims.schedule, th.data(), be.data());
+    if (custom) {
+        if (!theta_in || !beta_in) return fail(GPAD_ERR_INVALID, "run_scaled: give both theta and beta");
+        for (int v = 0; v < N; ++v) {
+            th[v] = dt == GPAD_DTYPE_F64 ? ((const double*)theta_in)[v] : ((const float*)theta_in)[v];
+            be[v] = dt == GPAD_DTYPE_F64 ? ((const double*)beta_in)[v] : ((const float*)beta_in)[v];
+        }
+    }
+    th[N] = th[N + 1] = 0.0;  // pads: read by the prefetch, never used
+    be[N] = be[N + 1] = 0.0;
+    int rc;
+    if ((rc = h->theta.ensure(es * len))) return rc;
+    if ((rc = h->beta.ensure(es * len))) return rc;
+    const std::vector<float> tf(th.begin(), th.end()), bf(be.begin(), be.end());  // (f32 handles)
+    const bool f64 = dt == GPAD_DTYPE_F64;
+    HIP_TRY(hipMemcpyAsync(h->theta.p, f64 ? (const void*)th.data() : tf.data(), es * len, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->beta.p, f64 ? (const void*)be.data() : bf.data(), es * len, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    h->sched_len = custom ? 0 : len;  // custom tables are never reused
+    h->sched_kind = h->dims.schedule;
+    h->sched_dtype = dt;
+    return GPAD_OK;
+}
+
+extern "C" {
+
+int gpad_setup(gpad_handle_t h, const gpad_dims_t* d, const void* ML, const void* G, double L) {
+    return gpad::abi_guard("gpad_setup", [&]() -> int {
+        return setup_impl(h, d, ML, G, L, false);
+    });
+}
+
+int gpad_setup_scaled(gpad_handle_t h, const gpad_dims_t* d, const void* MGneg, const void* GL,
+                      double L) {
+    return gpad::abi_guard("gpad_setup_scaled", [&]() -> int {
+        return setup_impl(h, d, MGneg, GL, L, true);
+    });
+}
+
+int gpad_setup_hessian(gpad_handle_t h, const void* H) {
+    return gpad::abi_guard("gpad_setup_hessian", [&]() -> int {
+        if (!h) return fail(GPAD_ERR_INVALID, "gpad_setup_hessian: null handle");
+        if (h->cls) return no_classes("gpad_setup_hessian");
+        if (!h->ready) return fail(GPAD_ERR_NOT_SETUP, "gpad_setup_hessian: call gpad_setup first");
+        if (h->flat) return fail(GPAD_ERR_UNSUPPORTED, "gpad_setup_hessian: not on the flat battery path");
+        h->hess_ok = false;
+        h->hfrag64_ok = false;
+        if (!H) return GPAD_OK;
+        HIP_TRY(hipSetDevice(h->device));
+        const gpad_dims_t& d = h->dims;
+        const int n = d.n, nmats = d.shared ? 1 : d.batch;
+        const size_t es = esize(d.dtype), raw = (size_t)n * n * nmats * es;
+        int rc;
+        if ((rc = h->Hq.ensure(es * (size_t)n * h->ldn * nmats))) return rc;
+        const void* dH = H;
+        DevBuf stage;
+        if (d.memory == GPAD_MEM_HOST) {
+            if ((rc = stage.ensure(raw))) return rc;
+            HIP_TRY(hipMemcpyAsync(stage.p, H, raw, hipMemcpyHostToDevice, h->stream));
+            dH = stage.p;
+        }
+        const long long in_stride = d.shared ? 0 : (long long)n * n, out_stride = (long long)n * h->ldn;
+        if (d.dtype == GPAD_DTYPE_F32)
+            HIP_TRY(gpad::launch_pack_kmajor<float>((const float*)dH, (float*)h->Hq.p, n, n, h->ldn, 1.0, nmats, in_stride,
+                                                    out_stride, h->stream));
+        else
+            HIP_TRY(gpad::launch_pack_kmajor<double>((const double*)dH, (double*)h->Hq.p, n, n, h->ldn, 1.0, nmats,
+                                                     in_stride, out_stride, h->stream));
+        if (h->frag64_ok) {  // shared f64: H for the f64 panels' value branches
+            if ((rc = h->hfrag64.ensure(gpad::panel64_frag_bytes(n, d.m)))) return rc;
+            HIP_TRY(gpad::launch_pack_panel64((const double*)dH, n, n, 1.0, h->frag64_tiles, h->hfrag64.p, h->stream));
+            h->hfrag64_ok = true;
+        }
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        h->hess_ok = true;
+        return GPAD_OK;
+    });
+}
+
+int gpad_setup_flat(gpad_handle_t h, const gpad_dims_t* d, int n_u, const float* MGf, const float* GLf,
+                    double L) {
+    return gpad::abi_guard("gpad_setup_flat", [&]() -> int {
+        if (!h) return fail(GPAD_ERR_INVALID, "gpad_setup_flat: null handle");
+        int rc = validate_dims(d);
+        if (rc) return rc;
+        if (!MGf || !GLf) return fail(GPAD_ERR_INVALID, "gpad_setup_flat: null matrix");
+        if (!(L > 0.0) || !std::isfinite(L)) return fail(GPAD_ERR_INVALID, "gpad_setup_flat: L must be > 0");
+        if (d->dtype != GPAD_DTYPE_F32 || !d->shared)
+            return fail(GPAD_ERR_UNSUPPORTED, "gpad_setup_flat: f32 and shared matrices only");
+        if (n_u <= 0 || d->n % n_u != 0 || d->m < 4 * d->n)
+            return fail(GPAD_ERR_INVALID, "gpad_setup_flat: need n = n_u*N and m >= 4 n_u N");
+        HIP_TRY(hipSetDevice(h->device));
+        unbind_problem(h);
+        h->dims = *d;
+        if (h->dims.check_every <= 0) h->dims.check_every = 10;
+        h->L = L;
+        h->scaled = true;
+        const int Nh = d->n / n_u, m = d->m;
+        const size_t bytes = sizeof(float) * (size_t)Nh * m;
+        h->ldn = round4(d->n);
+        h->ldm = round4(m);
+        if ((rc = h->MGt.ensure(bytes)) || (rc = h->GLt.ensure(bytes))) return rc;
+        const void* dG = GLf;
+        if (d->memory == GPAD_MEM_HOST) {
+            if ((rc = h->stage.ensure(bytes))) return rc;
+            HIP_TRY(hipMemcpyAsync(h->MGt.p, MGf, bytes, hipMemcpyHostToDevice, h->stream));
+            HIP_TRY(hipMemcpyAsync(h->stage.p, GLf, bytes, hipMemcpyHostToDevice, h->stream));
+            dG = h->stage.p;
+        } else {
+            HIP_TRY(hipMemcpyAsync(h->MGt.p, MGf, bytes, hipMemcpyDeviceToDevice, h->stream));
+        }
+        HIP_TRY(gpad::launch_transpose_flat((const float*)dG, (float*)h->GLt.p, m, Nh, h->stream));
+        h->GLx.release();
+        if (gpad::flat_resident_supported(d->n, m, n_u)) {
+            if ((rc = h->GLx.ensure(sizeof(float) * (size_t)d->n * h->ldm))) return rc;
+            HIP_TRY(gpad::launch_expand_flat_gl((const float*)dG, (float*)h->GLx.p, Nh, n_u, m, h->ldm,
+                                                h->stream));
+        }
+        h->frag_ok = false;
+        h->frag_tiles = 0;
+        {  // MFMA panels over the flat data (gpad_flatpanel.hip)
+            const size_t fb = gpad::flatpanel_frag_bytes(d->n, m, n_u);
+            if (fb) {
+                if ((rc = h->frag.ensure(fb))) return rc;
+                HIP_TRY(gpad::launch_pack_flatpanel((const float*)h->MGt.p, (const float*)h->GLt.p, d->n, m, n_u,
+                                                    h->frag.p, h->stream));
+                h->frag_ok = true;
+            }
+        }
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        if (d->memory == GPAD_MEM_HOST && !h->keep_stage) h->stage.release();
+        h->n_u = n_u;
+        h->flat = true;
+        h->ready = true;
+        return GPAD_OK;
+    });
+}
+
+int gpad_schedule(int N, int kind, double* theta, double* beta) {
+    return gpad::abi_guard("gpad_schedule", [&]() -> int {
+        if (N < 0 || !theta || !beta) return fail(GPAD_ERR_INVALID, "gpad_schedule: bad arguments");
+        host_schedule(N, kind, theta, beta);
+        return GPAD_OK;
+    });
+}
+
+int gpad_precompute(gpad_handle_t h, int n, int m, int batch, int shared, int memory, const double* H,
+                    const double* A, const double* f, double* ML, double* gP, double* L) {
+    return gpad::abi_guard("gpad_precompute", [&]() -> int {
+        if (!h) return fail(GPAD_ERR_INVALID, "gpad_precompute: null handle");
+        if (n <= 0 || m < 0 || batch <= 0 || !H || !A || !ML || !L || (f == nullptr) != (gP == nullptr) ||
+            (memory != GPAD_MEM_HOST && memory != GPAD_MEM_DEVICE))
+            return fail(GPAD_ERR_INVALID, "gpad_precompute: bad arguments");
+        HIP_TRY(hipSetDevice(h->device));
+        const bool host = memory == GPAD_MEM_HOST;
+        const int nmat = shared ? 1 : batch;  // eliminations
+        const size_t nH = (size_t)nmat * n * n, nA = (size_t)nmat * m * n, nML = (size_t)nmat * n * m;
+        const size_t nF = f ? (size_t)batch * n : 0;
+        // shared: one elimination of [H | A' | I] gives ML and inv(H); gP = inv(H) f' per row after
+        const int fchunk = shared ? (f ? n : 0) : (f ? 1 : 0);
+        if (!gpad::precompute_supported(n, m, fchunk))
+            return fail(GPAD_ERR_UNSUPPORTED, "gpad_precompute: 2n + m too large for the LDS pivot row");
+        // device views of the operands (host memory: staged copies)
+        DevBuf stage, work;
+        const double *dH = H, *dA = A, *df = f;
+        double *dML = ML, *dgP = gP, *dL = L;
+        const size_t tot = nH + nA + nF + nML + nF + nmat;
+        int rc;
+        if (host) {
+            if ((rc = stage.ensure(sizeof(double) * tot))) return rc;
+            double* b = (double*)stage.p;
+            double* sH = b;
+            double* sA = sH + nH;
+            double* sf = sA + nA;
+            dML = sf + nF;
+            dgP = f ? dML + nML : nullptr;
+            dL = dML + nML + nF;
+            HIP_TRY(hipMemcpyAsync(sH, H, sizeof(double) * nH, hipMemcpyHostToDevice, h->stream));
+            HIP_TRY(hipMemcpyAsync(sA, A, sizeof(double) * nA, hipMemcpyHostToDevice, h->stream));
+            if (f) HIP_TRY(hipMemcpyAsync(sf, f, sizeof(double) * nF, hipMemcpyHostToDevice, h->stream));
+            dH = sH;
+            dA = sA;
+            df = f ? sf : nullptr;
+        }
+        if (shared) {
+            const size_t wb = gpad::precompute_work_bytes(n, m, fchunk, 1);
+            if ((rc = work.ensure(wb + (f ? sizeof(double) * (size_t)n * n : 0)))) return rc;
+            double* Hinv = f ? (double*)((char*)work.p + wb) : nullptr;
+            HIP_TRY(gpad::launch_precompute(n, m, fchunk, dH, 0, dA, 0, nullptr, 0, (double*)work.p, dML, Hinv, dL, 0, 1,
+                                            h->stream));
+            if (f) HIP_TRY(gpad::launch_apply_inv(n, batch, Hinv, df, dgP, h->stream));
+        } else {
+            const size_t per = gpad::precompute_work_bytes(n, m, fchunk, 1);
+            int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)batch, ((size_t)1 << 30) / per));
+            chunk = std::min(chunk, 4 * h->num_cus);
+            if ((rc = work.ensure(per * chunk))) return rc;
+            for (int b0 = 0; b0 < batch; b0 += chunk) {
+                const int cnt = std::min(chunk, batch - b0);
+                HIP_TRY(gpad::launch_precompute(n, m, fchunk, dH, (long long)n * n, dA, (long long)m * n, df, n,
+                                                (double*)work.p, dML, dgP, dL, b0, cnt, h->stream));
+            }
+        }
+        if (host) {
+            HIP_TRY(hipMemcpyAsync(ML, dML, sizeof(double) * nML, hipMemcpyDeviceToHost, h->stream));
+            if (f) HIP_TRY(hipMemcpyAsync(gP, dgP, sizeof(double) * nF, hipMemcpyDeviceToHost, h->stream));
+            HIP_TRY(hipMemcpyAsync(L, dL, sizeof(double) * nmat, hipMemcpyDeviceToHost, h->stream));
+        }
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        return GPAD_OK;
+    });
+}
+
+}  // extern "C"

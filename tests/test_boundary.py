@@ -2,7 +2,7 @@
 dims, stats)`` (include/gpad.h) called directly through ctypes, and by a plain-C caller
 (apps/gpad_main.c --one-shot), against the oracle (bit-exact, iteration counts included).
 
-gpad_solve keeps one handle per thread and device between calls (csrc/gpad_host.cpp): repeated
+gpad_solve keeps one handle per thread and device between calls (csrc/gpad_run.cpp): repeated
 calls with changing shapes, batches, memory kinds and dtypes, and with host matrices rewritten in
 place under the same pointers, must each solve exactly the problem they were given.
 """
@@ -161,7 +161,7 @@ def test_c_app_one_shot_bitexact(gpu, oracle):
 def test_fresh_handle_follows_shape_prior(gpu, oracle):
     """a handle with no plan of its own plans its first phased solve from the
     shape's prior -- the last plan any handle of the process made for the same (n, m, batch, K, N)
-    (csrc/gpad_host.cpp plan_for).  Handle A solves batch 1 (its plan then becomes the prior); a new
+    (csrc/gpad_run.cpp plan_for).  Handle A solves batch 1 (its plan then becomes the prior); a new
     handle B solves batch 2 following that prior: the same phases and survivor counts as A solving
     batch 2 with its own plan (made from the same counts), bit-identical results.  Then the north-star
     gpad_solve, from a freshly created cached handle, equals the oracle on batch 3."""

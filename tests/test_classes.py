@@ -211,13 +211,15 @@ def test_symbols_and_version():
     """The three entry points are declared, exported and defined; the minor is still 6."""
     from gpad_mpc import _lib
     hdr = open(os.path.join(ROOT, "include", "gpad.h")).read()
-    host = open(os.path.join(ROOT, "gpu-dualgradient-mpc_amd", "csrc", "gpad_host.cpp")).read()
+    csrc = os.path.join(ROOT, "gpu-dualgradient-mpc_amd", "csrc")
+    host = open(os.path.join(csrc, "gpad_host.cpp")).read()
+    state = open(os.path.join(csrc, "gpad_state.cpp")).read()  # (the plant and class entry points)
     assert re.search(r"\bint gpad_class_order\(const int\* class_of, int batch, int K, int\* perm, int\* offsets\);", hdr)
     assert re.search(r"\bint gpad_setup_classes\(gpad_handle_t h, const gpad_dims_t\* dims, int K, const int\* class_of,", hdr)
     assert re.search(r"\bint gpad_setup_plant_classes\(gpad_handle_t h, int nx, int nu,", hdr)
     lib = _lib.load()
     for name in ("gpad_class_order", "gpad_setup_classes", "gpad_setup_plant_classes"):
-        assert name in _lib.EXPORTS and name in host
+        assert name in _lib.EXPORTS and name in state
         assert hasattr(lib, name)
     assert int(re.search(r"#define GPAD_VERSION_MINOR (\d+)", hdr).group(1)) == 6 == _lib.VERSION_MINOR
     assert re.search(r'gpad_version\(void\) \{ return "gpad-mi355x 0\.6 ', host)

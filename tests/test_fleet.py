@@ -222,9 +222,10 @@ def test_symbol_and_version():
     assert re.search(r"\bint gpad_setup_plant_batch\(gpad_handle_t h, int nx, int nu,", hdr)
     assert "gpad_setup_plant_batch" in _lib.EXPORTS
     assert int(re.search(r"#define GPAD_VERSION_MINOR (\d+)", hdr).group(1)) == 6 == _lib.VERSION_MINOR
-    host = open(os.path.join(ROOT, "gpu-dualgradient-mpc_amd", "csrc", "gpad_host.cpp")).read()
+    csrc = os.path.join(ROOT, "gpu-dualgradient-mpc_amd", "csrc")
+    host = open(os.path.join(csrc, "gpad_host.cpp")).read()
     assert re.search(r'gpad_version\(void\) \{ return "gpad-mi355x 0\.6 ', host)
-    assert "gpad_setup_plant_batch" in host
+    assert "gpad_setup_plant_batch" in open(os.path.join(csrc, "gpad_state.cpp")).read()
 
 
 def test_equal_capacities_reproduce_battery_plant():

@@ -294,7 +294,7 @@ def test_panel_phase_plan_reuse_bitexact(gpu, oracle, fin):
 def test_async_runs_plan_from_previous_solve(gpu, oracle):
     """Asynchronous solves (device tensors, stats=False) never sync for counts: each phased solve
     copies its counts to pinned host memory behind it and the next run plans from them once they
-    landed (csrc/gpad_host.cpp run_typed).  The plan appears without any stats call, and the
+    landed (csrc/gpad_run.cpp run_typed).  The plan appears without any stats call, and the
     planned solve of a different batch is still exact."""
     import torch
     import gpad_mpc

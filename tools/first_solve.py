@@ -1,5 +1,5 @@
 """A fresh handle's first phased solve: in a warm process where another handle
-has solved the shape, a new handle follows the shape's plan prior (csrc/gpad_host.cpp plan_for)
+has solved the shape, a new handle follows the shape's plan prior (csrc/gpad_run.cpp plan_for)
 instead of the default schedule.  Fresh C4-shard inputs every solve (bench.make_stream):
   A        : 4 solves on one handle (its plans become the shape's prior)
   B first  : a new handle's first solve (prior)            B planned : its next 4 (own plans)
