@@ -14,21 +14,19 @@
 //
 // Fragment images (built by launch_pack_bigpanel): PA1[b][t] = -ML tile t (16 rows), k-block b
 // (b < T2, t < T1); PA2[b][t] = G/L tile t, k-block b (b < T1, t < T2); each a float4 per lane,
-// lane (j, c) holding A[16t + pi(c)][16b + 4q + j] as in gpad_panel.hip.
+// lane (j, c) holding A[16t + pi(c)][16b + 4q + j] as in gpad_panel.h.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <cstdlib>
 
 #include "gpad_internal.h"
+#include "gpad_panel.h"  // (f32x4, as_float4, pi16)
 
 namespace gpad {
 
-typedef float bf32x4 __attribute__((ext_vector_type(4)));
 constexpr int kBigMaxTiles = 64;  // n, m <= 1024 (4 tiles per wave and GEMM)
 constexpr int kBigWaves = 16;
-
-__device__ __forceinline__ int bpi16(int rho) { return 4 * (rho & 3) + (rho >> 2); }
 
 __global__ void pack_bigpanel_kernel(const float* __restrict__ src, int rows, int cols, double scale, int Tr,
                                      int Tk, float4* __restrict__ dst) {
@@ -36,7 +34,7 @@ __global__ void pack_bigpanel_kernel(const float* __restrict__ src, int rows, in
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= Tr * Tk * 64) return;
     const int lane = idx & 63, t = (idx >> 6) % Tr, b = (idx >> 6) / Tr;
-    const int row = 16 * t + bpi16(lane & 15);
+    const int row = 16 * t + pi16(lane & 15);
     float v[4];
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
@@ -83,15 +81,11 @@ hipError_t launch_pack_bigpanel(const float* ML, const float* G, int n, int m, f
     return hipGetLastError();
 }
 
-__device__ __forceinline__ float4 bas_float4(__attribute__((ext_vector_type(4))) unsigned v) {
-    return make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
-}
-
 // acc = sum over k-blocks b < nkb (the last one only its kq 4-steps) of A[b][t] x B[b]:
 // A by buffer loads (byte offset (b * Tr + t) KiB + lane 16 B) two k-blocks ahead, B from LDS
 // one block ahead.  Unrolled by two with fixed register roles and unconditional (clamped) loads
-// so that each block waits only for its own operands (see panel_gemm_rt in gpad_panel.hip).
-__device__ __forceinline__ void big_blk(bf32x4& acc, const float4& a, const float4& b, int steps) {
+// so that each block waits only for its own operands (see panel_gemm_rt in gpad_pair_gemm.h).
+__device__ __forceinline__ void big_blk(f32x4& acc, const float4& a, const float4& b, int steps) {
     __builtin_amdgcn_sched_barrier(0);
     acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, b.x, acc, 0, 0, 0);
     if (steps > 1) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, b.y, acc, 0, 0, 0);
@@ -99,7 +93,7 @@ __device__ __forceinline__ void big_blk(bf32x4& acc, const float4& a, const floa
     if (steps > 3) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, b.w, acc, 0, 0, 0);
     __builtin_amdgcn_sched_barrier(0);
 }
-__device__ __forceinline__ void big_blk2(bf32x4& acc0, bf32x4& acc1, const float4& a, const float4& c,
+__device__ __forceinline__ void big_blk2(f32x4& acc0, f32x4& acc1, const float4& a, const float4& c,
                                          const float4& b, int steps) {
     __builtin_amdgcn_sched_barrier(0);
     acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, b.x, acc0, 0, 0, 0);
@@ -119,12 +113,12 @@ __device__ __forceinline__ void big_blk2(bf32x4& acc0, bf32x4& acc1, const float
     __builtin_amdgcn_sched_barrier(0);
 }
 
-__device__ __forceinline__ bf32x4 big_gemm(__amdgpu_buffer_rsrc_t PA, const float4* B, int t, int Tr, int nkb,
+__device__ __forceinline__ f32x4 big_gemm(__amdgpu_buffer_rsrc_t PA, const float4* B, int t, int Tr, int nkb,
                                            int kq, int lane) {
-    bf32x4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
+    f32x4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
     const int voff = t * 1024 + lane * 16, stride = Tr * 1024, last = nkb - 1;
     auto lda = [&](int kb) -> float4 {
-        return bas_float4(__builtin_amdgcn_raw_buffer_load_b128(PA, voff, (kb < last ? kb : last) * stride, 0));
+        return as_float4(__builtin_amdgcn_raw_buffer_load_b128(PA, voff, (kb < last ? kb : last) * stride, 0));
     };
     float4 a0 = lda(0), a1 = lda(1), b0 = B[lane], b1;
     int kb = 0;  // pairs of full blocks, then the rest (the last block with its kq steps)
@@ -150,12 +144,12 @@ __device__ __forceinline__ bf32x4 big_gemm(__amdgpu_buffer_rsrc_t PA, const floa
 // two row tiles t0, t1 of the same GEMM in one pass: the chains interleave (hiding the 40-cycle
 // MFMA dependency of each other) and share every B fragment (one LDS read for both)
 __device__ __forceinline__ void big_gemm2(__amdgpu_buffer_rsrc_t PA, const float4* B, int t0, int t1, int Tr,
-                                          int nkb, int kq, int lane, bf32x4& acc0, bf32x4& acc1) {
-    acc0 = bf32x4{0.0f, 0.0f, 0.0f, 0.0f};
-    acc1 = bf32x4{0.0f, 0.0f, 0.0f, 0.0f};
+                                          int nkb, int kq, int lane, f32x4& acc0, f32x4& acc1) {
+    acc0 = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+    acc1 = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
     const int v0 = t0 * 1024 + lane * 16, v1 = t1 * 1024 + lane * 16, stride = Tr * 1024, last = nkb - 1;
     auto lda = [&](int voff, int kb) -> float4 {
-        return bas_float4(__builtin_amdgcn_raw_buffer_load_b128(PA, voff, (kb < last ? kb : last) * stride, 0));
+        return as_float4(__builtin_amdgcn_raw_buffer_load_b128(PA, voff, (kb < last ? kb : last) * stride, 0));
     };
     float4 a0 = lda(v0, 0), c0 = lda(v1, 0), a1 = lda(v0, 1), c1 = lda(v1, 1), b0 = B[lane], b1;
     int kb = 0;  // pairs of full blocks, then the rest (the last block with its kq steps)
@@ -260,7 +254,7 @@ __global__ __launch_bounds__(64 * kBigWaves) void gpad_bigpanel_kernel(SolveArgs
             for (int q = 0; q < NT2; ++q) {
                 const int t = w + kBigWaves * q;
                 if (t < T2) {
-                    const bf32x4 cz = big_gemm(PA2, Zh, t, T2, T1, kq2, lane);
+                    const f32x4 cz = big_gemm(PA2, Zh, t, T2, T1, kq2, lane);
 #pragma unroll
                     for (int r = 0; r < 4; ++r) u[q][r] = cz[r];
                 }
@@ -280,7 +274,7 @@ __global__ __launch_bounds__(64 * kBigWaves) void gpad_bigpanel_kernel(SolveArgs
             for (int q = 0; q < NT1; ++q) {
                 const int t = w + kBigWaves * q;
                 if (t < T1) {
-                    const bf32x4 acc = big_gemm(PA1, Wl, t, T1, T2, kq1, lane);
+                    const f32x4 acc = big_gemm(PA1, Wl, t, T1, T2, kq1, lane);
                     float zh[4];
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
@@ -295,12 +289,12 @@ __global__ __launch_bounds__(64 * kBigWaves) void gpad_bigpanel_kernel(SolveArgs
             // ---- GEMM 2 + epilogue: y+ (8d), next w (8a), test partials ----------------------------
             float violz = -INFINITY, violh = -INFINITY, wmin = INFINITY, magh = 0.0f;
             double gap = 0.0;
-            bf32x4 acc_next = {0.0f, 0.0f, 0.0f, 0.0f};
+            f32x4 acc_next = {0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
             for (int q = 0; q < NT2; ++q) {
                 const int t = w + kBigWaves * q;
                 // tiles q, q + 1 of this wave in one interleaved pass (acc of q + 1 kept for the next q)
-                bf32x4 acc;
+                f32x4 acc;
                 constexpr bool kPair = NT2 > 1;
                 if constexpr (kPair) {
                     if ((q & 1) == 0) {
@@ -412,7 +406,7 @@ __global__ __launch_bounds__(64 * kBigWaves) void gpad_bigpanel_kernel(SolveArgs
                     for (int q = 0; q < NT2; ++q) {
                         const int t = w + kBigWaves * q;
                         if (t < T2) {
-                            const bf32x4 cz = big_gemm(PA2, Zh, t, T2, T1, kq2, lane);
+                            const f32x4 cz = big_gemm(PA2, Zh, t, T2, T1, kq2, lane);
                             const float4 p4 = Pd[t * 64 + lane];
                             const float pdq[4] = {p4.x, p4.y, p4.z, p4.w};
 #pragma unroll

@@ -23,10 +23,10 @@
 #include <cstdlib>
 
 #include "gpad_internal.h"
+#include "gpad_panel.h"  // (f32x4, as_float4, pi16)
 
 namespace gpad {
 
-typedef float ff32x4 __attribute__((ext_vector_type(4)));
 constexpr int kFlatPanelWaves = 16;
 constexpr int kFlatPanelWavesMax = 16;
 
@@ -91,8 +91,6 @@ static size_t flatpanel_lds_bytes(const FlatGeom& g, int P) {
     return (size_t)P * g.PB * 1024 + (size_t)P * g.U2 * sizeof(FlatPanelSlot);
 }
 
-__device__ __forceinline__ int fp_pi16(int rho) { return 4 * (rho & 3) + (rho >> 2); }
-
 // A values from the flat data as the setup stores it: MGf row-major Nh x m (sign-folded -ML),
 // GLT t-major Nh x m (GLT[t][r] = GLf[r][t])
 __device__ __forceinline__ float flat_a1(const FlatGeom& g, const float* MGf, int j, int i, int s) {
@@ -115,7 +113,7 @@ __global__ void pack_flatpanel_kernel(FlatGeom g, const float* __restrict__ MGf,
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= g.total) return;
     const int lane = idx & 63;
-    const int rrow = fp_pi16(lane & 15);  // row inside the tile (fragment-order permutation)
+    const int rrow = pi16(lane & 15);  // row inside the tile (fragment-order permutation)
     float v[4];
     if (idx < g.off1c) {  // [n_u][KBc][T1]: the cell blocks of each cell's 8b chains
         const int blk = idx >> 6;
@@ -160,22 +158,18 @@ hipError_t launch_pack_flatpanel(const float* MGf, const float* GLT, int n, int 
     return hipGetLastError();
 }
 
-__device__ __forceinline__ float4 fas_float4(__attribute__((ext_vector_type(4))) unsigned v) {
-    return make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
-}
-
 // one unit's chain over nkb k-blocks (the last only its kq 4-steps): A by buffer loads at byte
 // offset voff + b * stride, two k-blocks in flight; B block b from Ba (b < kbs) or Bb (b >= kbs)
-__device__ __forceinline__ ff32x4 fp_gemm(__amdgpu_buffer_rsrc_t PA, int voff, int stride, int nkb, int kq,
+__device__ __forceinline__ f32x4 fp_gemm(__amdgpu_buffer_rsrc_t PA, int voff, int stride, int nkb, int kq,
                                           const float4* Ba, int kbs, const float4* Bb, int lane) {
-    ff32x4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
-    float4 a0 = fas_float4(__builtin_amdgcn_raw_buffer_load_b128(PA, voff, 0, 0));
-    float4 a1 = nkb > 1 ? fas_float4(__builtin_amdgcn_raw_buffer_load_b128(PA, voff, stride, 0)) : a0;
+    f32x4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
+    float4 a0 = as_float4(__builtin_amdgcn_raw_buffer_load_b128(PA, voff, 0, 0));
+    float4 a1 = nkb > 1 ? as_float4(__builtin_amdgcn_raw_buffer_load_b128(PA, voff, stride, 0)) : a0;
     float4 b0 = kbs > 0 ? Ba[lane] : Bb[lane];
     for (int kb = 0; kb < nkb; ++kb) {
         const float4 ak = a0, bk = b0;
         a0 = a1;
-        if (kb + 2 < nkb) a1 = fas_float4(__builtin_amdgcn_raw_buffer_load_b128(PA, voff, (kb + 2) * stride, 0));
+        if (kb + 2 < nkb) a1 = as_float4(__builtin_amdgcn_raw_buffer_load_b128(PA, voff, (kb + 2) * stride, 0));
         if (kb + 1 < nkb) b0 = kb + 1 < kbs ? Ba[(kb + 1) * 64 + lane] : Bb[(kb + 1 - kbs) * 64 + lane];
         const int steps = kb + 1 < nkb ? 4 : kq;
         __builtin_amdgcn_sched_barrier(0);
@@ -219,7 +213,7 @@ struct FpPre {
 template <bool ALDS>
 __device__ __forceinline__ float4 fp_lda(__amdgpu_buffer_rsrc_t PA, const float4* As, int voff, int off) {
     if constexpr (ALDS) return As[(voff + off) >> 4];
-    else return fas_float4(__builtin_amdgcn_raw_buffer_load_b128(PA, voff, off, 0));
+    else return as_float4(__builtin_amdgcn_raw_buffer_load_b128(PA, voff, off, 0));
 }
 // A block kb of a chain sits at byte offset voff + kb * stride (+ ajump from block akbs on: the
 // 8b chains continue in the shared coupling image)
@@ -240,10 +234,10 @@ __device__ __forceinline__ FpPre fp_pre(__amdgpu_buffer_rsrc_t PA, const float4*
 // the last block): the waitcnt for a block's operands then counts only the loads issued after
 // them, instead of draining the queue at every conditional load or register rotation.
 template <bool ALDS>
-__device__ __forceinline__ ff32x4 fp_chain(__amdgpu_buffer_rsrc_t PA, const float4* As, FpPre f, int voff, int stride,
+__device__ __forceinline__ f32x4 fp_chain(__amdgpu_buffer_rsrc_t PA, const float4* As, FpPre f, int voff, int stride,
                                            int nkb, int kq, const float4* Ba, int kbs, const float4* Bb, int lane,
                                            int akbs = 1 << 30, int ajump = 0) {
-    ff32x4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
+    f32x4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
     const int last = nkb - 1;
     auto ldb = [&](int kb) -> float4 { return kb < kbs ? Ba[kb * 64 + lane] : Bb[(kb - kbs) * 64 + lane]; };
     float4 a0 = f.a0, a1 = f.a1;
@@ -337,7 +331,7 @@ __global__ __launch_bounds__(64 * W, 4) void gpad_flatpanel_kernel(SolveArgs<flo
     const __amdgpu_buffer_rsrc_t PA =
         __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(a.frag), 0, g.total * 16, 0x00020000);
     const bool use_tol = a.tol > 0.0;
-    // phased compaction (as gpad_panel.hip): a phase runs iterations [v_begin, v_end) over the
+    // phased compaction (as gpad_panel.hip; the phase loop is gpad_phases.cpp): a phase runs iterations [v_begin, v_end) over the
     // instances idx_in[0 .. *count_in) (null: all), parks the survivors and lists them
     const bool fresh = a.v_begin == 0;
     const bool carry = a.v_end < N;
@@ -433,7 +427,7 @@ __global__ __launch_bounds__(64 * W, 4) void gpad_flatpanel_kernel(SolveArgs<flo
                     const float4* L = fp_lds + x.pp * PBf;
                     const int voff = fp_voff2(g, x, lane), stride = (cp ? g.KBe : g.KBc) * 1024;
                     const int nkb = cp ? g.KB3 : g.T1;
-                    const ff32x4 cz = fp_chain<ALDS>(PA, As, fp_pre<ALDS>(PA, As, voff, stride, nkb), voff, stride, nkb,
+                    const f32x4 cz = fp_chain<ALDS>(PA, As, fp_pre<ALDS>(PA, As, voff, stride, nkb), voff, stride, nkb,
                                                cp ? g.kq3 : g.kq2, cp ? L + oZn : L + oZc + x.cell * g.T1 * 64,
                                                nkb, L + oZn, lane);
 #pragma unroll
@@ -467,7 +461,7 @@ __global__ __launch_bounds__(64 * W, 4) void gpad_flatpanel_kernel(SolveArgs<flo
                     const int voff = fp_voff1(g, x, lane);
                     const int ajump = fp_ajump1(g, x);
                     const FpPre f = q == 0 ? pre1 : fp_pre<ALDS>(PA, As, voff, g.T1 * 1024, g.KB1, g.KBc, ajump);
-                    const ff32x4 acc = fp_chain<ALDS>(PA, As, f, voff, g.T1 * 1024, g.KB1, g.kq1, L + x.j * g.KBc * 64, g.KBc,
+                    const f32x4 acc = fp_chain<ALDS>(PA, As, f, voff, g.T1 * 1024, g.KB1, g.kq1, L + x.j * g.KBc * 64, g.KBc,
                                                       L + oWe, lane, g.KBc, ajump);
                     float zh[4];
 #pragma unroll
@@ -504,7 +498,7 @@ __global__ __launch_bounds__(64 * W, 4) void gpad_flatpanel_kernel(SolveArgs<flo
                     const int voff = fp_voff2(g, x, lane), stride = (cp ? g.KBe : g.KBc) * 1024;
                     const int nkb = cp ? g.KB3 : g.T1;
                     const FpPre f = q == 0 ? pre2 : fp_pre<ALDS>(PA, As, voff, stride, nkb);
-                    const ff32x4 acc = fp_chain<ALDS>(PA, As, f, voff, stride, nkb, cp ? g.kq3 : g.kq2,
+                    const f32x4 acc = fp_chain<ALDS>(PA, As, f, voff, stride, nkb, cp ? g.kq3 : g.kq2,
                                                 cp ? L + oZn : L + oZc + x.cell * g.T1 * 64, nkb, L + oZn, lane);
                     float4* wp = L + (cp ? oWe + x.t * 64 : (x.cell * g.KBc + x.t) * 64) + lane;
                     const float4 w4 = *wp;
@@ -623,7 +617,7 @@ __global__ __launch_bounds__(64 * W, 4) void gpad_flatpanel_kernel(SolveArgs<flo
                             const float4* L = fp_lds + x.pp * PBf;
                             const int voff = fp_voff2(g, x, lane), stride = (cp ? g.KBe : g.KBc) * 1024;
                             const int nkb = cp ? g.KB3 : g.T1;
-                            const ff32x4 cz = fp_chain<ALDS>(PA, As, fp_pre<ALDS>(PA, As, voff, stride, nkb), voff,
+                            const f32x4 cz = fp_chain<ALDS>(PA, As, fp_pre<ALDS>(PA, As, voff, stride, nkb), voff,
                                                              stride, nkb, cp ? g.kq3 : g.kq2,
                                                              cp ? L + oZn : L + oZc + x.cell * g.T1 * 64, nkb,
                                                              L + oZn, lane);
@@ -823,7 +817,8 @@ static hipError_t launch_flatpanel_w8(const SolveArgs<float>& a, FlatGeom g, int
 // are sized for a.batch, extra workgroups find no group); a.frag = the flat fragment images.
 // P panels per workgroup: as many as keep every CU busy (groups >= CUs), the phase-1 units within
 // one per wave and the phase-2 units within 4 per wave, and the LDS within 160 KiB.
-static hipError_t launch_flatpanel_once(const SolveArgs<float>& a, hipStream_t s) {
+// (the phase loop over such launches is gpad_phases.cpp launch_flatpanel)
+hipError_t launch_flatpanel_once(const SolveArgs<float>& a, hipStream_t s) {
     if (!flatpanel_supported(a.n, a.m, a.n_u) || !a.frag) return hipErrorInvalidValue;
     FlatGeom g = flat_geom(a.n, a.m, a.n_u);
     const int panels = (a.batch + 15) / 16;
@@ -878,61 +873,6 @@ static hipError_t launch_flatpanel_once(const SolveArgs<float>& a, hipStream_t s
         default: return launch_fp_nt<4, 4>(a, g, lds, alds, grid, s);
     }
 #undef FP_CASE
-}
-
-// Phase schedule of a phased flat solve: 2K iterations, then a quarter of the iterations done so
-// far (rounded to the test period K), so phases stay short while most columns are alive and grow
-// geometrically in a long tail (O(log N) launches); past the previous solve's last iteration
-// (v_pred) one phase runs to N, so an unused tail costs no empty launches.  Estimated on battery
-// tol-mode batches of 8192: column utilisation ~0.9-0.96 vs 0.61-0.70 in one launch.
-int flat_phase_len(int v0, int check_every, const Tuning* t) {
-    const int K = check_every > 0 ? check_every : 10;
-    const int base = (t && t->phase_len > 0) ? t->phase_len : 2 * K;
-    const int grow = (v0 / 4) / K * K;
-    return grow > base ? grow : base;
-}
-
-hipError_t launch_flatpanel(const SolveArgs<float>& a0, hipStream_t s) {
-    if (!flatpanel_supported(a0.n, a0.m, a0.n_u) || !a0.frag) return hipErrorInvalidValue;
-    SolveArgs<float> a = a0;
-    const Tuning tn = a.tune ? *a.tune : Tuning{};
-    a.v_begin = 0;
-    a.v_end = a.N;
-    a.idx_in = nullptr;
-    a.count_in = nullptr;
-    // phases pay when the batch is several resident rounds of groups (the time of a resident round
-    // is its slowest column either way; compaction shortens the queue of rounds): measured on
-    // battery packs, eps mode, phased vs one launch -- C1 8192: 1.91 vs 1.63 ms, 65536: 8.8 vs
-    // 10.0 ms; N = 50 4096: 25.1 vs 23.9 ms, 16384: 67.7 vs 87.2 ms (profiles/r02_flat_phased.txt).
-    // GPAD_OPT_PHASED: 0 never, 1 (default) from 4 panels per CU, 2 always.
-    const int panels = (a.batch + 15) / 16;
-    const bool phased = a.tol > 0.0 && a.pwork != nullptr &&
-                        (tn.phased == 2 || (tn.phased == 1 && panels >= 4 * a.num_cus));
-    if (!phased) return launch_flatpanel_once(a, s);
-    // workspace as the panel path's (panel_work_bytes): idx ping-pong, phase counts, carried w, u
-    int* idx0 = reinterpret_cast<int*>(a.pwork);
-    int* idx1 = idx0 + a.batch;
-    int* counts = idx1 + a.batch;
-    float* wc = reinterpret_cast<float*>(counts + 2 * kPanelMaxPhases);
-    a.wc = wc;
-    a.uc = wc + (size_t)a.batch * a.m;
-    hipError_t e = hipMemsetAsync(counts, 0, sizeof(int) * kPanelMaxPhases, s);
-    if (e != hipSuccess) return e;
-    int v0 = 0;
-    for (int ph = 0; v0 < a.N; ++ph) {
-        int plen = ph >= kPanelMaxPhases - 1 ? a.N : flat_phase_len(v0, a.check_every, &tn);
-        if (a0.v_pred > 0 && v0 >= a0.v_pred) plen = a.N;  // beyond the prediction: one last phase
-        const int v1 = (a.N - v0 <= plen) ? a.N : v0 + plen;
-        a.v_begin = v0;
-        a.v_end = v1;
-        a.idx_in = ph ? ((ph & 1) ? idx0 : idx1) : nullptr;
-        a.count_in = ph ? counts + ph - 1 : nullptr;
-        a.idx_out = (ph & 1) ? idx1 : idx0;
-        a.count_out = counts + ph;
-        if ((e = launch_flatpanel_once(a, s)) != hipSuccess) return e;
-        v0 = v1;
-    }
-    return hipSuccess;
 }
 
 }  // namespace gpad

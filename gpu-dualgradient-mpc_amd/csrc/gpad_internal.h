@@ -1,5 +1,5 @@
 // gpad_internal.h -- device-side argument blocks and kernel launchers shared by the
-// HIP kernels (gpad_kernels.hip, gpad_panel.hip) and the host runtime (gpad_host.h and its units).
+// HIP kernels (gpad_kernels.hip, the panel units, ...) and the host runtime (gpad_host.h and its units).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -41,7 +41,7 @@ struct Tuning {
 
 // Device error word of a run (SolveArgs::err): kernels OR these bits in with a vector atomic;
 // the host turns a non-zero word into GPAD_ERR_DEVICE when it collects or syncs the run.
-constexpr int kDevErrHandoff = 1;  // a chain hand-off wait expired (gpad_panel.hip handoff_wait)
+constexpr int kDevErrHandoff = 1;  // a chain hand-off wait expired (gpad_pairs.h handoff_wait)
 // SolveArgs::debug bits (fault injection for tests; 0 in production)
 constexpr int kDebugDropHandoff = 1;  // the first hand-off helper skips its first post
 
@@ -81,7 +81,7 @@ struct SolveArgs {
     const T* GLt;          // G/L, k-major: [n][ldm]
     long long strideA;     // elements between consecutive instances' -ML images (0 = shared)
     long long strideB;     // elements between consecutive instances' G/L images (0 = shared)
-    const void* frag;      // panel kernel: fragment-packed matrices (see gpad_panel.hip)
+    const void* frag;      // panel kernel: fragment-packed matrices (see gpad_panel.h)
     int frag_tiles;        // tile count the fragment image was packed for
     const T* gP;           // per-instance H^-1 q, [batch][ld_gP]
     const T* g;            // per-instance rhs,    [batch][ld_g]
@@ -98,7 +98,7 @@ struct SolveArgs {
     int* iters;            // [batch] iterations executed
     int* conv;             // [batch] 0 = not converged, 1 = test (A) passed, 2 = test (B) passed
     int num_cus;           // compute units of the device (persistent-grid sizing)
-    // panel kernel, phased compaction (set by launch_panel; see gpad_panel.hip)
+    // panel kernel, phased compaction (set by launch_panel; see gpad_phases.cpp)
     void* pwork;           // workspace of panel_work_bytes(m, batch) bytes, or null (one phase)
     int v_begin, v_end;    // iterations [v_begin, v_end) of this phase
     int v_pred;            // flat panels: predicted last iteration (previous solve), 0 = unknown
@@ -194,7 +194,6 @@ bool loop_panel_supported(int n, int m, int nx, int nu);
 int loop_panel_grid(int n, int m, int batch, int num_cus, const Tuning* t);
 // persistent grid of `grid` <= min(ceil(batch / 16), kAbsmaxMaxBlocks) workgroups
 hipError_t launch_loop_panel(const LoopArgs& a, int grid, hipStream_t s);
-hipError_t launch_panel(const SolveArgs<float>& a, hipStream_t s, bool* supported);
 // f64 panels on the f64 MFMA pipe (gpad_panel64.hip): shared matrices, n, m <= 256, one panel of 16
 // instances per workgroup, value-function branches when a.hfrag64 is set; a.frag = the -ML | G_L
 // images of launch_pack_panel64, a.frag_tiles = panel64_tiles(n, m)
@@ -203,8 +202,6 @@ int panel64_tiles(int n, int m);
 size_t panel64_frag_bytes(int n, int m);  // one T x T operand image
 hipError_t launch_pack_panel64(const double* src, int rows, int cols, double scale, int T, void* dst, hipStream_t s);
 hipError_t launch_panel64(const SolveArgs<double>& a, hipStream_t s);
-// launch_panel at (n, m) runs the panel pairs, which fold max |g| into their loads (gmax_part)
-bool panel_folds_gmax(int n, int m);
 
 // Phase end of a panel kernel: list panel P's parked columns.  Called by the wave that speaks for
 // the panel, whose lanes 0..15 (j == 0) hold columns 0..15; `park`: this lane's column carries
@@ -241,15 +238,14 @@ __device__ __forceinline__ void list_survivors(const Args& a, int P, bool park, 
         if (park && j == 0) a.idx_out[base + rank] = inst;
     }
 }
-// the boundary before phase ph >= 1: the survivors phase ph - 1 listed per panel (seg_cnt / seg_idx)
-// -> idx_out[0 .. *count_out), optionally ordered longest-predicted-first (pred: the previous
-// solve's counts, when the list is the finisher's: count <= fin_cur).  count_prev / fin_prev:
-// phase ph - 1's own input count and finisher threshold (count_prev <= fin_prev: the finisher
-// took that list and the panel phase listed nothing).
-hipError_t launch_phase_compact(const int* seg_cnt, const int* seg_idx, const int* count_prev, int batch,
-                                int fin_prev, int* idx_out, int* count_out, const int* pred, int fin_cur,
-                                hipStream_t s);
-size_t panel_frag_bytes(int n, int m, int batch);
+// ---- the f32 MFMA panels of shared-matrix batches, by unit (layout and shape rules: gpad_panel.h) ----
+// gpad_phases.cpp (host only): the phase schedule, the planner, the workspace and the phase loops.
+// launch_panel: every launch of a solve -- one phase, or with tol > 0 and a.pwork the phases with
+// their boundaries and finisher; *supported false (and nothing launched): no fragment image for
+// this geometry
+hipError_t launch_panel(const SolveArgs<float>& a, hipStream_t s, bool* supported);
+// launch_panel at (n, m) runs the panel pairs, which fold max |g| into their loads (gmax_part)
+bool panel_folds_gmax(int n, int m);
 size_t panel_work_bytes(int m, int batch);
 int panel_phase_len(int check_every, const Tuning* t);
 int panel_fin_thresh(int n, int m, int num_cus, const Tuning* t);
@@ -264,15 +260,29 @@ struct PanelPlan {
 };
 int panel_plan(const int* iters, int batch, int n, int m, int N, int check_every, int num_cus, const Tuning* t,
                PanelPlan* out);
+// gpad_panel.hip: the fragment packer, the size helpers (big panels included) and one phase launch
+// of the T-wave kernel, T = 1..8
+size_t panel_frag_bytes(int n, int m, int batch);
 int panel_tiles(int n, int m, int batch);
+hipError_t launch_pack_panel(const float* ML, const float* G, int n, int m, int batch, float mg_sign,
+                             double g_scale, void* frag, hipStream_t s);
+hipError_t launch_panel_single(int T, const SolveArgs<float>& a, int grid, hipStream_t s);
+// gpad_pairs.hip: one phase launch of the pair / relay kernel, T = 9..16 (picks the KQ / DROP instantiation)
+hipError_t launch_panel_pairs(int T, const SolveArgs<float>& a, int grid, hipStream_t s);
+// gpad_compact.hip: the boundary before phase ph >= 1: the survivors phase ph - 1 listed per panel
+// (seg_cnt / seg_idx) -> idx_out[0 .. *count_out), optionally ordered longest-predicted-first (pred:
+// the previous solve's counts, when the list is the finisher's: count <= fin_cur).  count_prev /
+// fin_prev: phase ph - 1's own input count and finisher threshold (count_prev <= fin_prev: the
+// finisher took that list and the panel phase listed nothing).
+hipError_t launch_phase_compact(const int* seg_cnt, const int* seg_idx, const int* count_prev, int batch,
+                                int fin_prev, int* idx_out, int* count_out, const int* pred, int fin_cur,
+                                hipStream_t s);
 // gpad_bigpanel.hip: shared f32 matrices with n or m in (256, 1024]
 bool bigpanel_supported(int n, int m);
 size_t bigpanel_frag_bytes(int n, int m);
 hipError_t launch_pack_bigpanel(const float* ML, const float* G, int n, int m, float mg_sign, double g_scale,
                                 void* frag, hipStream_t s);
 hipError_t launch_bigpanel(const SolveArgs<float>& a, int grid, hipStream_t s);
-hipError_t launch_pack_panel(const float* ML, const float* G, int n, int m, int batch, float mg_sign,
-                             double g_scale, void* frag, hipStream_t s);
 
 // layout: out[k*ld + i] = (T)(scale * in[i*cols + k]) for i < rows, k < cols; zero pad i >= rows
 template <typename T>
@@ -335,7 +345,10 @@ bool flatpanel_supported(int n, int m, int n_u);
 size_t flatpanel_frag_bytes(int n, int m, int n_u);
 hipError_t launch_pack_flatpanel(const float* MGf, const float* GLT, int n, int m, int n_u, void* frag,
                                  hipStream_t s);
-// tol > 0 with a.pwork (panel_work_bytes): phased compaction, phases of flat_phase_len iterations
+// one launch over a.batch instances or over the phase's list (a.idx_in / a.count_in)
+hipError_t launch_flatpanel_once(const SolveArgs<float>& a, hipStream_t s);
+// gpad_phases.cpp: the solve -- tol > 0 with a.pwork (panel_work_bytes): phased compaction, phases of
+// flat_phase_len iterations, each a launch_flatpanel_once
 hipError_t launch_flatpanel(const SolveArgs<float>& a, hipStream_t s);
 int flat_phase_len(int v0, int check_every, const Tuning* t);
 // flat G_L (m x Nh) -> full k-major image out[k*ld + r] (k < n), zero off the structure

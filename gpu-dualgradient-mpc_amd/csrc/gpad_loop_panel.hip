@@ -21,7 +21,7 @@
 // iteration counter v and the iteration limit falls on an event; with fixed N all columns of a
 // workgroup start together and reach N together.
 //
-// panel_gemm, the vector typedefs and PanelSlot are gpad_panel.h's, shared with gpad_panel.hip.
+// panel_gemm, the vector typedefs, PanelSlot and the shape rules are gpad_panel.h's, shared with gpad_panel.hip.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -59,7 +59,7 @@ constexpr int kLpTabMax = 32 * 1024;  // (static + dynamic LDS of the T = 16 ker
 // words of dynamic LDS before the schedule tables: x rows [2][16][nxa], u rows [16][nu]
 __host__ __device__ inline int lp_state_words(int nxa, int nu) { return 32 * nxa + 16 * nu; }
 // the schedule tables (theta | beta, N + 2 words each) go to LDS when they leave the workgroups of
-// a CU resident: 32 / T workgroups for T <= 8, one above (launch_panel_t's figure)
+// a CU resident: 32 / T workgroups for T <= 8, one above (gpad_panel.h panel_resident_grid's figure)
 template <int T>
 __host__ __device__ inline bool lp_tab_in_lds(int N, int nxa, int nu) {
     const long long tab = 8ll * ((long long)N + 2);
@@ -444,21 +444,14 @@ __global__ __launch_bounds__(64 * T) void gpad_loop_panel_kernel(LoopArgs la) {
 }
 
 // ---- host side --------------------------------------------------------------------------------
-static int lp_tiles(int n, int m) {
-    const int t = ((n > m ? n : m) + 15) / 16;
-    return t >= 1 && t <= 16 ? t : 0;
-}
-
 bool loop_panel_supported(int n, int m, int nx, int nu) {
-    return n >= 1 && m >= 1 && lp_tiles(n, m) != 0 && nx >= 1 && nx <= kLoopMaxState && nu >= 1 &&
+    return n >= 1 && m >= 1 && panel_tiles_for(n, m) != 0 && nx >= 1 && nx <= kLoopMaxState && nu >= 1 &&
            nu <= kLoopMaxState && nu <= n;
 }
 
 int loop_panel_grid(int n, int m, int batch, int num_cus, const Tuning* tn) {
-    // resident workgroups, as launch_panel_t: 32 / T per CU for T <= 8, one above
-    const int T = lp_tiles(n, m);
     const int panels = (batch + 15) / 16;
-    const int resident = T > 8 ? num_cus : num_cus * (32 / (T ? T : 1));
+    const int resident = panel_resident_grid(panel_tiles_for(n, m), num_cus);
     int grid = panels < resident ? panels : resident;
     if (tn && tn->panel_max_grid > 0 && tn->panel_max_grid < grid) grid = tn->panel_max_grid;
     if (grid > kAbsmaxMaxBlocks) grid = kAbsmaxMaxBlocks;
@@ -477,7 +470,7 @@ static hipError_t launch_loop_panel_t(const LoopArgs& a, int grid, hipStream_t s
 
 hipError_t launch_loop_panel(const LoopArgs& a, int grid, hipStream_t st) {
     const SolveArgs<float>& s = a.s;
-    const int T = lp_tiles(s.n, s.m);
+    const int T = panel_tiles_for(s.n, s.m);
     if (!T || !s.frag || s.frag_tiles != T || s.strideA || s.strideB ||
         !loop_panel_supported(s.n, s.m, a.nx + a.ns, a.nu) || a.nx < 1 || a.ns < 0 || (a.ns && !a.S) || !s.qctr ||
         s.N < 1 || a.steps < 1 || s.batch < 1 || s.check_every < 1 || (s.tol > 0.0 && s.N % s.check_every != 0) ||

@@ -1,15 +1,74 @@
-// gpad_panel.h -- the pieces of the T-wave f32 MFMA panel shared by gpad_panel.hip (gpad_panel_kernel:
-// a batch of independent solves) and gpad_loop_panel.hip (gpad_loop_panel_kernel: a queue of
-// closed-loop packs): the vector types, the per-tile slots of the Algorithm-1 test and the skinny
-// GEMM.  Both kernels run exactly this panel_gemm per (row tile, column), so their MFMA chains
-// cannot drift apart.  The fragment layout is described at the top of gpad_panel.hip.
+// gpad_panel.h -- what every f32 MFMA panel unit shares (gfx950): the fragment layout, the vector
+// types, the tile row permutation, the per-tile slots of the Algorithm-1 test, the skinny GEMM of the
+// T-wave panel, and the host-side shape rules (tile count, resident grid, hand-off shapes).
+// Included by gpad_panel.hip (gpad_panel_kernel: a batch of independent solves, T <= 8), gpad_pairs.hip
+// (panel pairs, 8 < T <= 16), gpad_loop_panel.hip (a queue of closed-loop packs), gpad_bigpanel.hip,
+// gpad_flatpanel.hip and the host phase driver gpad_phases.cpp.  gpad_panel_kernel and
+// gpad_loop_panel_kernel run exactly this panel_gemm per (row tile, column), so their MFMA chains
+// cannot drift apart.
+//
+// Shared-matrix batches on the f32 MFMA pipe.  When every instance of a batch shares ML and G (one
+// plant, many states: the battery scenario batch), the two mat-vecs of a GPAD iteration over 16
+// instances are two skinny GEMMs:  Zhat[n x 16] = (-ML) W[m x 16]  and  Y'[m x 16] = G_L Zhat[n x 16].
+// One workgroup owns a panel of 16 instances for the whole solve (no inter-workgroup traffic at all).
+// Both GEMMs are padded to T tiles of 16 rows (T = ceil(max(n, m)/16)) and the workgroup has
+// T waves: wave t owns row tile t of BOTH GEMMs (one 4-register accumulator each), so every
+// per-row quantity (z, y, u = G_L z, g_P, p_D) of the panel lives in registers, and W / Zhat
+// are exchanged through LDS.  Many waves per SIMD hide the 40-cycle MFMA dependency and
+// overlap one wave's epilogue with another wave's MFMAs.
+//
+// MFMA: v_mfma_f32_16x16x4_f32 (f32 in, f32 accumulate).  Lane l holds A[l&15][k=l>>4],
+// B[k=l>>4][l&15] and C/D rows 4(l>>4)+r, column l&15 (r = 0..3).  Its result is bit-for-bit
+// a k-ordered fmaf chain, so accumulating k-steps in ascending order reproduces the
+// reference's sequential `sum += a*b` exactly (seq_functions.cpp:61,82).
+//
+// Row permutation pi(rho) = 4(rho&3) + (rho>>2) inside every 16-row tile of the packed A
+// operands makes accumulator register r of lane (j = l>>4, c = l&15) hold original row
+// 16t + 4r + j -- which is exactly the B-operand fragment of k-step 4t + r of the NEXT GEMM.
+// So W and Zhat live in LDS in "fragment order" [tile][lane][4]: a ds_read_b128 per 16-k block
+// yields the four B registers, with no transposes and no bank conflicts.
+//
+// Packed operands in HBM/L2 (built once by pack_panel_kernel at setup; T x T tiles each):
+//   PA1[b][t][lane][q] = -ML[16t + pi(lane&15)][16b + 4q + (lane>>4)]   (b < TM, t < TN)
+//   PA2[b][t][lane][q] = G_L[16t + pi(lane&15)][16b + 4q + (lane>>4)]   (b < TN, t < TM)
+// one float4 per lane per (block, tile): 1 KiB per wave-instruction, fully coalesced.
 #pragma once
 
 #include <hip/hip_runtime.h>
 
 namespace gpad {
 
+// ---- host-side shape rules ---------------------------------------------------------------------
+constexpr int kPanelMaxTiles = 16;  // n, m <= 256 (1024-thread workgroups)
+
+// T = ceil(max(n, m) / 16) when the T-wave / pair kernels take the shape, else 0
+inline int panel_tiles_for(int n, int m) {
+    const int t = ((n > m ? n : m) + 15) / 16;
+    return t >= 1 && t <= kPanelMaxTiles ? t : 0;
+}
+
+// Resident workgroups of a panel grid: a panel-pair workgroup (T > 8) or a big-panel one (T = 0)
+// fills a CU; T-wave panels (T <= 8) share one, 32 / T of them.
+inline int panel_resident_grid(int T, int num_cus) { return (T < 1 || T > 8) ? num_cus : num_cus * (32 / T); }
+
+// The chain hand-off shapes of the panel pairs (gpad_pairs.h Handoff): T = 9, 11, 13 with full-length
+// chains on every tile of both GEMMs, i.e. both dimensions in (16 (T - 1), 16 T].
+inline bool panel_handoff_shape(int T, int n, int m) {
+    return (T == 9 || T == 11 || T == 13) && n > 16 * (T - 1) && m > 16 * (T - 1) && (n + 15) / 16 == T &&
+           (m + 15) / 16 == T;
+}
+
+// ---- device pieces -----------------------------------------------------------------------------
 typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+
+__device__ __forceinline__ int pi16(int rho) { return 4 * (rho & 3) + (rho >> 2); }
+
+// the 128-bit buffer load's result as the four floats it holds
+__device__ __forceinline__ float4 as_float4(u32x4 v) {
+    return make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z),
+                       __uint_as_float(v.w));
+}
 
 struct PanelSlot {  // per wave (row tile), per instance partials of the Algorithm-1 test
     float violz[16], violh[16], wmin[16];
@@ -23,13 +82,6 @@ struct PanelSlot {  // per wave (row tile), per instance partials of the Algorit
 // The MFMA k-order is ascending (block 0..T-1, step 0..3), i.e. the reference's sequential chain.
 // A is read with buffer loads: one 32-bit lane offset (t*1 KiB + lane*16 B) in a VGPR and the
 // k-block offset as a compile-time scalar, so the unrolled blocks cost no address registers.
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ float4 as_float4(u32x4 v) {
-    return make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z),
-                       __uint_as_float(v.w));
-}
-
 template <int T>
 __device__ __forceinline__ f32x4 panel_gemm(__amdgpu_buffer_rsrc_t PA, const float* Bl, int voff,
                                             int lane) {

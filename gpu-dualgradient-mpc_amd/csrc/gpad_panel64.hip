@@ -144,7 +144,7 @@ __device__ __forceinline__ void chain64(__amdgpu_buffer_rsrc_t PA, const f64x4* 
 // previous one parked in LDS (bit-identical: the same ascending-k MFMA sequence).  T = 13: SIMD
 // loads 52,39,39,39 k-blocks -> 43,42,42,42.  Roles are dealt from the last wave down (the SIMD
 // issues MFMAs oldest wave first), so the sequential relay runs on the oldest waves, at raised
-// priority, as in the f32 one-panel relay (gpad_panel.hip Handoff).  Relay waves own a phantom
+// priority, as in the f32 one-panel relay (gpad_pairs.h Handoff).  Relay waves own a phantom
 // tile T (no rows) everywhere else, so they follow the workgroup's control flow and barriers
 // without touching the real tiles' state.
 template <int T>
@@ -187,7 +187,7 @@ struct P64Hand {
     int herr;                       // relay: a wait expired (reported at exit, GPAD_ERR_DEVICE)
 };
 
-// bounded wait for a parked accumulator (as gpad_panel.hip handoff_wait: an expired wait is
+// bounded wait for a parked accumulator (as gpad_pairs.h handoff_wait: an expired wait is
 // recorded and fails the run rather than hanging the GPU or returning stale results)
 template <class Lds>
 __device__ __forceinline__ f64x4 p64_wait(Lds& L, int slot, int gen, int lane) {

@@ -148,7 +148,7 @@ def test_product_path_has_no_oracle_dependency():
 
 
 def test_phase_planner_host_only():
-    """gpad_plan_phases (the panel solver's phase planner, csrc/gpad_panel.hip panel_plan) on
+    """gpad_plan_phases (the panel solver's phase planner, csrc/gpad_phases.cpp panel_plan) on
     synthetic survival curves: ends strictly increasing and closing at N, takeover threshold
     covering the previous solve's survivors, and the degenerate inputs."""
     from gpad_mpc.solver import GpadSolver

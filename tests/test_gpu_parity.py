@@ -181,7 +181,7 @@ def test_panel_phased_compaction_bitexact(gpu, oracle, grid, phase, fin, tol, N,
     """Phased compaction + grid-stride panels (+ panel pairs for T > 8 when panels outnumber
     workgroups) + the resident finisher for the tail (fin = its threshold; 0 disables it);
     n, m in (192, 208], (160, 176] and (128, 144] run the panel pairs' chain hand-off (T = 13, 11,
-    9, gpad_panel.hip Handoff; one-panel relays at T = 13, 9) with the receiver's last k-block at
+    9, gpad_pairs.h Handoff; one-panel relays at T = 13, 9) with the receiver's last k-block at
     every kq:
     survivors of each phase are re-packed into new panels (different columns, workgroups,
     pairs and phases) or finished one per workgroup; every instance must still match its own
@@ -260,7 +260,7 @@ def test_finisher_queue_bitexact(gpu, oracle, grid, nm, B, z0s):
 
 @pytest.mark.parametrize("fin", [None, 0])
 def test_panel_phase_plan_reuse_bitexact(gpu, oracle, fin):
-    """A handle plans its phases from the previous solve's iteration counts (csrc/gpad_panel.hip
+    """A handle plans its phases from the previous solve's iteration counts (csrc/gpad_phases.cpp
     panel_plan); a later solve that needs more (or fewer) iterations than the plan expects must
     still be exact -- the plan moves launch boundaries and the finisher takeover only."""
     import gpad_mpc

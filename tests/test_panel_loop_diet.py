@@ -1,4 +1,4 @@
-"""The panel-pair solve loop (gpad_panel.hip panel2_run) against the f32 oracle, bit for bit.
+"""The panel-pair solve loop (gpad_pairs.h panel2_run) against the f32 oracle, bit for bit.
 
 The loop's epilogues are scheduled for the fewest vector instructions beside the MFMA chains
 (the schedule load, the splats, the stage order of 8d / 8a, the u recursion and the test's

@@ -23,7 +23,7 @@ option that selects the variant):
 
 * gpad_kernels.hip stream (f32 and f64): test_seed[*-stream], test_seed_f64 ("stream");
   resident: test_seed[*-resident] ("resident");
-* gpad_panel.hip small panels (T <= 8): test_seed[37x53-panel]; panel pairs (T > 8), one panel per
+* gpad_panel.hip small panels (T <= 8): test_seed[37x53-panel]; gpad_pairs.hip panel pairs (T > 8), one panel per
   workgroup: test_seed[*-panel-onepanel]; pair layout (panel_max_grid = 2 for three panels):
   test_seed[*-panel-pair] and test_seed_mixed_batches, whose case (iii) depends on the per-wave znz
   flags being combined ("panel");

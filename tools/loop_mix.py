@@ -3,7 +3,7 @@
 
   python3 tools/loop_mix.py [--kernel 'gpad_panel2_kernel<13, 2, false>'] [--asm FILE] [-v]
 
-Compiles csrc/gpad_panel.hip to gfx950 assembly (hipcc --cuda-device-only -S; --asm reads an
+Compiles csrc/gpad_pairs.hip to gfx950 assembly (hipcc --cuda-device-only -S; --asm reads an
 assembly file made earlier instead), takes one kernel, and finds its loops: a label that a later
 branch jumps back to opens a loop body, the last such branch closes it.  A solve loop is the
 innermost loop that holds both MFMAs and workgroup barriers; there is one per wave role, in the
@@ -80,7 +80,7 @@ def mangled(kernel: str) -> str:
 def compile_asm(out: str) -> None:
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     cmd = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-I../include",
-           "--cuda-device-only", "-S", "-o", out, "csrc/gpad_panel.hip"]
+           "--cuda-device-only", "-S", "-o", out, "csrc/gpad_pairs.hip"]
     subprocess.run(cmd, check=True, cwd=PKG, stderr=subprocess.DEVNULL)
 
 

@@ -2,7 +2,7 @@
 
   GPAD_LIB=tools/abx/libgpad_stamp.so GPAD_LIB_TOLERANT=1 python3 tools/phase_stamps.py --batch 4096
 Solves fresh C4-generator batches with uniform 20-iteration phases and no finisher (plan off), then
-reads workgroup 0's stamps of the phase [100, 120) (gpad_panel.hip GPAD_PSTAMP): kernel entry,
+reads workgroup 0's stamps of the phase [100, 120) (gpad_pairs.hip GPAD_PSTAMP): kernel entry,
 (--plan V: the default planned solve instead, the library built with -DGPAD_STAMP_PHASE_V=V
 -DGPAD_STAMP_V0=V+1, e.g. the C4 shard's second phase at V = 260)
 state loaded, after the load barrier, loop exit, survivors parked, after the closing barrier --

@@ -2,7 +2,7 @@
 
   GPAD_LIB=tools/abl/stamp.so python3 tools/stamp_panel.py --batch 8192
 (the library built with EXTRA=-DGPAD_STAMP; the product build has no stamps).  Runs the C4-shape
-panel solve for a fixed N, reads workgroup 0's stamps (gpad_panel.hip GPAD_STAMP_AT) and prints,
+panel solve for a fixed N, reads workgroup 0's stamps (gpad_pairs.hip GPAD_STAMP_AT) and prints,
 per wave and averaged over the stamped iterations, the cycles of: GEMM-1 issue, its epilogue, the
 wait at its barrier, GEMM-2 issue, its epilogue, the wait at the closing barrier.
 """
