@@ -21,7 +21,7 @@
 #include <cstdlib>
 
 #include "gpad_internal.h"
-#include "gpad_panel.h"  // (f32x4, as_float4, pi16)
+#include "gpad_panel.h"  // (f32x4, as_float4, pi16; the Algorithm-1 test of gpad_panel_test.h)
 
 namespace gpad {
 
@@ -46,15 +46,10 @@ __global__ void pack_bigpanel_kernel(const float* __restrict__ src, int rows, in
 
 __host__ __device__ inline int big_tiles(int x) { return (x + 15) / 16; }
 
-struct BigSlot {  // per wave: its tiles' partials of the test, per column
-    float violz[16], violh[16], wmin[16];
-    double gap[16];
-    float magh[16];  // max(|G_L zhat| + |pD|); with violz reused by the verification of test (A)
-};
-
-// LDS: w and p_D per GEMM-2 row tile, zhat per GEMM-1 row tile (1 KiB each), 16 test slots
+// LDS: w and p_D per GEMM-2 row tile, zhat per GEMM-1 row tile (1 KiB each), 16 test slots (one per
+// wave: its tiles' partials, per column)
 static size_t big_lds_bytes(int n, int m) {
-    return (size_t)(big_tiles(n) + 2 * big_tiles(m)) * 64 * sizeof(float4) + kBigWaves * sizeof(BigSlot);
+    return (size_t)(big_tiles(n) + 2 * big_tiles(m)) * 64 * sizeof(float4) + kBigWaves * sizeof(TestSlot<float>);
 }
 
 bool bigpanel_supported(int n, int m) {
@@ -182,7 +177,7 @@ __global__ __launch_bounds__(64 * kBigWaves) void gpad_bigpanel_kernel(SolveArgs
     float4* Wl = big_lds;           // [T2][64] w in fragment order (B of GEMM 1)
     float4* Zh = big_lds + T2 * 64;  // [T1][64] zhat (B of GEMM 2)
     float4* Pd = Zh + T1 * 64;       // [T2][64] p_D rows
-    BigSlot* slots = reinterpret_cast<BigSlot*>(Pd + T2 * 64);
+    TestSlot<float>* slots = reinterpret_cast<TestSlot<float>*>(Pd + T2 * 64);
 
     const int lane = threadIdx.x & 63;
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -287,8 +282,7 @@ __global__ __launch_bounds__(64 * kBigWaves) void gpad_bigpanel_kernel(SolveArgs
             }
             __syncthreads();
             // ---- GEMM 2 + epilogue: y+ (8d), next w (8a), test partials ----------------------------
-            float violz = -INFINITY, violh = -INFINITY, wmin = INFINITY, magh = 0.0f;
-            double gap = 0.0;
+            TestPart<float> part;
             f32x4 acc_next = {0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
             for (int q = 0; q < NT2; ++q) {
@@ -324,14 +318,7 @@ __global__ __launch_bounds__(64 * kBigWaves) void gpad_bigpanel_kernel(SolveArgs
                         if (use_tol) {
                             const float un = __builtin_fmaf(omt, u[q][r], th * cv);
                             if (active) u[q][r] = un;
-                            if (chk && active && (16 * t + 4 * r + j) < m) {
-                                const float tt = cv + pdq[r];
-                                violh = fmaxf(violh, tt);
-                                magh = fmaxf(magh, __builtin_fabsf(cv) + __builtin_fabsf(pdq[r]));
-                                wmin = fminf(wmin, wv[r]);
-                                gap -= (double)wv[r] * (double)tt;
-                                violz = fmaxf(violz, u[q][r] + pdq[r]);
-                            }
+                            if (chk && active && (16 * t + 4 * r + j) < m) part.row(cv, pdq[r], wv[r], u[q][r]);
                         }
                         if (active) y[q][r] = yp;
                     }
@@ -339,21 +326,8 @@ __global__ __launch_bounds__(64 * kBigWaves) void gpad_bigpanel_kernel(SolveArgs
                 }
             }
             if (chk) {  // this wave's partials per column -> its slot
-#pragma unroll
-                for (int o = 16; o < 64; o <<= 1) {
-                    violz = fmaxf(violz, __shfl_xor(violz, o, 64));
-                    violh = fmaxf(violh, __shfl_xor(violh, o, 64));
-                    magh = fmaxf(magh, __shfl_xor(magh, o, 64));
-                    wmin = fminf(wmin, __shfl_xor(wmin, o, 64));
-                    gap += __shfl_xor(gap, o, 64);
-                }
-                if (j == 0) {
-                    slots[w].violz[c] = violz;
-                    slots[w].violh[c] = violh;
-                    slots[w].magh[c] = magh;
-                    slots[w].wmin[c] = wmin;
-                    slots[w].gap[c] = gap;
-                }
+                part.fold<true>();  // (the __shfl_xor fold: gpad_panel_test.h col_fold)
+                part.put(slots[w], c, j == 0);
             }
             th = th_next;
             bn = bn_next;
@@ -365,20 +339,8 @@ __global__ __launch_bounds__(64 * kBigWaves) void gpad_bigpanel_kernel(SolveArgs
             bool zh_out = true;  // this iteration's zhat still in Zh (no verification GEMM ran)
             if (chk) {
                 int st1 = 0;
-                if (lane < 16 && ((live >> lane) & 1u)) {
-                    double vz = -INFINITY, vh = -INFINITY, wm = INFINITY, gq = 0.0, mh = 0.0;
-#pragma unroll
-                    for (int s2 = 0; s2 < kBigWaves; ++s2) {
-                        vz = fmax(vz, (double)slots[s2].violz[lane]);
-                        vh = fmax(vh, (double)slots[s2].violh[lane]);
-                        mh = fmax(mh, (double)slots[s2].magh[lane]);
-                        wm = fmin(wm, (double)slots[s2].wmin[lane]);
-                        gq += slots[s2].gap[lane];
-                    }
-                    st1 = (vz * a.L <= a.tol ? 1 : 0) |
-                          ((viol_ok(vh, mh, a.L, a.tol, ViolMargin<float>::value) && (wm >= 0.0) &&
-                            (gq * a.L <= a.tol_gap)) ? 2 : 0);
-                }
+                if (lane < 16 && ((live >> lane) & 1u))
+                    st1 = stage1<float, kBigWaves>(slots, 0, kBigWaves, lane, a.L, a.tol, a.tol_gap).bits;
                 const unsigned mA = (unsigned)__ballot(st1 & 1);
                 m2 = (unsigned)__ballot(st1 & 2);
                 if (mA) {  // (A) nominated for some column: G_L z for the panel
@@ -401,7 +363,7 @@ __global__ __launch_bounds__(64 * kBigWaves) void gpad_bigpanel_kernel(SolveArgs
                     }
                     __syncthreads();
                     const bool nom = active && ((mA >> c) & 1u);
-                    float vc = -INFINITY, mc = 0.0f;
+                    VerPart<float> vp;
 #pragma unroll
                     for (int q = 0; q < NT2; ++q) {
                         const int t = w + kBigWaves * q;
@@ -413,32 +375,17 @@ __global__ __launch_bounds__(64 * kBigWaves) void gpad_bigpanel_kernel(SolveArgs
                             for (int r = 0; r < 4; ++r) {
                                 if (nom && (16 * t + 4 * r + j) < m) {
                                     u[q][r] = cz[r];  // the recursion restarts from the direct value
-                                    vc = fmaxf(vc, cz[r] + pdq[r]);
-                                    mc = fmaxf(mc, __builtin_fabsf(cz[r]) + __builtin_fabsf(pdq[r]));
+                                    vp.row(cz[r], pdq[r]);
                                 }
                             }
                         }
                     }
-#pragma unroll
-                    for (int o = 16; o < 64; o <<= 1) {
-                        vc = fmaxf(vc, __shfl_xor(vc, o, 64));
-                        mc = fmaxf(mc, __shfl_xor(mc, o, 64));
-                    }
-                    if (j == 0) {  // every wave's stage-1 reads precede the barrier above
-                        slots[w].violz[c] = vc;
-                        slots[w].magh[c] = mc;
-                    }
+                    vp.fold<true>();
+                    vp.put(slots[w], c, j == 0);
                     __syncthreads();
                     bool ver = false;
-                    if (lane < 16 && ((mA >> lane) & 1u)) {
-                        double vcc = -INFINITY, mcc = 0.0;
-#pragma unroll
-                        for (int s2 = 0; s2 < kBigWaves; ++s2) {
-                            vcc = fmax(vcc, (double)slots[s2].violz[lane]);
-                            mcc = fmax(mcc, (double)slots[s2].magh[lane]);
-                        }
-                        ver = viol_ok(vcc, mcc, a.L, a.tol, ViolMargin<float>::value);
-                    }
+                    if (lane < 16 && ((mA >> lane) & 1u))
+                        ver = verified<float, kBigWaves>(slots, 0, kBigWaves, lane, a.L, a.tol);
                     m1 = (unsigned)__ballot(ver);
                     m2 &= ~m1;
                 }

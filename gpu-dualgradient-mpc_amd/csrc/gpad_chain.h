@@ -1,6 +1,8 @@
 // gpad_chain.h -- device helpers shared by the latency kernels (gpad_kernels.hip: stream and
 // resident kernels; gpad_duo.hip: the two-instance ping-pong kernel): fused-arithmetic wrappers,
 // wave64 reductions and the Algorithm-1 test slots, and the register-resident DPP fmaf chains.
+// The MFMA panel kernels' test (gpad_panel_test.h) takes the butterflies, the reduction ops and
+// check_code from here.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -85,6 +87,7 @@ __device__ __forceinline__ T wave_reduce(T v, Op op) {  // levels 32, 16, ..., 1
 struct OpMax { template <typename T> __device__ T operator()(T a, T b) const { return fmax(a, b); } };
 struct OpMin { template <typename T> __device__ T operator()(T a, T b) const { return fmin(a, b); } };
 struct OpAdd { template <typename T> __device__ T operator()(T a, T b) const { return a + b; } };
+struct OpAbsmaxNan { __device__ float operator()(float x, float y) const { return absmax_nan(x, y); } };
 template <typename T>
 __device__ __forceinline__ T wave_max(T v) { return wave_reduce(v, OpMax{}); }
 template <typename T>

@@ -23,7 +23,7 @@
 #include <cstdlib>
 
 #include "gpad_internal.h"
-#include "gpad_panel.h"  // (f32x4, as_float4, pi16)
+#include "gpad_panel.h"  // (f32x4, as_float4, pi16; the Algorithm-1 test of gpad_panel_test.h)
 
 namespace gpad {
 
@@ -82,13 +82,8 @@ __host__ __device__ inline FlatGeom flat_geom(int n, int m, int n_u) {
 //   Zc [n_u][T1]   zhat per cell (row i of cell j = zhat[i n_u + j])
 //   Zn [KB3]       zhat in natural order (the coupling rows' operand)
 // test partials: one slot per phase-2 unit (its 16 columns, reduced over the unit's rows)
-struct FlatPanelSlot {
-    float violz[16], violh[16], wmin[16];
-    double gap[16];
-    float magh[16];  // max(|G_L zhat| + |pD|); with violz reused by the verification of test (A)
-};
 static size_t flatpanel_lds_bytes(const FlatGeom& g, int P) {
-    return (size_t)P * g.PB * 1024 + (size_t)P * g.U2 * sizeof(FlatPanelSlot);
+    return (size_t)P * g.PB * 1024 + (size_t)P * g.U2 * sizeof(TestSlot<float>);
 }
 
 // A values from the flat data as the setup stores it: MGf row-major Nh x m (sign-folded -ML),
@@ -321,8 +316,8 @@ __global__ __launch_bounds__(64 * W, 4) void gpad_flatpanel_kernel(SolveArgs<flo
     // per panel pp at fp_lds + pp * PB * 64:  Wc [n_u][KBc] | We [KBe] | Zc [n_u][T1] | Zn [KB3]
     const int oWe = g.n_u * g.KBc * 64, oZc = oWe + g.KBe * 64, oZn = oZc + g.n_u * g.T1 * 64;
     const int PBf = g.PB * 64;
-    FlatPanelSlot* slots = reinterpret_cast<FlatPanelSlot*>(fp_lds + P * PBf);  // [P * U2]
-    float4* As = fp_lds + P * PBf + (P * g.U2 * (int)sizeof(FlatPanelSlot)) / 16;  // ALDS: the A image
+    TestSlot<float>* slots = reinterpret_cast<TestSlot<float>*>(fp_lds + P * PBf);  // [P * U2]
+    float4* As = fp_lds + P * PBf + (P * g.U2 * (int)sizeof(TestSlot<float>)) / 16;  // ALDS: the A image
 
     const int lane = threadIdx.x & 63;
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -505,8 +500,7 @@ __global__ __launch_bounds__(64 * W, 4) void gpad_flatpanel_kernel(SolveArgs<flo
                     const float wv[4] = {w4.x, w4.y, w4.z, w4.w};
                     const int lim = cp ? g.E : 4 * g.Nh;
                     float wn[4];
-                    float violz = -INFINITY, violh = -INFINITY, wmin = INFINITY, magh = 0.0f;
-                    double gap = 0.0;
+                    TestPart<float> part;
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
                         const float cv = acc[r], wi = wv[r], pdi = pd[q][r];
@@ -515,35 +509,15 @@ __global__ __launch_bounds__(64 * W, 4) void gpad_flatpanel_kernel(SolveArgs<flo
                         if (use_tol) {
                             const float un2 = __builtin_fmaf(omt, u[q][r], th * cv);
                             if (act) u[q][r] = un2;
-                            if (chk && act && 16 * x.t + 4 * r + jl < lim) {
-                                const float tt = cv + pdi;
-                                violh = fmaxf(violh, tt);
-                                magh = fmaxf(magh, __builtin_fabsf(cv) + __builtin_fabsf(pdi));
-                                wmin = fminf(wmin, wi);
-                                gap -= (double)wi * (double)tt;
-                                violz = fmaxf(violz, u[q][r] + pdi);
-                            }
+                            if (chk && act && 16 * x.t + 4 * r + jl < lim) part.row(cv, pdi, wi, u[q][r]);
                         }
                         wn[r] = __builtin_fmaf(bn, yp - y[q][r], yp);
                         if (act) y[q][r] = yp;
                     }
                     if (act) *wp = make_float4(wn[0], wn[1], wn[2], wn[3]);
                     if (chk) {  // this unit's partials per column -> its slot
-#pragma unroll
-                        for (int o = 16; o < 64; o <<= 1) {
-                            violz = fmaxf(violz, __shfl_xor(violz, o, 64));
-                            violh = fmaxf(violh, __shfl_xor(violh, o, 64));
-                            magh = fmaxf(magh, __shfl_xor(magh, o, 64));
-                            wmin = fminf(wmin, __shfl_xor(wmin, o, 64));
-                            gap += __shfl_xor(gap, o, 64);
-                        }
-                        if (jl == 0) {
-                            slots[un].violz[c] = violz;
-                            slots[un].violh[c] = violh;
-                            slots[un].magh[c] = magh;
-                            slots[un].wmin[c] = wmin;
-                            slots[un].gap[c] = gap;
-                        }
+                        part.fold<true>();  // (the __shfl_xor fold: gpad_panel_test.h col_fold)
+                        part.put(slots[un], c, jl == 0);
                     }
                 }
             }
@@ -561,19 +535,8 @@ __global__ __launch_bounds__(64 * W, 4) void gpad_flatpanel_kernel(SolveArgs<flo
             if (chk) {  // lane = (panel lane >> 4, column lane & 15): reduce that panel's unit slots
                 int st1 = 0;
                 const int pp = lane >> 4;
-                if (pp < P && ((live >> lane) & 1ull)) {
-                    double vz = -INFINITY, vh = -INFINITY, wm = INFINITY, gq = 0.0, mh = 0.0;
-                    for (int s2 = pp * g.U2; s2 < (pp + 1) * g.U2; ++s2) {
-                        vz = fmax(vz, (double)slots[s2].violz[c]);
-                        vh = fmax(vh, (double)slots[s2].violh[c]);
-                        mh = fmax(mh, (double)slots[s2].magh[c]);
-                        wm = fmin(wm, (double)slots[s2].wmin[c]);
-                        gq += slots[s2].gap[c];
-                    }
-                    st1 = (vz * a.L <= a.tol ? 1 : 0) |
-                          ((viol_ok(vh, mh, a.L, a.tol, ViolMargin<float>::value) && (wm >= 0.0) &&
-                            (gq * a.L <= a.tol_gap)) ? 2 : 0);
-                }
+                if (pp < P && ((live >> lane) & 1ull))
+                    st1 = stage1<float>(slots, pp * g.U2, g.U2, c, a.L, a.tol, a.tol_gap).bits;
                 const unsigned long long mA = __ballot(st1 & 1);
                 m2 = __ballot(st1 & 2);
                 if (mA) {  // (A) nominated for some column: the flat G_L z chains of the group
@@ -622,36 +585,19 @@ __global__ __launch_bounds__(64 * W, 4) void gpad_flatpanel_kernel(SolveArgs<flo
                                                              cp ? L + oZn : L + oZc + x.cell * g.T1 * 64, nkb,
                                                              L + oZn, lane);
                             const int lim = cp ? g.E : 4 * g.Nh;
-                            float vc = -INFINITY, mc = 0.0f;
+                            VerPart<float> vp;
 #pragma unroll
                             for (int r = 0; r < 4; ++r) {
                                 if (nom) u[q][r] = cz[r];  // the recursion restarts from the direct value
-                                if (nom && 16 * x.t + 4 * r + jl < lim) {
-                                    vc = fmaxf(vc, cz[r] + pd[q][r]);
-                                    mc = fmaxf(mc, __builtin_fabsf(cz[r]) + __builtin_fabsf(pd[q][r]));
-                                }
+                                if (nom && 16 * x.t + 4 * r + jl < lim) vp.row(cz[r], pd[q][r]);
                             }
-#pragma unroll
-                            for (int o = 16; o < 64; o <<= 1) {
-                                vc = fmaxf(vc, __shfl_xor(vc, o, 64));
-                                mc = fmaxf(mc, __shfl_xor(mc, o, 64));
-                            }
-                            if (jl == 0) {  // every wave's stage-1 reads precede the barrier above
-                                slots[un].violz[c] = vc;
-                                slots[un].magh[c] = mc;
-                            }
+                            vp.fold<true>();
+                            vp.put(slots[un], c, jl == 0);
                         }
                     }
                     __syncthreads();
                     bool ver = false;
-                    if (pp < P && ((mA >> lane) & 1ull)) {
-                        double vcc = -INFINITY, mcc = 0.0;
-                        for (int s2 = pp * g.U2; s2 < (pp + 1) * g.U2; ++s2) {
-                            vcc = fmax(vcc, (double)slots[s2].violz[c]);
-                            mcc = fmax(mcc, (double)slots[s2].magh[c]);
-                        }
-                        ver = viol_ok(vcc, mcc, a.L, a.tol, ViolMargin<float>::value);
-                    }
+                    if (pp < P && ((mA >> lane) & 1ull)) ver = verified<float>(slots, pp * g.U2, g.U2, c, a.L, a.tol);
                     m1 = __ballot(ver);
                     m2 &= ~m1;
                 }

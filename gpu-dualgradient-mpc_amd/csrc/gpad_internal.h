@@ -49,6 +49,11 @@ constexpr int kDebugDropHandoff = 1;  // the first hand-off helper skips its fir
 // passes when L max(chain + pD) + kViolMargin L max(|chain| + |pD|) <= tol (16 units of 2^-24 /
 // 2^-53).  Test (A) is nominated by the recursive u = G_L z and decided on the direct chain
 // G_L z (which then also resets u).  Same constants and arithmetic as oracle/gpad_oracle.h.
+// The test around the decision is written three times, once per way a kernel holds its rows:
+// gpad_chain.h (check_publish / check_stage1 / check_verify: the register-resident family),
+// gpad_panel_test.h (every MFMA panel kernel, f32 and f64) and gpad_pairs.h (the panel pairs'
+// packed slots).  The code is gpad_chain.h's check_code, or its two ballot masks (verified (A),
+// then (B) without it) in the kernels whose lanes 0..15 / 0..63 decide for the columns.
 template <typename T> struct ViolMargin;
 template <> struct ViolMargin<float> { static constexpr double value = 0x1p-20; };
 template <> struct ViolMargin<double> { static constexpr double value = 0x1p-49; };
@@ -64,8 +69,9 @@ __device__ __forceinline__ double absmax_nan(double acc, double x) {
                              b = (unsigned long long)__double_as_longlong(x) & 0x7fffffffffffffffull;
     return __longlong_as_double((long long)(a > b ? a : b));
 }
-// the decision itself, one expression everywhere (no contraction: -ffp-contract=off).  The maxima
-// start from -inf / 0 and drop NaNs (fmax), so an instance whose rows are all NaN -- a NaN or an
+// the decision itself, one expression: called from the three texts above and, for the value
+// branches' violation part, from the stream kernel -- nowhere else (no contraction:
+// -ffp-contract=off).  The maxima start from -inf / 0 and drop NaNs (fmax), so an instance whose rows are all NaN -- a NaN or an
 // infinity in its g poisons every row within two iterations -- arrives with viol = -inf, mag = 0:
 // no evidence is not a pass (a finite problem's viol is finite; pD = -inf in every row gives
 // mag = inf, which never passed)

@@ -313,8 +313,6 @@ __device__ __forceinline__ void loop_solo(const SolveArgs<float>& a, const DuoCt
     }
 }
 
-struct OpAbsmaxNan { __device__ float operator()(float x, float y) const { return absmax_nan(x, y); } };
-
 // The fleet kernel's context and its max |g| epilogue: gpad_loop_kernel's own text of both, kept
 // apart because that kernel's register allocation moves when they are hoisted out of its body
 // (+1 VGPR in most buckets, other scratch at 208/208).

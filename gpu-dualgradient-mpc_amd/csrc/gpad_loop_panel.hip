@@ -7,7 +7,8 @@
 // workgroup is gpad_panel_kernel<T>'s (gpad_panel.hip): a panel of 16 packs, wave t = row tile t of both
 // GEMMs over the fragment images gpad_setup packs, the same MFMA chains (every k-block, ascending,
 // the zero-padding blocks included) and the same epilogues and Algorithm-1 test, operation for
-// operation.  What differs is the bookkeeping: every column carries its own pack, MPC step and
+// operation -- enforced, not copied: both kernels call gpad_panel.h's panel_gemm, panel_primal and
+// panel_dual and gpad_panel_test.h's test.  What differs is the bookkeeping: every column carries its own pack, MPC step and
 // iteration count vc, so theta / beta are per lane (theta[vc], beta[vc + 1]: the same table words,
 // hence the same bits), and at a test event the columns that finished run the step boundary of
 // gpad_loop.h in place -- counters, u = z*[0:nu], x+ = A x + B u, M(x+), g(x+), the u seed -- and go on
@@ -20,13 +21,10 @@
 // change step only at events, so every column's vc = v (mod check_every) for the workgroup's
 // iteration counter v and the iteration limit falls on an event; with fixed N all columns of a
 // workgroup start together and reach N together.
-//
-// panel_gemm, the vector typedefs, PanelSlot and the shape rules are gpad_panel.h's, shared with gpad_panel.hip.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 
-#include "gpad_chain.h"
 #include "gpad_internal.h"
 #include "gpad_panel.h"
 
@@ -46,12 +44,10 @@ struct __attribute__((aligned(16))) LoopPanelLds {
     float Zh[T * 256];  // [T][64][4] zhat (B of GEMM 2)
     float Gp[T * 256];  // g_P rows of tile t
     float Pd[T * 256];  // p_D rows of tile t
-    PanelSlot slots[T];
+    TestSlot<float> slots[T];
     LpCol col[16];
     float gmw[16];      // per wave: max |g| at the kernel's end
 };
-
-struct OpAbsmaxNan { __device__ float operator()(float x, float y) const { return absmax_nan(x, y); } };
 
 constexpr int kLpLdsPerCu = 160 * 1024;
 constexpr int kLpTabMax = 32 * 1024;  // (static + dynamic LDS of the T = 16 kernel stay below 128 KiB)
@@ -92,7 +88,7 @@ __global__ __launch_bounds__(64 * T) void gpad_loop_panel_kernel(LoopArgs la) {
     float4* Zh4 = reinterpret_cast<float4*>(L.Zh);
     float4* Gp4 = reinterpret_cast<float4*>(L.Gp);
     float4* Pd4 = reinterpret_cast<float4*>(L.Pd);
-    PanelSlot* slots = L.slots;
+    TestSlot<float>* slots = L.slots;
     const bool use_tol = a.tol > 0.0;
     // row tiles whose results nobody reads: 16t >= n in GEMM 1, 16t >= m in GEMM 2 (their packed rows
     // are zero)
@@ -142,55 +138,14 @@ __global__ __launch_bounds__(64 * T) void gpad_loop_panel_kernel(LoopArgs la) {
             if (ev) ke = period;
             const bool chk = use_tol && ev;
             const float omt = 1.0f - th;
-            // ---- GEMM 1 + epilogue: zhat = -ML w - g_P (8b), z = (1-th) z + th zhat (8c) ----
-            {
-                f32x4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
-                if (g1) acc = panel_gemm<T>(PA1, L.Wl, voff, lane);
-                const float4 g4 = Gp4[slot];
-                const float gp[4] = {g4.x, g4.y, g4.z, g4.w};
-                float zh[4];
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    zh[r] = acc[r] - gp[r];
-                    const float zn = __builtin_fmaf(omt, z[r], th * zh[r]);
-                    if (active) z[r] = zn;
-                }
-                Zh4[slot] = make_float4(zh[0], zh[1], zh[2], zh[3]);
-            }
+            // ---- GEMM 1 and GEMM 2 with their epilogues: gpad_panel.h's, as gpad_panel_kernel calls them ----
+            f32x4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
+            if (g1) acc = panel_gemm<T>(PA1, L.Wl, voff, lane);
+            panel_primal(acc, Gp4, Zh4, slot, omt, th, active, z);
             __syncthreads();
-            // ---- GEMM 2 + epilogue: y+ = [w + G_L zhat + p_D]+ (8d), next w (8a) ----------
-            float violz = -INFINITY, violh = -INFINITY, wmin = INFINITY, magh = 0.0f;
-            double gap = 0.0;
-            {
-                f32x4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
-                if (g2) acc = panel_gemm<T>(PA2, L.Zh, voff, lane);
-                const float4 w4 = Wl4[slot];
-                const float wv[4] = {w4.x, w4.y, w4.z, w4.w};
-                const float4 p4 = Pd4[slot];
-                const float pd[4] = {p4.x, p4.y, p4.z, p4.w};
-                float wn[4];
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const float cv = acc[r];
-                    const float sv = (wv[r] + pd[r]) + cv;
-                    const float yp = (__builtin_fabsf(sv) + sv) * 0.5f;
-                    wn[r] = __builtin_fmaf(bn, yp - y[r], yp);
-                    if (use_tol) {
-                        const float un = __builtin_fmaf(omt, u[r], th * cv);
-                        if (active) u[r] = un;
-                        if (chk && active && (16 * t + 4 * r + j) < m) {
-                            const float tt = cv + pd[r];
-                            violh = fmaxf(violh, tt);
-                            magh = fmaxf(magh, __builtin_fabsf(cv) + __builtin_fabsf(pd[r]));
-                            wmin = fminf(wmin, wv[r]);
-                            gap -= (double)wv[r] * (double)tt;
-                            violz = fmaxf(violz, u[r] + pd[r]);
-                        }
-                    }
-                    if (active) y[r] = yp;
-                }
-                if (active) Wl4[slot] = make_float4(wn[0], wn[1], wn[2], wn[3]);
-            }
+            acc = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+            if (g2) acc = panel_gemm<T>(PA2, L.Zh, voff, lane);
+            TestPart<float> part = panel_dual(acc, Wl4, Pd4, slot, omt, th, bn, use_tol, chk, active, 16 * t + j, m, y, u);
             th = th_next;
             bn = bn_next;
             if (active) ++vc;
@@ -203,35 +158,12 @@ __global__ __launch_bounds__(64 * T) void gpad_loop_panel_kernel(LoopArgs la) {
             // ---- Algorithm 1 test, per column: lane groups j, then row tiles through LDS ----
             int code = 0;
             if (chk) {
-                violz = bfly<32>(bfly<16>(violz, OpMax{}), OpMax{});
-                violh = bfly<32>(bfly<16>(violh, OpMax{}), OpMax{});
-                magh = bfly<32>(bfly<16>(magh, OpMax{}), OpMax{});
-                wmin = bfly<32>(bfly<16>(wmin, OpMin{}), OpMin{});
-                gap = bfly<32>(bfly<16>(gap, OpAdd{}), OpAdd{});
-                if (j == 0) {
-                    slots[t].violz[c] = violz;
-                    slots[t].violh[c] = violh;
-                    slots[t].magh[c] = magh;
-                    slots[t].wmin[c] = wmin;
-                    slots[t].gap[c] = gap;
-                }
+                part.fold();
+                part.put(slots[t], c, j == 0);
                 __syncthreads();
                 int st1 = 0;
-                if (active) {
-                    double vz = -INFINITY, vh = -INFINITY, wm = INFINITY, gq = 0.0, mh = 0.0;
-#pragma unroll
-                    for (int s2 = 0; s2 < T; ++s2) {
-                        vz = fmax(vz, (double)slots[s2].violz[c]);
-                        vh = fmax(vh, (double)slots[s2].violh[c]);
-                        mh = fmax(mh, (double)slots[s2].magh[c]);
-                        wm = fmin(wm, (double)slots[s2].wmin[c]);
-                        gq += slots[s2].gap[c];
-                    }
-                    st1 = (vz * a.L <= a.tol ? 1 : 0) |
-                          ((viol_ok(vh, mh, a.L, a.tol, ViolMargin<float>::value) && (wm >= 0.0) &&
-                            (gq * a.L <= a.tol_gap)) ? 2 : 0);
-                }
-                bool verified = false;
+                if (active) st1 = stage1<float, T>(slots, 0, T, c, a.L, a.tol, a.tol_gap).bits;
+                bool ver = false;
                 if (__syncthreads_or(st1 & 1)) {  // (A) nominated somewhere: G_L z for the panel
                     Zh4[slot] = make_float4(z[0], z[1], z[2], z[3]);
                     __syncthreads();
@@ -239,33 +171,20 @@ __global__ __launch_bounds__(64 * T) void gpad_loop_panel_kernel(LoopArgs la) {
                     if (g2) cz = panel_gemm<T>(PA2, L.Zh, voff, lane);
                     const float4 p4 = Pd4[slot];
                     const float pd[4] = {p4.x, p4.y, p4.z, p4.w};
-                    float vv = -INFINITY, mc = 0.0f;
+                    VerPart<float> vp;
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
                         if ((st1 & 1) && (16 * t + 4 * r + j) < m) {
                             u[r] = cz[r];  // the recursion restarts from the direct value
-                            vv = fmaxf(vv, cz[r] + pd[r]);
-                            mc = fmaxf(mc, __builtin_fabsf(cz[r]) + __builtin_fabsf(pd[r]));
+                            vp.row(cz[r], pd[r]);
                         }
                     }
-                    vv = bfly<32>(bfly<16>(vv, OpMax{}), OpMax{});
-                    mc = bfly<32>(bfly<16>(mc, OpMax{}), OpMax{});
-                    if (j == 0) {  // every wave finished reading the slots before the barrier above
-                        slots[t].violz[c] = vv;
-                        slots[t].magh[c] = mc;
-                    }
+                    vp.fold();
+                    vp.put(slots[t], c, j == 0);
                     __syncthreads();
-                    if (st1 & 1) {
-                        double vcc = -INFINITY, mcc = 0.0;
-#pragma unroll
-                        for (int s2 = 0; s2 < T; ++s2) {
-                            vcc = fmax(vcc, (double)slots[s2].violz[c]);
-                            mcc = fmax(mcc, (double)slots[s2].magh[c]);
-                        }
-                        verified = viol_ok(vcc, mcc, a.L, a.tol, ViolMargin<float>::value);
-                    }
+                    if (st1 & 1) ver = verified<float, T>(slots, 0, T, c, a.L, a.tol);
                 }
-                code = ((st1 & 1) && verified) ? 1 : ((st1 & 2) ? 2 : 0);
+                code = check_code(st1, ver);
             }
             // ---- step boundary of the columns whose solve ended ------------------------------
             fin = active && (code != 0 || vc >= N);

@@ -1,11 +1,13 @@
-// gpad_panel.h -- what every f32 MFMA panel unit shares (gfx950): the fragment layout, the vector
-// types, the tile row permutation, the per-tile slots of the Algorithm-1 test, the skinny GEMM of the
-// T-wave panel, and the host-side shape rules (tile count, resident grid, hand-off shapes).
-// Included by gpad_panel.hip (gpad_panel_kernel: a batch of independent solves, T <= 8), gpad_pairs.hip
-// (panel pairs, 8 < T <= 16), gpad_loop_panel.hip (a queue of closed-loop packs), gpad_bigpanel.hip,
-// gpad_flatpanel.hip and the host phase driver gpad_phases.cpp.  gpad_panel_kernel and
-// gpad_loop_panel_kernel run exactly this panel_gemm per (row tile, column), so their MFMA chains
-// cannot drift apart.
+// gpad_panel.h -- what every f32 MFMA panel unit shares (gfx950):
+//   * the fragment layout (below), the vector types and the tile row permutation pi16 -- every unit;
+//   * the host-side shape rules: tile count, resident grid, hand-off shapes -- gpad_phases.cpp too;
+//   * the Algorithm-1 test, through gpad_panel_test.h (its one text; the f64 panels include that
+//     header alone) -- gpad_panel.hip, gpad_loop_panel.hip, gpad_bigpanel.hip, gpad_flatpanel.hip;
+//     gpad_pairs.hip keeps its own packed slots;
+//   * the iteration of the T-wave panel -- panel_gemm, panel_primal (GEMM 1's epilogue) and
+//     panel_dual (GEMM 2's, with the test partials) -- which gpad_panel_kernel (a batch of
+//     independent solves, T <= 8) and gpad_loop_panel_kernel (a queue of closed-loop packs) both
+//     call: their MFMA chains, epilogues and test are one text and cannot drift apart.
 //
 // Shared-matrix batches on the f32 MFMA pipe.  When every instance of a batch shares ML and G (one
 // plant, many states: the battery scenario batch), the two mat-vecs of a GPAD iteration over 16
@@ -35,6 +37,8 @@
 #pragma once
 
 #include <hip/hip_runtime.h>
+
+#include "gpad_panel_test.h"
 
 namespace gpad {
 
@@ -70,14 +74,6 @@ __device__ __forceinline__ float4 as_float4(u32x4 v) {
                        __uint_as_float(v.w));
 }
 
-struct PanelSlot {  // per wave (row tile), per instance partials of the Algorithm-1 test
-    float violz[16], violh[16], wmin[16];
-    double gap[16];
-    float magh[16];  // max(|G_L zhat| + |pD|): test (B)'s rounding scale
-};
-// (A) nominated by the recursive u is decided on the direct G_L z (gpad_internal.h ViolMargin):
-// the verification reuses violz / magh of the slots for max(G_L z + pD) / max(|G_L z| + |pD|).
-
 // acc = A[tile t] (T k-blocks, streamed from L2 one block ahead) x B (LDS, fragment order).
 // The MFMA k-order is ascending (block 0..T-1, step 0..3), i.e. the reference's sequential chain.
 // A is read with buffer loads: one 32-bit lane offset (t*1 KiB + lane*16 B) in a VGPR and the
@@ -106,6 +102,51 @@ __device__ __forceinline__ f32x4 panel_gemm(__amdgpu_buffer_rsrc_t PA, const flo
         asm volatile("" ::: "memory");  // keep the prefetch one k-block deep
     }
     return acc;
+}
+
+// The two epilogues of the T-wave panel's iteration.  `slot`: this lane's float4 in the [T][64][4]
+// LDS tiles; register r of z / y / u <-> row row0 + 4r of the column (row0 = 16t + j).
+// GEMM 1 (acc = -ML w): zhat = acc - g_P (8b) into Zh, z = (1-th) z + th zhat (8c)
+__device__ __forceinline__ void panel_primal(f32x4 acc, const float4* Gp4, float4* Zh4, int slot, float omt,
+                                             float th, bool active, float (&z)[4]) {
+    const float4 g4 = Gp4[slot];
+    const float gp[4] = {g4.x, g4.y, g4.z, g4.w};
+    float zh[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        zh[r] = acc[r] - gp[r];
+        const float zn = __builtin_fmaf(omt, z[r], th * zh[r]);
+        if (active) z[r] = zn;
+    }
+    Zh4[slot] = make_float4(zh[0], zh[1], zh[2], zh[3]);
+}
+// GEMM 2 (acc = G_L zhat): y+ = [w + acc + p_D]+ (8d), the next w (8a) into Wl, the recursion
+// u = (1-th) u + th acc; at a test event (chk) the partials of the column's live rows (< m)
+__device__ __forceinline__ TestPart<float> panel_dual(f32x4 acc, float4* Wl4, const float4* Pd4, int slot,
+                                                      float omt, float th, float bn, bool use_tol, bool chk,
+                                                      bool active, int row0, int m, float (&y)[4],
+                                                      float (&u)[4]) {
+    TestPart<float> part;
+    const float4 w4 = Wl4[slot];
+    const float wv[4] = {w4.x, w4.y, w4.z, w4.w};
+    const float4 p4 = Pd4[slot];
+    const float pd[4] = {p4.x, p4.y, p4.z, p4.w};
+    float wn[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const float cv = acc[r];
+        const float sv = (wv[r] + pd[r]) + cv;
+        const float yp = (__builtin_fabsf(sv) + sv) * 0.5f;
+        wn[r] = __builtin_fmaf(bn, yp - y[r], yp);
+        if (use_tol) {
+            const float un = __builtin_fmaf(omt, u[r], th * cv);
+            if (active) u[r] = un;
+            if (chk && active && (row0 + 4 * r) < m) part.row(cv, pd[r], wv[r], u[r]);
+        }
+        if (active) y[r] = yp;
+    }
+    if (active) Wl4[slot] = make_float4(wn[0], wn[1], wn[2], wn[3]);
+    return part;
 }
 
 }  // namespace gpad

@@ -6,7 +6,6 @@
 
 #include <cmath>
 
-#include "gpad_chain.h"  // (the VALU butterflies of the test reductions)
 #include "gpad_internal.h"
 #include "gpad_panel.h"
 
@@ -81,7 +80,7 @@ __global__ __launch_bounds__(64 * T) void gpad_panel_kernel(SolveArgs<float> a) 
     // g_P rows and p_D rows of tile t
     __shared__ __attribute__((aligned(16))) float Gp[T * 256];
     __shared__ __attribute__((aligned(16))) float Pd[T * 256];
-    __shared__ PanelSlot slots[T];
+    __shared__ TestSlot<float> slots[T];
 
     const int lane = threadIdx.x & 63;
     const int t = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // row tile of this wave
@@ -152,52 +151,11 @@ __global__ __launch_bounds__(64 * T) void gpad_panel_kernel(SolveArgs<float> a) 
             const bool chk = use_tol && (v % K) == 0;  // uniform: every column is at iteration v
             const float omt = 1.0f - th;
             // ---- GEMM 1 + epilogue: zhat = -ML w - g_P (8b), z = (1-th) z + th zhat (8c) ----
-            {
-                const f32x4 acc = panel_gemm<T>(PA1, Wl, voff, lane);
-                const float4 g4 = Gp4[slot];
-                const float gp[4] = {g4.x, g4.y, g4.z, g4.w};
-                float zh[4];
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    zh[r] = acc[r] - gp[r];
-                    const float zn = __builtin_fmaf(omt, z[r], th * zh[r]);
-                    if (active) z[r] = zn;
-                }
-                Zh4[slot] = make_float4(zh[0], zh[1], zh[2], zh[3]);
-            }
+            panel_primal(panel_gemm<T>(PA1, Wl, voff, lane), Gp4, Zh4, slot, omt, th, active, z);
             __syncthreads();
             // ---- GEMM 2 + epilogue: y+ = [w + G_L zhat + p_D]+ (8d), next w (8a) ----------
-            float violz = -INFINITY, violh = -INFINITY, wmin = INFINITY, magh = 0.0f;
-            double gap = 0.0;
-            {
-                const f32x4 acc = panel_gemm<T>(PA2, Zh, voff, lane);
-                const float4 w4 = Wl4[slot];
-                const float wv[4] = {w4.x, w4.y, w4.z, w4.w};
-                const float4 p4 = Pd4[slot];
-                const float pd[4] = {p4.x, p4.y, p4.z, p4.w};
-                float wn[4];
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const float cv = acc[r];
-                    const float sv = (wv[r] + pd[r]) + cv;
-                    const float yp = (__builtin_fabsf(sv) + sv) * 0.5f;
-                    wn[r] = __builtin_fmaf(bn, yp - y[r], yp);
-                    if (use_tol) {
-                        const float un = __builtin_fmaf(omt, u[r], th * cv);
-                        if (active) u[r] = un;
-                        if (chk && active && (16 * t + 4 * r + j) < m) {
-                            const float tt = cv + pd[r];
-                            violh = fmaxf(violh, tt);
-                            magh = fmaxf(magh, __builtin_fabsf(cv) + __builtin_fabsf(pd[r]));
-                            wmin = fminf(wmin, wv[r]);
-                            gap -= (double)wv[r] * (double)tt;
-                            violz = fmaxf(violz, u[r] + pd[r]);
-                        }
-                    }
-                    if (active) y[r] = yp;
-                }
-                if (active) Wl4[slot] = make_float4(wn[0], wn[1], wn[2], wn[3]);
-            }
+            TestPart<float> part = panel_dual(panel_gemm<T>(PA2, Zh, voff, lane), Wl4, Pd4, slot, omt, th, bn,
+                                              use_tol, chk, active, 16 * t + j, m, y, u);
             th = th_next;
             bn = bn_next;
             __syncthreads();
@@ -207,36 +165,12 @@ __global__ __launch_bounds__(64 * T) void gpad_panel_kernel(SolveArgs<float> a) 
             int code = 0;
             bool zh_out = true;  // this iteration's zhat still in Zh (no verification GEMM ran)
             if (chk) {
-                // lane groups j (xor 16, 32) on the VALU (gpad_chain.h: the shfl_xor butterfly's values)
-                violz = bfly<32>(bfly<16>(violz, OpMax{}), OpMax{});
-                violh = bfly<32>(bfly<16>(violh, OpMax{}), OpMax{});
-                magh = bfly<32>(bfly<16>(magh, OpMax{}), OpMax{});
-                wmin = bfly<32>(bfly<16>(wmin, OpMin{}), OpMin{});
-                gap = bfly<32>(bfly<16>(gap, OpAdd{}), OpAdd{});
-                if (j == 0) {
-                    slots[t].violz[c] = violz;
-                    slots[t].violh[c] = violh;
-                    slots[t].magh[c] = magh;
-                    slots[t].wmin[c] = wmin;
-                    slots[t].gap[c] = gap;
-                }
+                part.fold();
+                part.put(slots[t], c, j == 0);
                 __syncthreads();
                 int st1 = 0;
-                if (active) {
-                    double vz = -INFINITY, vh = -INFINITY, wm = INFINITY, gq = 0.0, mh = 0.0;
-#pragma unroll
-                    for (int s2 = 0; s2 < T; ++s2) {
-                        vz = fmax(vz, (double)slots[s2].violz[c]);
-                        vh = fmax(vh, (double)slots[s2].violh[c]);
-                        mh = fmax(mh, (double)slots[s2].magh[c]);
-                        wm = fmin(wm, (double)slots[s2].wmin[c]);
-                        gq += slots[s2].gap[c];
-                    }
-                    st1 = (vz * a.L <= a.tol ? 1 : 0) |
-                          ((viol_ok(vh, mh, a.L, a.tol, ViolMargin<float>::value) && (wm >= 0.0) &&
-                            (gq * a.L <= a.tol_gap)) ? 2 : 0);
-                }
-                bool verified = false;
+                if (active) st1 = stage1<float, T>(slots, 0, T, c, a.L, a.tol, a.tol_gap).bits;
+                bool ver = false;
                 if (__syncthreads_or(st1 & 1)) {  // (A) nominated somewhere: G_L z for the panel
                     zh_out = false;
                     if (st1 & 2) {  // test (B)'s result (zhat) out now: Zh is about to hold z
@@ -253,33 +187,20 @@ __global__ __launch_bounds__(64 * T) void gpad_panel_kernel(SolveArgs<float> a) 
                     const f32x4 cz = panel_gemm<T>(PA2, Zh, voff, lane);
                     const float4 p4 = Pd4[slot];
                     const float pd[4] = {p4.x, p4.y, p4.z, p4.w};
-                    float vc = -INFINITY, mc = 0.0f;
+                    VerPart<float> vp;
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
                         if ((st1 & 1) && (16 * t + 4 * r + j) < m) {
                             u[r] = cz[r];  // the recursion restarts from the direct value
-                            vc = fmaxf(vc, cz[r] + pd[r]);
-                            mc = fmaxf(mc, __builtin_fabsf(cz[r]) + __builtin_fabsf(pd[r]));
+                            vp.row(cz[r], pd[r]);
                         }
                     }
-                    vc = bfly<32>(bfly<16>(vc, OpMax{}), OpMax{});
-                    mc = bfly<32>(bfly<16>(mc, OpMax{}), OpMax{});
-                    if (j == 0) {  // every wave finished reading the slots before the barrier above
-                        slots[t].violz[c] = vc;
-                        slots[t].magh[c] = mc;
-                    }
+                    vp.fold();
+                    vp.put(slots[t], c, j == 0);
                     __syncthreads();
-                    if (st1 & 1) {
-                        double vcc = -INFINITY, mcc = 0.0;
-#pragma unroll
-                        for (int s2 = 0; s2 < T; ++s2) {
-                            vcc = fmax(vcc, (double)slots[s2].violz[c]);
-                            mcc = fmax(mcc, (double)slots[s2].magh[c]);
-                        }
-                        verified = viol_ok(vcc, mcc, a.L, a.tol, ViolMargin<float>::value);
-                    }
+                    if (st1 & 1) ver = verified<float, T>(slots, 0, T, c, a.L, a.tol);
                 }
-                code = ((st1 & 1) && verified) ? 1 : ((st1 & 2) ? 2 : 0);
+                code = check_code(st1, ver);
             }
             // ---- finished columns: results out ---------------------------------------------
             if (active && (code != 0 || v >= N)) {

@@ -35,6 +35,7 @@
 #include <cmath>
 
 #include "gpad_internal.h"
+#include "gpad_panel_test.h"  // (the Algorithm-1 test, S = double)
 
 namespace gpad {
 
@@ -153,19 +154,7 @@ struct P64Relay {
     static constexpr int C1 = T / 4, C2 = 2 * T / 4, C3 = 3 * T / 4;
 };
 
-struct P64Slot {  // per tile and column: the test partials / the value-function sums
-    double violz[16], violh[16], wmin[16], gap[16], magh[16];
-};
-
-// max / min / sum of this lane's 4 rows over the 4 lane groups of its column (xor 16, 32)
-__device__ __forceinline__ double col_max(double v) {
-    v = fmax(v, __shfl_xor(v, 16, 64));
-    return fmax(v, __shfl_xor(v, 32, 64));
-}
-__device__ __forceinline__ double col_min(double v) {
-    v = fmin(v, __shfl_xor(v, 16, 64));
-    return fmin(v, __shfl_xor(v, 32, 64));
-}
+// a value-function sum of this lane's 4 rows over the 4 lane groups of its column (xor 16, 32)
 __device__ __forceinline__ double col_sum(double v) {
     v += __shfl_xor(v, 16, 64);
     return v + __shfl_xor(v, 32, 64);
@@ -275,7 +264,7 @@ __global__ __launch_bounds__(RELAY ? 1024 : 64 * T) void gpad_panel64_kernel(Sol
     __shared__ f64x4 Zh[TL * 64];
     __shared__ f64x4 Xv[TL * 64];
     __shared__ f64x4 Gp[TL * 64];
-    __shared__ P64Slot slots[TL];
+    __shared__ TestSlot<double> slots[TL];
     __shared__ double vsum[2][TL][16];
     __shared__ P64Hand<RELAY> L;
     __shared__ int newinst[16];  // REFILL: the instance each column takes next (-1 none, -2 keeps its own)
@@ -381,7 +370,7 @@ __global__ __launch_bounds__(RELAY ? 1024 : 64 * T) void gpad_panel64_kernel(Sol
             }
             __syncthreads();
             // ---- GEMM 2 + epilogue: y+ = [w + G_L zhat + p_D]+ (8d), next w (8a), test partials ----
-            double violz = -INFINITY, violh = -INFINITY, wmin = INFINITY, magh = 0.0, gap = 0.0;
+            TestPart<double> part;
             {
                 const f64x4 acc = p64_gemm<T, RELAY>(L, PA2, Zh, voff, lane, nkb2, on2, rrole, ++hgen, apre);
                 apre = p64_first_a<T, RELAY>(PA1, voff, lane, on1, rrole);  // the next GEMM 1's
@@ -396,32 +385,15 @@ __global__ __launch_bounds__(RELAY ? 1024 : 64 * T) void gpad_panel64_kernel(Sol
                     if (use_tol) {
                         const double un = __builtin_fma(omt, u[r], th * cv);
                         if (active) u[r] = un;
-                        if (chk && active && (16 * t + 4 * r + j) < m) {
-                            const double tt = cv + pd[r];
-                            violh = fmax(violh, tt);
-                            magh = fmax(magh, fabs(cv) + fabs(pd[r]));
-                            wmin = fmin(wmin, wv[r]);
-                            gap -= wv[r] * tt;
-                            violz = fmax(violz, u[r] + pd[r]);
-                        }
+                        if (chk && active && (16 * t + 4 * r + j) < m) part.row(cv, pd[r], wv[r], u[r]);
                     }
                     if (active) y[r] = yp;
                 }
                 if (active) Wl[slot] = wn;  // (GEMM 2 reads Zh; the next GEMM 1 reads w after the barrier)
             }
             if (chk) {
-                violz = col_max(violz);
-                violh = col_max(violh);
-                magh = col_max(magh);
-                wmin = col_min(wmin);
-                gap = col_sum(gap);
-                if (j == 0) {
-                    slots[t].violz[c] = violz;
-                    slots[t].violh[c] = violh;
-                    slots[t].magh[c] = magh;
-                    slots[t].wmin[c] = wmin;
-                    slots[t].gap[c] = gap;
-                }
+                part.fold();
+                part.put(slots[t], c, j == 0);
             }
             __syncthreads();
             if (REFILL ? !chk : (!chk && v < N)) continue;  // (REFILL: N % K == 0, a column reaches N at a test)
@@ -430,55 +402,30 @@ __global__ __launch_bounds__(RELAY ? 1024 : 64 * T) void gpad_panel64_kernel(Sol
             // ---- Algorithm 1, per column (lane c's column; every wave reads every tile) ----------
             int code = 0;
             if (chk) {
-                int st1 = 0;
-                bool vh_ok = false, w_ok = false;
-                double gq = 0.0;
-                if (active) {
-                    double vz = -INFINITY, vh = -INFINITY, wm = INFINITY, mh = 0.0;
-#pragma unroll
-                    for (int s2 = 0; s2 < T; ++s2) {
-                        vz = fmax(vz, slots[s2].violz[c]);
-                        vh = fmax(vh, slots[s2].violh[c]);
-                        mh = fmax(mh, slots[s2].magh[c]);
-                        wm = fmin(wm, slots[s2].wmin[c]);
-                        gq += slots[s2].gap[c];
-                    }
-                    vh_ok = viol_ok(vh, mh, a.L, a.tol, ViolMargin<double>::value);
-                    w_ok = wm >= 0.0;
-                    st1 = (vz * a.L <= a.tol ? 1 : 0) | ((vh_ok && w_ok && (gq * a.L <= a.tol_gap)) ? 2 : 0);
-                }
-                bool verified = false;
+                Stage1 s1 = {0, false, false, 0.0};
+                if (active) s1 = stage1<double, T>(slots, 0, T, c, a.L, a.tol, a.tol_gap);
+                const int st1 = s1.bits;
+                const bool vh_ok = s1.vh_ok, w_ok = s1.w_ok;
+                const double gq = s1.gq;
+                bool ver = false;
                 if (__syncthreads_or(st1 & 1)) {  // (A) nominated somewhere: G_L z for the panel
                     Xv[slot] = f64x4{z[0], z[1], z[2], z[3]};
                     __syncthreads();
                     const f64x4 cz = on2 ? gemm64<T>(PA2, Xv, voff, lane, nkb2) : f64x4{0.0, 0.0, 0.0, 0.0};
-                    double vc = -INFINITY, mc = 0.0;
+                    VerPart<double> vp;
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
                         if ((st1 & 1) && (16 * t + 4 * r + j) < m) {
                             u[r] = cz[r];  // the recursion restarts from the direct value
-                            vc = fmax(vc, cz[r] + pd[r]);
-                            mc = fmax(mc, fabs(cz[r]) + fabs(pd[r]));
+                            vp.row(cz[r], pd[r]);
                         }
                     }
-                    vc = col_max(vc);
-                    mc = col_max(mc);
-                    if (j == 0) {  // every wave read the stage-1 slots before the barrier above
-                        slots[t].violz[c] = vc;
-                        slots[t].magh[c] = mc;
-                    }
+                    vp.fold();
+                    vp.put(slots[t], c, j == 0);
                     __syncthreads();
-                    if (st1 & 1) {
-                        double vcc = -INFINITY, mcc = 0.0;
-#pragma unroll
-                        for (int s2 = 0; s2 < T; ++s2) {
-                            vcc = fmax(vcc, slots[s2].violz[c]);
-                            mcc = fmax(mcc, slots[s2].magh[c]);
-                        }
-                        verified = viol_ok(vcc, mcc, a.L, a.tol, ViolMargin<double>::value);
-                    }
+                    if (st1 & 1) ver = verified<double, T>(slots, 0, T, c, a.L, a.tol);
                 }
-                code = ((st1 & 1) && verified) ? 1 : ((st1 & 2) ? 2 : 0);
+                code = check_code(st1, ver);
                 // value-function branches (acceldualgrad.m:73, 76) where the MATLAB test reaches them
                 const bool need = value && active && code == 0 && vh_ok;
                 if (value && __syncthreads_or(need)) {

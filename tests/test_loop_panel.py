@@ -126,6 +126,36 @@ def test_one_panel(gpu, oracle, batch):
     check_panel(oracle, "lp34", p, states(p, 37, 7)[:batch], 6, 2000, 1e-4, False, 0)
 
 
+def both_codes_plant(packs=16):
+    """synthetic(12, 56, 3, 3) -- battery(3, 4)'s sizes, T = 4 -- with M0 = -z_f, the generator's strictly
+    feasible point (its first draw; G z_f - g <= -0.1 in every row).  At x = 0 the unconstrained minimiser
+    zhat = -g_P is z_f, so packs with a small state end by test (A) at the first event (code 1), while a
+    large state pushes the minimiser out of the feasible set: active constraints, test (B), code 2."""
+    base = synthetic(12, 56, 3, 3, packs=packs)
+    qp = base.qp
+    zf = np.random.default_rng(2).uniform(-0.5, 0.5, qp.n)  # synthetic_qp(seed=1) draws it from seed + 1
+    assert (np.asarray(qp.G) @ zf - np.asarray(qp.g).reshape(-1)).max() < -0.09, "zf is not the generator's feasible point"
+    scale = np.where(np.arange(packs) % 2 == 0, 0.05, 4.0)
+    X0 = (np.random.default_rng(5).uniform(-1, 1, (packs, 3)) * scale[:, None]).astype(np.float32)
+    return SimpleNamespace(**dict(vars(base), M0=-zf, X0=X0))
+
+
+@pytest.mark.gpu
+def test_both_codes_in_one_panel(gpu, oracle):
+    """One panel of 16 packs whose solves end by test (A) and by test (B) side by side: stage 1, the
+    verification GEMM on the direct G_L z and the code selection of gpad_loop_panel_kernel in one
+    workgroup (the other cases of this module end every solve with code 2).  The reference's own codes
+    -- the lockstep loop's -- hold both in every step."""
+    p = both_codes_plant()
+    cfg = (3, 2000, 1e-4, False)
+    ref = lockstep("lp-codes", p, p.X0, *cfg)
+    for t in range(cfg[0]):
+        assert {1, 2} <= set(ref.cd[t].tolist()), ref.cd[t]
+    assert ref.it.max() < cfg[1]
+    r, _ = check_panel(oracle, "lp-codes", p, p.X0, *cfg, 0)
+    assert {1, 2} <= set(r.cd[0].tolist())
+
+
 @pytest.mark.gpu
 @WARM
 def test_per_pack_plants(gpu, warm):

@@ -640,6 +640,29 @@ def test_seed_f64(gpu, oracle, name, hessian, opts):
 
 
 @pytest.mark.gpu
+def test_seed_f64_both_codes_in_one_panel(gpu, oracle):
+    """The f64 panels on one panel that the oracle ends with code 1 and with code 2 (test_seed_f64's
+    instances all end with code 1): stage 1, the verification GEMM and the code selection in one
+    workgroup, with the Hessian bound (the value-function branches read stage 1's parts).  Sixteen
+    instances of the 40x64 case, the even ones from z_f -- test (A) within two tests -- and the odd ones
+    from z0 = 0 -- test (B).  Counts and codes equal to the fp64 oracle, z*, y* to 1e-11, bit-identical
+    to the f64 stream kernel."""
+    n, m, _, s, K = F64_CASES["40x64"]
+    p = problem(n, m, 40, f64=True)
+    th, be = tables(f"shift{s}", NMAX, True)
+    z0 = np.array(p.zf[:16])
+    z0[1::2] = 0.0
+    ref = oracle_solves(p, z0, NMAX, TOL, K, th, be, H=p.H)
+    assert (ref[3][0::2] == 1).all() and (ref[3][1::2] == 2).all(), ref[3]
+    a = gpu_solve(p, 16, "panel", z0, NMAX, TOL, K, th, be, hessian=True)
+    b = gpu_solve(p, 16, "stream", z0, NMAX, TOL, K, th, be, hessian=True)
+    assert a[4]["kernel"] == "panel" and b[4]["kernel"] == "stream"
+    same(a, ref, "f64 mixed panel", f64=True)
+    for x, y_ in zip(a[:4], b[:4]):
+        np.testing.assert_array_equal(x, y_)
+
+
+@pytest.mark.gpu
 def test_seed_f64_refilled_columns(gpu, oracle):
     """More f64 panels than workgroups with N a multiple of the test period: columns that finish take
     the next instances, whose seed is the refill path's GEMM over the new columns, here with
