@@ -22,8 +22,14 @@
 // The per-instance arithmetic is that of the engines, which is the oracle's whatever the engine, so the
 // results are bit for bit those of the shared = 0 binding of the same fleet.
 //
-// Not in this file: classes running concurrently on several streams (each class pays its own tail per
-// call), exogenous signals, per-pack true plants under a class binding, Hessian branches.
+// The fused class loop (gpad_class_loop_fused, opt-in) replaces the `solve` stage of a closed loop by ONE
+// launch of the class-aware panel loop (gpad_loop_panel.hip) over every class, run through one more handle of
+// the whole batch in the sorted order (fused_create, fused_loop); the trajectories are then one
+// [steps][batch][len] array in the sorted order and the counts and codes come from that handle.  Every other
+// call still pays each class's own tail.
+//
+// Not in this file: classes running concurrently on several streams, exogenous signals, per-pack true
+// plants under a class binding, Hessian branches.
 #include <algorithm>
 #include <cmath>
 
@@ -47,6 +53,24 @@ struct ClassBinding {
     int nx = 0, nu = 0;
     int last_steps = 0;               // solves per instance of the last run (0: no run yet)
     std::vector<int> it, cd;          // one child's counts and codes on their way to the caller
+    // plant maps (classes_setup_plant): PM | M0 | Pg | g0 | A | B on the device, each array one copy per class
+    // (gpad_setup_plant_classes) or one for all; the children bind their copies from here
+    DevBuf maps;
+    size_t map_off[6] = {0, 0, 0, 0, 0, 0};  // element offsets in maps
+    bool map_has[6] = {false, false, false, false, false, false};
+    bool per_class = false;
+    // the fused class loop (gpad_class_loop_fused): every class in one launch of the class-aware panel loop,
+    // run through a handle of the whole batch in the sorted order (shared = 1 with the major class's matrices,
+    // which the launch never reads: it takes every class's fragment image from `frags`).  That handle owns
+    // the run's counters, status block, schedule tables and timing, as any handle does.
+    bool fused_on = false;
+    gpad_handle_t fused = nullptr;    // made the first time the loop is turned on (f32 only)
+    DevBuf mats;                      // f32: the major class's ML | G, kept for that setup
+    DevBuf frags;                     // K fragment images copied from the children
+    DevBuf ftab;                      // ints: off[K + 1] | qctr[K] | start[kAbsmaxMaxBlocks]
+    std::vector<int> start;           // host copy of the start classes dealt for start_grid workgroups
+    int start_grid = 0;
+    bool last_fused = false;          // the last run was the fused loop: its stats are the fused handle's
 
     int count(int k) const { return offsets[k + 1] - offsets[k]; }
     const int* d_perm() const { return (const int*)idx.p; }
@@ -66,11 +90,48 @@ bool class_order(const int* class_of, int batch, int K, int* perm, int* offsets)
     return true;
 }
 
+// The class each workgroup of the fused loop starts on.  First one workgroup for every non-empty class, the
+// classes with the most panels first (a grid below their number leaves the smallest to be reached by
+// switching); then every further workgroup goes where a workgroup has the most panels to serve,
+// panels_k / (dealt_k + 1) the largest (ties: the lowest class) -- the shares so follow the panel counts, and
+// no class holds more workgroups than panels while another is short.  start_class lists class 0's
+// workgroups, then class 1's ...
+bool class_loop_deal(const int* counts, int K, int grid, int* start_class) {
+    std::vector<long long> panels((size_t)K), dealt((size_t)K, 0);
+    std::vector<int> by_size;
+    for (int k = 0; k < K; ++k) {
+        if (counts[k] < 0) return false;
+        panels[k] = ((long long)counts[k] + 15) / 16;
+        if (panels[k]) by_size.push_back(k);
+    }
+    if (by_size.empty()) return false;
+    std::stable_sort(by_size.begin(), by_size.end(), [&](int a, int b) { return panels[a] > panels[b]; });
+    int left = grid;
+    for (size_t i = 0; i < by_size.size() && left > 0; ++i, --left) dealt[by_size[i]] = 1;
+    for (; left > 0; --left) {
+        int best = by_size[0];
+        for (int k : by_size)  // panels_k / (dealt_k + 1) > panels_best / (dealt_best + 1), in integers
+            if (panels[k] * (dealt[best] + 1) > panels[best] * (dealt[k] + 1) ||
+                (panels[k] * (dealt[best] + 1) == panels[best] * (dealt[k] + 1) && k < best))
+                best = k;
+        ++dealt[best];
+    }
+    int w = 0;
+    for (int k = 0; k < K; ++k)
+        for (long long i = 0; i < dealt[k]; ++i) start_class[w++] = k;
+    return true;
+}
+
 void classes_free(ClassBinding* cb) {
     if (!cb) return;
     (void)hipSetDevice(cb->device);
     for (gpad_handle_t c : cb->child)
         if (c) (void)gpad_destroy(c);  // (synchronises the stream first)
+    if (cb->fused) (void)gpad_destroy(cb->fused);
+    cb->maps.release();
+    cb->mats.release();
+    cb->frags.release();
+    cb->ftab.release();
     cb->idx.release();
     cb->sorted.release();
     cb->stage.release();
@@ -138,6 +199,13 @@ static int setup_body(ClassBinding* cb, const Tuning& tune, const void* ML, cons
         if ((rc = gpad_setup(cb->child[k], &cd, dML + mat * k, dG + mat * k, L))) break;  // (synchronises)
         rc = apply_tuning(cb->child[k], tune);
     }
+    if (!rc && d.dtype == GPAD_DTYPE_F32 && !(rc = cb->mats.ensure(2 * mat))) {  // for classes_loop_fused
+        hipError_t e = hipMemcpyAsync(cb->mats.p, dML + mat * cb->major, mat, hipMemcpyDeviceToDevice, cb->stream);
+        if (e == hipSuccess)
+            e = hipMemcpyAsync((char*)cb->mats.p + mat, dG + mat * cb->major, mat, hipMemcpyDeviceToDevice, cb->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(cb->stream);
+        if (e != hipSuccess) rc = fail(GPAD_ERR_HIP, std::string("gpad_setup_classes: matrix copy: ") + hipGetErrorString(e));
+    }
     up.release();
     return rc;
 }
@@ -183,6 +251,8 @@ int classes_set_stream(ClassBinding* cb, hipStream_t stream) {
         const int rc = gpad_set_stream(c, stream);
         if (rc) return rc;
     }
+    if (cb->fused)
+        if (const int rc = gpad_set_stream(cb->fused, stream)) return rc;
     cb->stream = stream;
     return GPAD_OK;
 }
@@ -193,6 +263,75 @@ int classes_set_option(ClassBinding* cb, int option, int value) {
         const int rc = gpad_set_option(c, option, value);
         if (rc) return rc;
     }
+    if (cb->fused) return gpad_set_option(cb->fused, option, value);  // (GPAD_OPT_PANEL_MAX_GRID caps its grid)
+    return GPAD_OK;
+}
+
+// the maps of class k (or the one copy) as the children and the fused handle bind them
+static void class_maps(const ClassBinding* cb, int k, const void* out[6]) {
+    const gpad_dims_t& d = cb->dims;
+    const size_t es = esize(d.dtype);
+    const size_t elems[6] = {(size_t)d.n * cb->nx, (size_t)d.n, (size_t)d.m * cb->nx, (size_t)d.m,
+                             (size_t)cb->nx * cb->nx, (size_t)cb->nx * cb->nu};
+    for (int i = 0; i < 6; ++i)
+        out[i] = cb->map_has[i] ? (const char*)cb->maps.p + es * (cb->map_off[i] + (cb->per_class ? elems[i] * k : 0))
+                                : nullptr;
+}
+
+// The fused handle's plant: it needs nx, nu and which maps are bound; the launch reads the binding's own
+// per-class copies (ClassLoop), so any class's maps do.
+static int fused_bind_plant(ClassBinding* cb) {
+    const void* a[6];
+    class_maps(cb, 0, a);
+    return gpad_setup_plant(cb->fused, cb->nx, cb->nu, a[0], a[1], a[2], a[3], a[4], a[5]);  // (synchronises)
+}
+
+// The whole-batch handle of the fused loop with what its launch reads: the K fragment images (copied from
+// the children, which packed them at gpad_setup) and the offsets table.  f64 bindings have none: their
+// loops always run class by class.
+static int fused_create(ClassBinding* cb, const Tuning& tune) {
+    const gpad_dims_t& d = cb->dims;
+    if (d.dtype != GPAD_DTYPE_F32) return GPAD_OK;
+    gpad_dims_t fd = d;
+    fd.shared = 1;
+    fd.memory = GPAD_MEM_DEVICE;
+    const size_t mat = (size_t)d.n * d.m * sizeof(float);
+    gpad_handle_t f = nullptr;
+    int rc = gpad_create(&f, cb->device, cb->stream);
+    if (!rc) rc = gpad_setup(f, &fd, cb->mats.p, (const char*)cb->mats.p + mat, cb->child[cb->major]->L);
+    if (!rc) rc = apply_tuning(f, tune);
+    const int K = cb->K;
+    const size_t image = f && f->frag_ok && f->frag_tiles >= 1 && f->frag_tiles <= 16
+                             ? (size_t)2 * f->frag_tiles * f->frag_tiles * 1024
+                             : 0;  // (0: not a shape of the panel loop -- every loop falls back)
+    if (!rc && image) rc = cb->frags.ensure(image * K);
+    if (!rc) rc = cb->ftab.ensure(sizeof(int) * ((size_t)2 * K + 1 + kAbsmaxMaxBlocks));
+    hipError_t e = hipSuccess;
+    for (int k = 0; k < K && !rc && image && e == hipSuccess; ++k)
+        if (cb->child[k])
+            e = hipMemcpyAsync((char*)cb->frags.p + image * k, cb->child[k]->frag.p, image, hipMemcpyDeviceToDevice,
+                               cb->stream);
+    if (!rc && e == hipSuccess)
+        e = hipMemcpyAsync(cb->ftab.p, cb->offsets.data(), sizeof(int) * ((size_t)K + 1), hipMemcpyHostToDevice, cb->stream);
+    if (!rc && e == hipSuccess) e = hipStreamSynchronize(cb->stream);
+    if (!rc && e != hipSuccess) rc = fail(GPAD_ERR_HIP, std::string("gpad_class_loop_fused: ") + hipGetErrorString(e));
+    if (rc) {
+        if (f) (void)gpad_destroy(f);
+        return rc;
+    }
+    cb->fused = f;
+    cb->start_grid = 0;
+    if (cb->plant && (rc = fused_bind_plant(cb))) {
+        (void)gpad_destroy(f);
+        cb->fused = nullptr;
+    }
+    return rc;
+}
+
+int classes_loop_fused(ClassBinding* cb, bool on, const Tuning& tune) {
+    if (on && !cb->fused)
+        if (const int rc = fused_create(cb, tune)) return rc;
+    cb->fused_on = on;
     return GPAD_OK;
 }
 
@@ -208,48 +347,43 @@ int classes_setup_plant(ClassBinding* cb, bool per_class, int nx, int nu, const 
     const void* src[6] = {PM, M0, Pg, g0, A, B};
     const size_t elems[6] = {(size_t)d.n * nx, (size_t)d.n, (size_t)d.m * nx, (size_t)d.m, (size_t)nx * nx,
                              (size_t)nx * nu};
-    const char* dev[6];
-    DevBuf up;
-    if (d.memory == GPAD_MEM_HOST) {  // the children take device pointers
-        size_t total = 0;
-        for (int i = 0; i < 6; ++i) total += src[i] ? elems[i] * copies : 0;
-        int rc = up.ensure(es * total);
-        if (rc) return rc;
-        size_t off = 0;
-        hipError_t e = hipSuccess;
-        for (int i = 0; i < 6 && e == hipSuccess; ++i) {
-            dev[i] = src[i] ? (const char*)up.p + es * off : nullptr;
-            if (!src[i] || elems[i] == 0) continue;
-            e = hipMemcpyAsync((char*)up.p + es * off, src[i], es * elems[i] * copies, hipMemcpyHostToDevice, cb->stream);
-            off += elems[i] * copies;
-        }
-        if (e == hipSuccess) e = hipStreamSynchronize(cb->stream);
-        if (e != hipSuccess) {
-            up.release();
-            return fail(GPAD_ERR_HIP, std::string(fn) + ": map upload: " + hipGetErrorString(e));
-        }
-    } else {
-        for (int i = 0; i < 6; ++i) dev[i] = (const char*)src[i];
-    }
+    // the maps on the device, kept: the children bind their copies from here, the fused loop reads them in place
+    size_t total = 0;
+    for (int i = 0; i < 6; ++i) total += src[i] ? elems[i] * copies : 0;
     cb->plant = false;  // (a failed rebinding leaves none)
-    int rc = GPAD_OK;
+    int rc = cb->maps.ensure(es * total);
+    if (rc) return rc;
+    const hipMemcpyKind kind = d.memory == GPAD_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
+    size_t off = 0;
+    hipError_t e = hipSuccess;
+    for (int i = 0; i < 6 && e == hipSuccess; ++i) {
+        cb->map_has[i] = src[i] != nullptr;
+        cb->map_off[i] = off;
+        if (!src[i] || elems[i] == 0) continue;
+        e = hipMemcpyAsync((char*)cb->maps.p + es * off, src[i], es * elems[i] * copies, kind, cb->stream);
+        off += elems[i] * copies;
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(cb->stream);
+    if (e != hipSuccess) return fail(GPAD_ERR_HIP, std::string(fn) + ": map upload: " + hipGetErrorString(e));
+    cb->per_class = per_class;
+    cb->nx = nx;
+    cb->nu = nu;
     for (int k = 0; k < cb->K && !rc; ++k) {
         if (!cb->child[k]) continue;
         const void* a[6];
-        for (int i = 0; i < 6; ++i) a[i] = dev[i] ? dev[i] + (per_class ? es * elems[i] * k : 0) : nullptr;
+        class_maps(cb, k, a);
         rc = gpad_setup_plant(cb->child[k], nx, nu, a[0], a[1], a[2], a[3], a[4], a[5]);  // (synchronises)
     }
-    up.release();
+    if (!rc && cb->fused) rc = fused_bind_plant(cb);
     if (rc) return rc;
     cb->plant = true;
     cb->plant_dyn = A != nullptr;
-    cb->nx = nx;
-    cb->nu = nu;
     return GPAD_OK;
 }
 
 // The stats of the last run from every child (each call synchronises the stream and reports that child's
-// device error word); counts and codes placed in the caller's order.
+// device error word); counts and codes placed in the caller's order.  After a fused loop the whole-batch
+// handle is the one "child", of every sorted position.
 int classes_last_stats(ClassBinding* cb, gpad_stats_t* st) {
     if (cb->last_steps <= 0) return fail(GPAD_ERR_NOT_SETUP, "gpad_last_stats: no run yet");
     const int batch = cb->dims.batch, steps = cb->last_steps;
@@ -262,9 +396,10 @@ int classes_last_stats(ClassBinding* cb, gpad_stats_t* st) {
     st->flags = 0;
     int first_err = GPAD_OK;
     std::string first_msg;
-    for (int k = 0; k < cb->K; ++k) {
-        if (!cb->child[k]) continue;
-        const int cnt = cb->count(k), off = cb->offsets[k];
+    for (int k = 0; k < (cb->last_fused ? 1 : cb->K); ++k) {
+        const gpad_handle_t c = cb->last_fused ? cb->fused : cb->child[k];
+        if (!c) continue;
+        const int cnt = cb->last_fused ? batch : cb->count(k), off = cb->last_fused ? 0 : cb->offsets[k];
         gpad_stats_t cs{};
         if (st->iters) {
             cb->it.resize((size_t)steps * cnt);
@@ -274,7 +409,7 @@ int classes_last_stats(ClassBinding* cb, gpad_stats_t* st) {
             cb->cd.resize((size_t)steps * cnt);
             cs.codes = cb->cd.data();
         }
-        const int rc = gpad_last_stats(cb->child[k], &cs);
+        const int rc = gpad_last_stats(c, &cs);
         if (rc && rc != GPAD_ERR_DEVICE) return rc;
         if (rc && !first_err) {  // every child is still asked: each reports (and clears) its own word
             first_err = rc;
@@ -285,7 +420,7 @@ int classes_last_stats(ClassBinding* cb, gpad_stats_t* st) {
         st->total_iterations += cs.total_iterations;
         if (std::isnan(cs.tol_floor) || cs.tol_floor > st->tol_floor) st->tol_floor = cs.tol_floor;
         st->flags |= cs.flags;
-        if (k == cb->major) st->kernel = cs.kernel;
+        if (cb->last_fused || k == cb->major) st->kernel = cs.kernel;
         for (int t = 0; t < steps; ++t)
             for (int i = 0; i < cnt; ++i) {
                 const size_t to = (size_t)t * batch + cb->perm[(size_t)off + i], from = (size_t)t * cnt + i;
@@ -299,10 +434,12 @@ int classes_last_stats(ClassBinding* cb, gpad_stats_t* st) {
     return GPAD_OK;
 }
 
+// (the handles that ran last report: the children, or after a fused loop the whole-batch handle)
 int classes_sync(ClassBinding* cb) {
     int first_err = GPAD_OK;
     std::string first_msg;
-    for (gpad_handle_t c : cb->child) {
+    for (int k = 0; k < (cb->last_fused ? 1 : cb->K); ++k) {
+        const gpad_handle_t c = cb->last_fused ? cb->fused : cb->child[k];
         if (!c) continue;
         const int rc = gpad_sync(c);
         if (rc && rc != GPAD_ERR_DEVICE) return rc;
@@ -317,6 +454,7 @@ int classes_sync(ClassBinding* cb) {
 
 int classes_accumulate(ClassBinding* cb, long long* acc) {
     if (cb->last_steps <= 0) return fail(GPAD_ERR_NOT_SETUP, "gpad_accumulate_iterations: no run yet");
+    if (cb->last_fused) return gpad_accumulate_iterations(cb->fused, acc);
     for (gpad_handle_t c : cb->child) {
         if (!c) continue;
         const int rc = gpad_accumulate_iterations(c, acc);
@@ -372,6 +510,7 @@ static int run_typed(ClassBinding* cb, T* z, T* y, const T* M, const T* g, int N
     }
     HIP_TRY(launch_class_gather<T>(in, cb->d_perm(), d.batch, cb->stream));
     cb->last_steps = 1;
+    cb->last_fused = false;
     cb->timed = false;
     for (int k = 0; k < cb->K; ++k) {
         if (!cb->child[k]) continue;
@@ -408,12 +547,60 @@ int classes_run(ClassBinding* cb, void* z, void* y, const void* M, const void* g
     return run_typed<float>(cb, (float*)z, (float*)y, (const float*)M, (const float*)g, N, tol, st);
 }
 
+// The fused class loop: gpad_closed_loop of the whole-batch handle on the sorted arrays, with the class tables
+// attached for the length of the call.  Grid: loop_panel_grid's rule on the classes' panels,
+// min(sum_k ceil(count_k / 16), resident workgroups, kAbsmaxMaxBlocks) capped by GPAD_OPT_PANEL_MAX_GRID.
+static int fused_loop(ClassBinding* cb, float* sx, float* sz, float* sy, int steps, int N, double tol, int warm,
+                      float* sxs, float* sus) {
+    const gpad_dims_t& d = cb->dims;
+    const gpad_handle_t f = cb->fused;
+    const int K = cb->K;
+    std::vector<int> counts((size_t)K);
+    long long panels = 0;
+    for (int k = 0; k < K; ++k) panels += ((counts[k] = cb->count(k)) + 15) / 16;
+    // (a batch of 16 * panels instances has exactly that many panels)
+    const int grid = loop_panel_grid(d.n, d.m, (int)std::min<long long>(16 * panels, 0x7ffffff0), f->num_cus, &f->tune);
+    int* tab = (int*)cb->ftab.p;  // off[K + 1] | qctr[K] | start[kAbsmaxMaxBlocks]
+    if (grid != cb->start_grid) {
+        cb->start.resize(kAbsmaxMaxBlocks);  // (never reallocated: a copy may still be reading it)
+        if (!class_loop_deal(counts.data(), K, grid, cb->start.data()))
+            return fail(GPAD_ERR_INVALID, "gpad_closed_loop: class loop: no workgroups to deal");
+        HIP_TRY(hipMemcpyAsync(tab + 2 * (size_t)K + 1, cb->start.data(), sizeof(int) * (size_t)grid,
+                               hipMemcpyHostToDevice, cb->stream));
+        cb->start_grid = grid;
+    }
+    const void* maps[6];
+    class_maps(cb, 0, maps);  // (class 0's copy is where each array starts)
+    ClassLoop cl{};
+    cl.K = K;
+    cl.grid = grid;
+    cl.off = tab;
+    cl.qctr = tab + K + 1;
+    cl.start = tab + 2 * (size_t)K + 1;
+    cl.frag = cb->frags.p;
+    cl.per_class = cb->per_class ? 1 : 0;
+    cl.PM = (const float*)maps[0];
+    cl.M0 = (const float*)maps[1];
+    cl.Pg = (const float*)maps[2];
+    cl.g0 = (const float*)maps[3];
+    cl.A = (const float*)maps[4];
+    cl.B = (const float*)maps[5];
+    f->cloop = &cl;
+    const int rc = gpad_closed_loop(f, sx, sz, sy, steps, N, tol, warm, sxs, sus, nullptr);
+    f->cloop = nullptr;
+    return rc;
+}
+
 template <typename T>
 static int state_typed(ClassBinding* cb, T* x, T* z, T* y, int steps, int N, double tol, int warm, T* xs, T* us,
                        gpad_stats_t* st) {
     const gpad_dims_t& d = cb->dims;
     const int nx = cb->nx, nu = cb->nu;
     const bool loop = steps > 0, host = d.memory == GPAD_MEM_HOST;
+    // gpad_class_loop_fused: a loop of a shape the panel loop takes runs as one launch over every class; any
+    // other call runs class by class as if it were off (as the loop options do)
+    const bool fused = loop && cb->fused_on && cb->fused && sizeof(T) == sizeof(float) &&
+                       loop_panel_shape(cb->fused, N, tol, nx);
     const bool zy_in = !loop || warm;  // a cold loop starts every step from z = y = 0: nothing to bring in
     const size_t batch = (size_t)d.batch, zn = batch * d.n, yn = batch * d.m, xn = batch * nx;
     const size_t xsn = loop && xs ? (size_t)steps * xn : 0, usn = loop && us ? (size_t)steps * batch * nu : 0;
@@ -454,7 +641,11 @@ static int state_typed(ClassBinding* cb, T* x, T* z, T* y, int steps, int N, dou
     HIP_TRY(launch_class_gather<T>(in, cb->d_perm(), d.batch, cb->stream));
     cb->last_steps = loop ? steps : 1;
     cb->timed = false;
-    for (int k = 0; k < cb->K; ++k) {
+    cb->last_fused = fused;
+    if constexpr (sizeof(T) == sizeof(float)) {
+        if (fused && (rc = fused_loop(cb, sx, sz, sy, steps, N, tol, warm, sxs, sus))) return rc;
+    }
+    for (int k = 0; k < cb->K && !fused; ++k) {
         if (!cb->child[k]) continue;
         const size_t off = (size_t)cb->offsets[k];
         T *kx = sx + off * nx, *kz = sz + off * d.n, *ky = sy + off * d.m;
@@ -490,8 +681,9 @@ static int state_typed(ClassBinding* cb, T* x, T* z, T* y, int steps, int N, dou
             tr.dst[tr.count] = cus;
             tr.len[tr.count++] = nu;
         }
-        HIP_TRY(launch_class_traj_scatter<T>(tr, cb->d_perm(), cb->d_pos_off(), cb->d_pos_cnt(), d.batch, steps,
-                                           cb->stream));
+        // (the fused loop wrote one [steps][batch][len] array in the sorted order, not a block per class)
+        HIP_TRY(launch_class_traj_scatter<T>(tr, cb->d_perm(), fused ? nullptr : cb->d_pos_off(),
+                                           fused ? nullptr : cb->d_pos_cnt(), d.batch, steps, cb->stream));
     }
     HIP_TRY(hipEventRecord(cb->ev1, cb->stream));
     cb->timed = true;

@@ -3,7 +3,8 @@
 // here at their top), gpad_classes.cpp (the runtime) and gpad_classes.hip (the row permutations).
 //
 // Not here: classes running concurrently on several streams (they run one after the other on the
-// handle's stream), exogenous signals, per-pack true plants under a class binding, Hessian branches.
+// handle's stream; a closed loop can run them as one launch, gpad_class_loop_fused), exogenous signals,
+// per-pack true plants under a class binding, Hessian branches.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -38,9 +39,28 @@ struct TrajMove {
     int len[2];
     int count;
 };
+// pos_off == pos_cnt == null: src is one [steps][batch][len] array in the sorted order (the fused class loop)
 template <typename T>
 hipError_t launch_class_traj_scatter(const TrajMove<T>& mv, const int* perm, const int* pos_off,
                                      const int* pos_cnt, int batch, int steps, hipStream_t s);
+
+// ---- the fused class loop (gpad_class_loop_fused) ---------------------------------------------------
+// What one launch of the class-aware panel loop (gpad_loop_panel.hip) needs beyond a plain closed loop of
+// the whole batch in the sorted order.  gpad_classes.cpp attaches it to the binding's whole-batch handle
+// (gpad_handle_s::cloop) for the length of one gpad_closed_loop call; gpad_state.cpp reads it.  All
+// pointers are device memory.
+struct ClassLoop {
+    int K, grid;
+    const int* off;    // [K + 1] offsets of the sorted order
+    const int* start;  // [grid] the class each workgroup starts on (class_loop_deal)
+    int* qctr;         // [K] claim counters
+    const void* frag;  // K fragment images, class k's at k * 2 * T * T * 1024 bytes
+    int per_class;     // 1: K copies of every map, 0: one
+    const float *PM, *M0, *Pg, *g0, *A, *B;  // (M0, g0: null when not bound)
+};
+// Host only (gpad_class_loop_deal): the class each of `grid` workgroups starts on, in proportion to the
+// classes' panel counts; false on a negative count or when every class is empty
+bool class_loop_deal(const int* counts, int K, int grid, int* start_class);
 
 // ---- gpad_classes.cpp -------------------------------------------------------------------------------
 // Host only: perm / offsets of the class-sorted order (gpad_class_order); false on an id outside 0..K-1
@@ -54,6 +74,9 @@ int classes_setup(ClassBinding** out, int device, hipStream_t stream, const Tuni
 void classes_free(ClassBinding* cb);
 int classes_set_stream(ClassBinding* cb, hipStream_t stream);
 int classes_set_option(ClassBinding* cb, int option, int value);
+// gpad_class_loop_fused: turns the fused class loop on or off (tune: the parent's options, for the
+// whole-batch handle made the first time it is turned on)
+int classes_loop_fused(ClassBinding* cb, bool on, const Tuning& tune);
 // per_class: every non-NULL map holds K copies (gpad_setup_plant_classes), else one for every class
 int classes_setup_plant(ClassBinding* cb, bool per_class, int nx, int nu, const void* PM, const void* M0,
                         const void* Pg, const void* g0, const void* A, const void* B);

@@ -70,7 +70,8 @@ __global__ __launch_bounds__(256) void class_traj_kernel(TrajMove<T> mv, const i
         T* dst;
         int len, j;
         locate<T>(mv, (int)(r - (long long)pos * row), src, dst, len, j);
-        const long long off = pos_off[pos], cnt = pos_cnt[pos];
+        // (no tables: one block [steps][batch][len] of every class, the fused class loop's)
+        const long long off = pos_off ? pos_off[pos] : 0, cnt = pos_cnt ? pos_cnt[pos] : batch;
         // class block [steps][cnt][len] at steps * off * len; row (t, pos - off)
         const long long from = ((long long)steps * off + (long long)t * cnt + (pos - off)) * len + j;
         const long long to = ((long long)t * batch + perm[pos]) * len + j;

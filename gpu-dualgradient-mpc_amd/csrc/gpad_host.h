@@ -190,6 +190,8 @@ struct gpad_handle_s {
     gpad::Tuning tune;                  // gpad_set_option
     gpad::ClassBinding* cls = nullptr;  // gpad_setup_classes: the class binding (gpad_classes.cpp), which then
                                         // serves the handle's runs; null: none
+    const gpad::ClassLoop* cloop = nullptr;  // set by a class binding on its whole-batch handle around one
+                                        // gpad_closed_loop call: that call is the fused class loop
     bool failed_run = false;            // the last run's device error was reported (fetch_status
                                         // clears the device word): later stats calls for that
                                         // run keep returning GPAD_ERR_DEVICE until the next run
@@ -210,6 +212,11 @@ int validate_dims(const gpad_dims_t* d);
 // the fragment images' validity, gpad_solve's shadow, and what was planned or predicted from its solves
 void unbind_problem(gpad_handle_t h);
 int ensure_schedule(gpad_handle_t h, int N, const void* theta_in, const void* beta_in);
+
+// ---- gpad_state.cpp ---------------------------------------------------------------------------------
+// the shape rules of GPAD_OPT_LOOP_PANEL for a closed loop of h's problem and plant (the option itself aside):
+// what the fused class loop asks of its whole-batch handle
+bool loop_panel_shape(gpad_handle_t h, int N, double tol, int nxa);
 
 // ---- gpad_run.cpp -----------------------------------------------------------------------------------
 // the counts of a finished solve: the next phased solve's plan / the f64 panels' next start order

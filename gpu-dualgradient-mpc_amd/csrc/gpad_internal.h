@@ -182,6 +182,12 @@ struct LoopArgs {
     // [nx][nx + ns] = [A E]; the slot's LDS state row holds [x_t; S[t][pack]]
     int ns;
     const float* S;        // [steps][batch][ns]
+    // the class loop (launch_loop_panel only; cls_K == 0: none): batch positions in the class-sorted
+    // order, class k at cls_off[k] .. cls_off[k+1]-1; s.frag = K fragment images one after the other,
+    // s.qctr = K claim counters (zeroed by the caller), per_plant = one copy of the maps per class
+    int cls_K;
+    const int* cls_off;    // device [K + 1]
+    const int* cls_start;  // device [grid]: the class workgroup b starts on (never an empty one)
 };
 // nx: columns of the state row, nx + ns with signals bound
 bool loop_supported(int n, int m, int nx, int nu);
@@ -198,7 +204,8 @@ hipError_t launch_loop(const LoopArgs& a, int grid, hipStream_t s);
 bool loop_panel_supported(int n, int m, int nx, int nu);
 // min(panels, resident workgroups), capped by Tuning::panel_max_grid and kAbsmaxMaxBlocks
 int loop_panel_grid(int n, int m, int batch, int num_cus, const Tuning* t);
-// persistent grid of `grid` <= min(ceil(batch / 16), kAbsmaxMaxBlocks) workgroups
+// persistent grid of `grid` <= min(ceil(batch / 16), kAbsmaxMaxBlocks) workgroups; with a.cls_K set the
+// class loop, grid <= min(sum_k ceil(count_k / 16), kAbsmaxMaxBlocks)
 hipError_t launch_loop_panel(const LoopArgs& a, int grid, hipStream_t s);
 // f64 panels on the f64 MFMA pipe (gpad_panel64.hip): shared matrices, n, m <= 256, one panel of 16
 // instances per workgroup, value-function branches when a.hfrag64 is set; a.frag = the -ML | G_L

@@ -21,6 +21,18 @@
 // change step only at events, so every column's vc = v (mod check_every) for the workgroup's
 // iteration counter v and the iteration limit falls on an event; with fixed N all columns of a
 // workgroup start together and reach N together.
+//
+// The class loop (gpad_class_loop_fused on a class-bound handle, gpad_classes.cpp) is the same body with
+// kCls set: one launch serves every plant class.  Packs are addressed in the class-sorted order, class k
+// at positions off[k] .. off[k+1]-1, with one fragment image, one copy of the plant maps and one claim
+// counter per class.  A workgroup serves one class kc at a time -- all 16 columns hold packs of kc, the
+// two buffer descriptors are kc's -- and where the plain kernel ends (no column active) it looks for
+// work in another class: the classes are scanned cyclically from kc + 1, at the first whose counter is
+// below its count one lane claims 16 positions with one atomicAdd (positions past the count are empty
+// columns), and all columns restart together exactly as at the kernel's start, which is the same
+// mechanism on the class the host dealt (LoopArgs::cls_start).  A full cycle with nothing claimed ends
+// the workgroup.  The columns restart together, so events stay workgroup-uniform by the argument above,
+// and no workgroup waits for another: the scan is bounded by K.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -66,9 +78,10 @@ __host__ __device__ inline bool lp_tab_in_lds(int N, int nxa, int nu) {
 
 }  // namespace
 
-template <int T>
+template <int T, bool kCls = false>
 __global__ __launch_bounds__(64 * T) void gpad_loop_panel_kernel(LoopArgs la) {
     __shared__ LoopPanelLds<T> L;
+    __shared__ int lp_sw[2];  // class loop only: the class the workgroup takes next (-1: none), its claimed base
     extern __shared__ __attribute__((aligned(16))) float lp_dyn[];
     const SolveArgs<float>& a = la.s;
 
@@ -78,9 +91,10 @@ __global__ __launch_bounds__(64 * T) void gpad_loop_panel_kernel(LoopArgs la) {
     const int n = a.n, m = a.m, N = a.N, batch = a.batch;
     const int nx = la.nx, nxa = la.nx + la.ns, nu = la.nu, steps = la.steps;
     const int abytes = T * T * 1024;  // one packed operand
-    const __amdgpu_buffer_rsrc_t PA1 =
+    // (class loop: rebuilt from class kc's image, the K images 2 * abytes apart, whenever kc changes)
+    __amdgpu_buffer_rsrc_t PA1 =
         __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(a.frag), 0, abytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t PA2 = __builtin_amdgcn_make_buffer_rsrc(
+    __amdgpu_buffer_rsrc_t PA2 = __builtin_amdgcn_make_buffer_rsrc(
         (void*)((const char*)a.frag + abytes), 0, abytes, 0x00020000);
     const int voff = t * 1024 + lane * 16;
     const int slot = t * 64 + lane;  // this lane's float4 in Wl / Zh / Gp / Pd
@@ -120,8 +134,36 @@ __global__ __launch_bounds__(64 * T) void gpad_loop_panel_kernel(LoopArgs la) {
     float th = 0.0f, bn = 0.0f;
     float gm = 0.0f;  // NaN-keeping max |g| of every g row this lane formed
     // the start is a boundary at which every column with a pack is refilled (static start: column c
-    // of workgroup b takes pack 16 b + c; later packs are claimed from the counter, from 16 grid on)
+    // of workgroup b takes pack 16 b + c; later packs are claimed from the counter, from 16 grid on;
+    // the class loop has no static start: enter_class below)
     bool fin = active, was_last = true, first = true;
+    // class loop: the workgroup's class, its first sorted position and its size (workgroup-uniform)
+    int kc = 0, cb0 = 0, cnt = batch;
+    // the workgroup takes class k with the 16 positions base .. base + 15 of it; every column restarts
+    auto enter_class = [&](int k, int base) {
+        kc = k;
+        cb0 = la.cls_off[k];
+        cnt = la.cls_off[k + 1] - cb0;
+        const char* f = (const char*)a.frag + (size_t)k * 2 * (size_t)abytes;
+        PA1 = __builtin_amdgcn_make_buffer_rsrc((void*)f, 0, abytes, 0x00020000);
+        PA2 = __builtin_amdgcn_make_buffer_rsrc((void*)(f + abytes), 0, abytes, 0x00020000);
+        pk = base + c < cnt ? cb0 + base + c : batch;
+        ts = 0;
+        vc = 0;
+        active = pk < batch;
+        fin = active;
+        was_last = true;
+        first = true;
+    };
+    if constexpr (kCls) {  // the class the host dealt; its first 16 packs come from the class's queue too
+        if (tid == 0) {
+            const int k = la.cls_start[blockIdx.x];
+            lp_sw[0] = k;
+            lp_sw[1] = atomicAdd(a.qctr + k, 16);
+        }
+        __syncthreads();
+        enter_class(__builtin_amdgcn_readfirstlane(lp_sw[0]), __builtin_amdgcn_readfirstlane(lp_sw[1]));
+    }
     if (t == 0 && j == 0) {
         L.col[c].pack = -1;
         L.col[c].t = 0;
@@ -216,13 +258,18 @@ __global__ __launch_bounds__(64 * T) void gpad_loop_panel_kernel(LoopArgs la) {
                 const bool want = fin && was_last && j == 0;
                 const unsigned long long lv = __ballot(want);
                 int base = 0;
-                if (lane == 0 && lv) base = atomicAdd(a.qctr, (int)__popcll(lv));
+                if (lane == 0 && lv) base = atomicAdd(a.qctr + kc, (int)__popcll(lv));
                 base = __shfl(base, 0, 64);
                 if (j == 0) {
                     int np = -1;
                     if (want) {
-                        np = 16 * (int)gridDim.x + base + (int)__popcll(lv & ((1ull << lane) - 1ull));
-                        if (np > batch) np = batch;
+                        np = base + (int)__popcll(lv & ((1ull << lane) - 1ull));
+                        if constexpr (kCls) {  // the next position of class kc, or none left in it
+                            np = np < cnt ? cb0 + np : batch;
+                        } else {
+                            np += 16 * (int)gridDim.x;
+                            if (np > batch) np = batch;
+                        }
                     }
                     L.col[c].pack = fin ? pk : -1;
                     L.col[c].t = ts;
@@ -240,7 +287,7 @@ __global__ __launch_bounds__(64 * T) void gpad_loop_panel_kernel(LoopArgs la) {
                 const float* xc = X + ((tc & 1) * 16 + col) * nxa;
                 float* xn = X + (((tc + 1) & 1) * 16 + col) * nxa;
                 if (row < nx) {
-                    const size_t pi = la.per_plant ? (size_t)pc : 0;
+                    const size_t pi = la.per_plant ? (size_t)(kCls ? kc : pc) : 0;  // (class loop: a copy per class)
                     const float* Ar = la.A + (pi * nx + row) * nxa;
                     const float* Br = la.B + (pi * nx + row) * nu;
                     float acc = 0.0f;
@@ -299,7 +346,7 @@ __global__ __launch_bounds__(64 * T) void gpad_loop_panel_kernel(LoopArgs la) {
             // M(x), g(x) of this lane's rows (affine2_kernel's order): acc = c0[i] (0 if absent), then
             // fma(P[i][k], x[k], acc) for ascending k over the nx + ns columns
             const float* xr = X + ((ts & 1) * 16 + c) * nxa;
-            const size_t pi = la.per_plant ? (size_t)pk : 0;
+            const size_t pi = la.per_plant ? (size_t)(kCls ? kc : pk) : 0;
             const float b0 = btp[0];
             float gp[4], pd[4], w[4];
 #pragma unroll
@@ -344,7 +391,36 @@ __global__ __launch_bounds__(64 * T) void gpad_loop_panel_kernel(LoopArgs la) {
             }
         }
         fin = false;
-        if (!__syncthreads_or(active ? 1 : 0)) break;  // (also publishes Wl, Gp, Pd; Zh free)
+        if (!__syncthreads_or(active ? 1 : 0)) {  // (also publishes Wl, Gp, Pd; Zh free)
+            if constexpr (!kCls) {
+                break;
+            } else {
+                // class kc has nothing left for this workgroup: on to the next class with unclaimed packs
+                if (tid == 0) {
+                    int nk = -1, base = 0;
+                    for (int i = 1; i < la.cls_K && nk < 0; ++i) {
+                        const int k = kc + i < la.cls_K ? kc + i : kc + i - la.cls_K;
+                        const int ck = la.cls_off[k + 1] - la.cls_off[k];
+                        if (__hip_atomic_load(a.qctr + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= ck) continue;
+                        base = atomicAdd(a.qctr + k, 16);
+                        if (base < ck) nk = k;  // (else other workgroups took the last ones meanwhile)
+                    }
+                    lp_sw[0] = nk;
+                    lp_sw[1] = base;
+                }
+                __syncthreads();
+                const int nk = __builtin_amdgcn_readfirstlane(lp_sw[0]);
+                if (nk < 0) break;
+                enter_class(nk, __builtin_amdgcn_readfirstlane(lp_sw[1]));
+                ke = period;
+                if (t == 0 && j == 0) {
+                    L.col[c].pack = -1;
+                    L.col[c].t = 0;
+                    L.col[c].refill = active ? pk : -1;
+                }
+                __syncthreads();  // L.col published (and lp_sw read by every wave)
+            }
+        }
     }
 
     // the run's max |g| (the certification floor): this workgroup's slot, workgroup 0 zeroes the rest
@@ -383,7 +459,8 @@ static hipError_t launch_loop_panel_t(const LoopArgs& a, int grid, hipStream_t s
     const int nxa = a.nx + a.ns;
     size_t dyn = sizeof(float) * (size_t)lp_state_words(nxa, a.nu);
     if (lp_tab_in_lds<T>(s.N, nxa, a.nu)) dyn += sizeof(float) * 2 * ((size_t)s.N + 2);
-    hipLaunchKernelGGL((gpad_loop_panel_kernel<T>), dim3(grid), dim3(64 * T), dyn, st, a);
+    if (a.cls_K) hipLaunchKernelGGL((gpad_loop_panel_kernel<T, true>), dim3(grid), dim3(64 * T), dyn, st, a);
+    else hipLaunchKernelGGL((gpad_loop_panel_kernel<T>), dim3(grid), dim3(64 * T), dyn, st, a);
     return hipGetLastError();
 }
 
@@ -393,7 +470,10 @@ hipError_t launch_loop_panel(const LoopArgs& a, int grid, hipStream_t st) {
     if (!T || !s.frag || s.frag_tiles != T || s.strideA || s.strideB ||
         !loop_panel_supported(s.n, s.m, a.nx + a.ns, a.nu) || a.nx < 1 || a.ns < 0 || (a.ns && !a.S) || !s.qctr ||
         s.N < 1 || a.steps < 1 || s.batch < 1 || s.check_every < 1 || (s.tol > 0.0 && s.N % s.check_every != 0) ||
-        grid < 1 || grid > (s.batch + 15) / 16 || grid > kAbsmaxMaxBlocks)
+        grid < 1 || grid > kAbsmaxMaxBlocks || a.cls_K < 0)
+        return hipErrorInvalidValue;
+    // the class loop: at most one workgroup per panel of a class (at most batch), the tables given, no signals
+    if (a.cls_K ? (!a.cls_off || !a.cls_start || a.ns || grid > s.batch) : grid > (s.batch + 15) / 16)
         return hipErrorInvalidValue;
     switch (T) {
         case 1: return launch_loop_panel_t<1>(a, grid, st);

@@ -137,6 +137,26 @@ extern "C" int gpad_setup_plant_classes(gpad_handle_t h, int nx, int nu, const v
     });
 }
 
+extern "C" int gpad_class_loop_fused(gpad_handle_t h, int on) {
+    return gpad::abi_guard("gpad_class_loop_fused", [&]() -> int {
+        if (!h) return fail(GPAD_ERR_INVALID, "gpad_class_loop_fused: null handle");
+        if (on != 0 && on != 1) return fail(GPAD_ERR_INVALID, "gpad_class_loop_fused: on must be 0 or 1");
+        if (!h->cls) return fail(GPAD_ERR_NOT_SETUP, "gpad_class_loop_fused: call gpad_setup_classes first");
+        HIP_TRY(hipSetDevice(h->device));
+        return gpad::classes_loop_fused(h->cls, on != 0, h->tune);
+    });
+}
+
+extern "C" int gpad_class_loop_deal(const int* counts, int K, int grid, int* start_class) {
+    return gpad::abi_guard("gpad_class_loop_deal", [&]() -> int {
+        if (!counts || !start_class) return fail(GPAD_ERR_INVALID, "gpad_class_loop_deal: null argument");
+        if (K < 1 || grid < 1) return fail(GPAD_ERR_INVALID, "gpad_class_loop_deal: K and grid must be >= 1");
+        if (!gpad::class_loop_deal(counts, K, grid, start_class))
+            return fail(GPAD_ERR_INVALID, "gpad_class_loop_deal: a negative count, or every class empty");
+        return GPAD_OK;
+    });
+}
+
 static bool plant_bound(gpad_handle_t h) {
     return h->plant_ready && h->plant_n == h->dims.n && h->plant_m == h->dims.m && h->plant_dtype == h->dims.dtype &&
            !(h->plant_batch && h->plant_batch != h->dims.batch);
@@ -260,7 +280,27 @@ static int state_work(gpad_handle_t h, T* z, T* y, const T* sg, int steps, T* xs
     w->M0 = h->has_M0 ? P + o.M0 : nullptr;
     w->g0 = h->has_g0 ? P + o.g0 : nullptr;
     w->B = P + o.B;
+    if constexpr (sizeof(T) == sizeof(float)) {
+        if (const gpad::ClassLoop* cl = h->cloop) {  // the fused class loop: the binding's maps, a copy per class
+            w->per_plant = cl->per_class != 0;
+            w->mPM = cl->PM;
+            w->mPg = cl->Pg;
+            w->mA = cl->A;
+            w->M0 = cl->M0;
+            w->g0 = cl->g0;
+            w->B = cl->B;
+        }
+    }
     return GPAD_OK;
+}
+
+// The shape rules of GPAD_OPT_LOOP_PANEL: shared matrices with a fragment image of at most 16 tiles; with a
+// tolerance the iteration limit must fall on a test (the kernel's events are workgroup-uniform).
+bool loop_panel_shape(gpad_handle_t h, int N, double tol, int nxa) {
+    const gpad_dims_t& d = h->dims;
+    return d.shared && h->frag_ok && h->frag_tiles >= 1 && h->frag_tiles <= 16 && !h->flat && !h->hess_ok && N >= 1 &&
+           (d.kernel == GPAD_KERNEL_AUTO || d.kernel == GPAD_KERNEL_PANEL) &&
+           (!(tol > 0.0) || N % d.check_every == 0) && gpad::loop_panel_supported(d.n, d.m, nxa, h->nu);
 }
 
 // Which one-launch engine serves a closed loop of an f32 handle: GPAD_KERNEL_LOOP_PANEL, GPAD_KERNEL_LOOP, or
@@ -268,16 +308,14 @@ static int state_work(gpad_handle_t h, T* z, T* y, const T* sg, int steps, T* xs
 // GPAD_OPT_LOOP_ASYNC: the whole loop in one launch of gpad_loop_kernel, every pack stepping on
 // its own (gpad_loop.hip).  Anything it does not cover runs the lockstep loop.
 // (per-instance matrices: its solo variant, where the resident kernel holds the shape)
-// GPAD_OPT_LOOP_PANEL comes first: the same loop on the MFMA panels (gpad_loop_panel.hip), shared
-// matrices with a fragment image of at most 16 tiles; with a tolerance the iteration limit must
-// fall on a test (the kernel's events are workgroup-uniform).
+// GPAD_OPT_LOOP_PANEL comes first: the same loop on the MFMA panels (gpad_loop_panel.hip).
+// A handle with the class tables attached (Handle::cloop) runs the fused class loop, GPAD_KERNEL_LOOP_CLASSES:
+// gpad_classes.cpp attaches them only to a loop that meets loop_panel_shape.
 static int one_launch_engine(gpad_handle_t h, bool loop, int N, double tol, int nxa) {
+    if (h->cloop) return GPAD_KERNEL_LOOP_CLASSES;
     const gpad_dims_t& d = h->dims;
     const int n = d.n, m = d.m, nu = h->nu;
-    const bool lpanel = loop && h->tune.loop_panel && d.shared && h->frag_ok && h->frag_tiles >= 1 &&
-                        h->frag_tiles <= 16 && !h->flat && !h->hess_ok && N >= 1 &&
-                        (d.kernel == GPAD_KERNEL_AUTO || d.kernel == GPAD_KERNEL_PANEL) &&
-                        (!(tol > 0.0) || N % d.check_every == 0) && gpad::loop_panel_supported(n, m, nxa, nu);
+    const bool lpanel = loop && h->tune.loop_panel && loop_panel_shape(h, N, tol, nxa);
     const bool async = lpanel || (loop && h->tune.loop_async && !h->flat && !h->hess_ok && N >= 1 &&
                                   (d.kernel == GPAD_KERNEL_AUTO || d.kernel == GPAD_KERNEL_RESIDENT) &&
                                   gpad::loop_supported(n, m, nxa, nu));
@@ -289,7 +327,8 @@ static int one_launch_engine(gpad_handle_t h, bool loop, int N, double tol, int 
 static int run_loop_one_launch(gpad_handle_t h, const StateWork<float>& w, int engine, int nsolve, int N, double tol,
                                int warm, const float** x_end) {
     const gpad_dims_t& d = h->dims;
-    const bool lpanel = engine == GPAD_KERNEL_LOOP_PANEL;
+    const gpad::ClassLoop* cl = engine == GPAD_KERNEL_LOOP_CLASSES ? h->cloop : nullptr;
+    const bool lpanel = engine == GPAD_KERNEL_LOOP_PANEL || cl;
     const int ns = w.ns;
     gpad::LoopArgs la{};
     gpad::SolveArgs<float>& a = la.s;
@@ -321,7 +360,15 @@ static int run_loop_one_launch(gpad_handle_t h, const StateWork<float>& w, int e
     la.warm = warm ? 1 : 0;
     la.per_plant = w.per_plant ? 1 : 0;
     int grid;
-    if (lpanel) {
+    if (cl) {  // every class in one launch: its images, counters and tables (the maps are in w already)
+        a.frag = cl->frag;
+        a.frag_tiles = h->frag_tiles;
+        a.qctr = cl->qctr;
+        la.cls_K = cl->K;
+        la.cls_off = cl->off;
+        la.cls_start = cl->start;
+        grid = cl->grid;
+    } else if (lpanel) {
         a.frag = h->frag.p;
         a.frag_tiles = h->frag_tiles;
         grid = gpad::loop_panel_grid(d.n, d.m, d.batch, h->num_cus, &h->tune);
@@ -413,7 +460,9 @@ static int state_typed(gpad_handle_t h, T* x, T* z, T* y, const T* sg, int steps
     const double margin = sizeof(T) == sizeof(float) ? gpad::ViolMargin<float>::value : gpad::ViolMargin<double>::value;
     if ((rc = reset_status(h, tol, margin))) return rc;  // g(x) unscaled: margin * L * (1/L)
     const int engine = sizeof(T) == sizeof(float) ? one_launch_engine(h, loop, N, tol, w.nxa) : 0;
-    if (engine) {  // the pack queue counter, zeroed ahead of the timed launch
+    if (engine == GPAD_KERNEL_LOOP_CLASSES) {  // one claim counter per class
+        HIP_TRY(hipMemsetAsync(h->cloop->qctr, 0, sizeof(int) * (size_t)h->cloop->K, h->stream));
+    } else if (engine) {  // the pack queue counter, zeroed ahead of the timed launch
         if ((rc = h->q64.ensure(sizeof(int)))) return rc;
         HIP_TRY(hipMemsetAsync(h->q64.p, 0, sizeof(int), h->stream));
     }

@@ -24,9 +24,10 @@ DTYPE_F32, DTYPE_F64 = 0, 1
 KERNEL_AUTO, KERNEL_STREAM, KERNEL_RESIDENT, KERNEL_PANEL, KERNEL_FLAT = 0, 1, 2, 3, 4
 KERNEL_LOOP = 6  # reported only: closed_loop in one launch (OPT_LOOP_ASYNC)
 KERNEL_LOOP_PANEL = 7  # reported only: closed_loop in one launch on the MFMA panels (OPT_LOOP_PANEL)
+KERNEL_LOOP_CLASSES = 8  # reported only: closed_loop of a class binding as one launch (set_class_loop_fused)
 KERNEL_NAMES = {KERNEL_AUTO: "auto", KERNEL_STREAM: "stream", KERNEL_RESIDENT: "resident",
                 KERNEL_PANEL: "panel", KERNEL_FLAT: "flat", KERNEL_LOOP: "loop",
-                KERNEL_LOOP_PANEL: "loop_panel"}
+                KERNEL_LOOP_PANEL: "loop_panel", KERNEL_LOOP_CLASSES: "loop_classes"}
 
 # every symbol include/gpad.h declares (checked by tests/test_abi.py)
 EXPORTS = [
@@ -45,6 +46,7 @@ EXPORTS = [
     "gpad_group_rccl_library",
     "gpad_setup_signals", "gpad_run_state_signals", "gpad_closed_loop_signals",
     "gpad_class_order", "gpad_setup_classes", "gpad_setup_plant_classes",
+    "gpad_class_loop_fused", "gpad_class_loop_deal",
 ]
 GROUP_RCCL, GROUP_PEER = 1, 2
 
@@ -198,6 +200,11 @@ def load(path: str | None = None) -> C.CDLL:
         L.gpad_setup_classes.argtypes = [vp, C.POINTER(Dims), i, C.POINTER(i), cvp, cvp, d]
         L.gpad_setup_plant_classes.argtypes = [vp, i, i, cvp, cvp, cvp, cvp, cvp, cvp]
         for name in ("gpad_class_order", "gpad_setup_classes", "gpad_setup_plant_classes"):
+            getattr(L, name).restype = i
+    if hasattr(L, "gpad_class_loop_fused"):  # (added within 0.6; absent from older builds under GPAD_LIB_TOLERANT)
+        L.gpad_class_loop_fused.argtypes = [vp, i]
+        L.gpad_class_loop_deal.argtypes = [C.POINTER(i), i, i, C.POINTER(i)]
+        for name in ("gpad_class_loop_fused", "gpad_class_loop_deal"):
             getattr(L, name).restype = i
     L.gpad_datafile_read.argtypes = [C.c_char_p, i, C.POINTER(DataFile)]
     L.gpad_datafile_write.argtypes = [C.c_char_p, i, C.POINTER(DataFile)]

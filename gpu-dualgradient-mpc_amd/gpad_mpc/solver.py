@@ -169,6 +169,13 @@ class GpadSolver:
         self.dims = dims
         self._classes = int(ML.shape[0])
 
+    def set_class_loop_fused(self, on: bool) -> None:
+        """gpad_class_loop_fused: after ``setup_classes``, run ``closed_loop`` as one launch over every class
+        (reported kernel "loop_classes") where the shape meets the rules of the ``loop_panel`` option; any
+        other call runs class by class as before.  Results are bit for bit the same either way.  Off by
+        default; a later ``setup_classes`` / ``setup*`` clears it."""
+        check(self.lib.gpad_class_loop_fused(self.h, 1 if on else 0), "gpad_class_loop_fused")
+
     def setup_flat(self, MGf, GLf, L: float, *, n_u: int, batch: int = 1,
                    schedule: int = _lib.SCHEDULE_MATLAB, check_every: int = 10,
                    kernel: int = _lib.KERNEL_AUTO, tol_gap: float = 0.0) -> None:
@@ -217,10 +224,12 @@ class GpadSolver:
             return None
         return self._stats_dict(st)
 
-    def last_stats(self, iters=None) -> dict:
+    def last_stats(self, iters=None, codes=None) -> dict:
         st = Stats()
         if iters is not None:
             st.iters = _count_array(iters, "iters", max(1, self.dims.batch if self.dims else 1))
+        if codes is not None:
+            st.codes = _count_array(codes, "codes", max(1, self.dims.batch if self.dims else 1))
         check(self.lib.gpad_last_stats(self.h, C.byref(st)), "gpad_last_stats")
         return self._stats_dict(st)
 

@@ -35,7 +35,9 @@ extern "C" {
                               * without a new minor (no layout or behaviour of 0.6 changes):
                               * gpad_setup_signals, gpad_run_state_signals, gpad_closed_loop_signals;
                               * GPAD_OPT_LOOP_PANEL (option 23) and the reported GPAD_KERNEL_LOOP_PANEL (7);
-                              * gpad_class_order, gpad_setup_classes, gpad_setup_plant_classes */
+                              * gpad_class_order, gpad_setup_classes, gpad_setup_plant_classes;
+                              * gpad_class_loop_fused, gpad_class_loop_deal and the reported
+                              * GPAD_KERNEL_LOOP_CLASSES (8) */
 
 /* status codes */
 #define GPAD_OK 0
@@ -77,6 +79,9 @@ extern "C" {
                                 * dims.kernel = 6 returns GPAD_ERR_INVALID                           */
 #define GPAD_KERNEL_LOOP_PANEL 7 /* reported only: gpad_closed_loop in one launch on the MFMA panels
                                 * (GPAD_OPT_LOOP_PANEL); dims.kernel = 7 returns GPAD_ERR_INVALID     */
+#define GPAD_KERNEL_LOOP_CLASSES 8 /* reported only: gpad_closed_loop of a class-bound handle as one launch
+                                * over every class (gpad_class_loop_fused); dims.kernel = 8 returns
+                                * GPAD_ERR_INVALID                                                   */
 
 typedef struct gpad_dims {
     int n;           /* primal variables, n = n_u * N                                   */
@@ -347,7 +352,8 @@ int gpad_closed_loop_signals(gpad_handle_t h, void* x, void* z, void* y, const v
  *     caller's instance order (the library permutes rows to and from a class-sorted workspace on the
  *     device).  gpad_set_stream and gpad_set_option are forwarded to every class, GPAD_OPT_LOOP_ASYNC
  *     and GPAD_OPT_LOOP_PANEL included, which each class then applies by its own rules (a class that
- *     does not qualify runs the lockstep loop).  The plain gpad_setup_plant binds the same maps for
+ *     does not qualify runs the lockstep loop); gpad_class_loop_fused, where it takes the call, is
+ *     looked at before the forwarded loop options.  The plain gpad_setup_plant binds the same maps for
  *     every class.
  *   - gpad_setup_hessian, gpad_setup_plant_batch, gpad_setup_signals (and the _signals runs) and
  *     gpad_run_scaled return GPAD_ERR_UNSUPPORTED, gpad_last_error naming the class binding.
@@ -360,9 +366,10 @@ int gpad_closed_loop_signals(gpad_handle_t h, void* x, void* z, void* y, const v
  * whole call, row permutations included.  A GPAD_ERR_DEVICE of any class is returned, and stays sticky
  * as on any handle.
  * The classes run one after the other on the handle's stream (a loop: class 0's `steps` steps, then
- * class 1's); they are independent, so the order changes no result.  Not provided: classes running
- * concurrently on several streams, signals, per-pack true plants under a class binding, Hessian
- * branches. */
+ * class 1's); they are independent, so the order changes no result.  Every (class, step) so pays its own
+ * launches and its own tail on a part of the GPU; gpad_class_loop_fused below runs a closed loop of every
+ * class as one launch instead.  Not provided: classes running concurrently on several streams, signals,
+ * per-pack true plants under a class binding, Hessian branches. */
 
 /* host only, no device work (for tests/tools, like gpad_plan_phases): the class-sorted order.
  * perm[batch]: sorted position -> instance, classes ascending, instances ascending inside a class
@@ -381,6 +388,35 @@ int gpad_setup_classes(gpad_handle_t h, const gpad_dims_t* dims, int K, const in
  * the handle is class-bound. */
 int gpad_setup_plant_classes(gpad_handle_t h, int nx, int nu, const void* PM, const void* M0,
                              const void* Pg, const void* g0, const void* A, const void* B);
+
+/* The fused class loop (opt-in, off by default): gpad_closed_loop of a class-bound handle as ONE launch of
+ * the class-aware MFMA panel loop (the kernel of GPAD_OPT_LOOP_PANEL; reported kernel =
+ * GPAD_KERNEL_LOOP_CLASSES).  A workgroup serves one class at a time -- its 16 panel columns hold packs of
+ * that class, claimed from the class's own queue -- and moves on to another class with unclaimed packs when
+ * its own has none left, so the call pays one tail and no per-class launch trains.  No workgroup waits for
+ * another.  Results (outputs, trajectories, per-step counts and codes, stats, tol_floor, flags) are bit
+ * for bit those of the binding without it.
+ * on = 0 or 1 (anything else: GPAD_ERR_INVALID); GPAD_ERR_NOT_SETUP unless the handle is class-bound;
+ * cleared by a later gpad_setup_classes and by every gpad_setup*.
+ * It is looked at before the forwarded loop options, and takes a call when steps >= 1 and the shape
+ * meets the rules of GPAD_OPT_LOOP_PANEL (the same for every class, which share dims): f32, n, m <= 256,
+ * dims.kernel AUTO or PANEL, N >= 1, tol <= 0 or N % check_every == 0, nx <= 64, nu <= min(n, 64), the
+ * plant bound with A and B.  Any other call (f64, gpad_run, gpad_run_state, ...) runs class by class exactly as
+ * if it were off, with that path's results and reported kernel, silently, as the loop options do.
+ * Grid: min(sum_k ceil(count_k / 16), resident workgroups, 1024), capped by GPAD_OPT_PANEL_MAX_GRID; the
+ * workgroups start on the classes gpad_class_loop_deal gives them.
+ * gpad_last_stats, gpad_accumulate_iterations, gpad_sync and the sticky GPAD_ERR_DEVICE work after a fused
+ * run as after any run, the stats by the rules above with kernel = GPAD_KERNEL_LOOP_CLASSES.  The binding
+ * makes one more handle of the whole batch the first time the loop is turned on (f32 bindings only). */
+int gpad_class_loop_fused(gpad_handle_t h, int on);
+
+/* host only, no device work (for tests/tools, like gpad_class_order): the class each of `grid` workgroups
+ * of the fused class loop starts on, start_class[grid], class 0's workgroups first.  Workgroups are dealt
+ * in proportion to the classes' panel counts ceil(counts[k] / 16); none goes to an empty class; with grid
+ * at least the number of non-empty classes each of those gets one, else the classes with the most panels
+ * are dealt first (ties: the lowest) and the others are reached by switching.
+ * GPAD_ERR_INVALID: NULL, K < 1, grid < 1, a negative count, every count zero. */
+int gpad_class_loop_deal(const int* counts, int K, int grid, int* start_class);
 
 /* ---- reference data-file boundary (main.cu:29-67 readData) ------------------------------
  * Text file: "n_u N m num_iterations L", then M_G (n*m), g_P (n), G_L (n*m), p_D (m),

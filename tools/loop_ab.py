@@ -32,9 +32,13 @@ class_of[b] = b % K; default batches 256 2048 8192).  Variant "fleet" is the dim
 expanded fleet (problems.expand_classes; setup(shared=False) + a stacked setup_plant, lockstep) -- the path
 a fleet of classes had to take before the class binding; "classes" is the class binding
 (setup_classes, csrc/gpad_classes.cpp) with the options off, "classes_panel" and "classes_async" the
-same with loop_panel = 1 and loop_async = 1.  With K = 1 a fifth variant, "shared", is the plain
-shared-matrix handle (lockstep): `classes_over_shared` is then the price of the row permutations and
-the child handle.  Every variant's outputs are compared with "fleet" bit for bit first; each line has
+same with loop_panel = 1 and loop_async = 1 (forwarded to every class: K one-launch loops back to back),
+"classes_fused" the fused class loop (set_class_loop_fused: every class in one launch, kernel
+"loop_classes"); `classes_fused_over_classes_best` is its rate over the best of the other three class
+variants.  With K = 1 two more variants: "shared", the plain shared-matrix handle (lockstep) --
+`classes_over_shared` is then the price of the row permutations and the child handle -- and
+"shared_panel", the same handle with loop_panel = 1: `classes_fused_over_shared_panel` is what the class
+bookkeeping of the fused kernel and the row permutations cost against the plain panel loop.  Every variant's outputs are compared with "fleet" bit for bit first; each line has
 the rates, `<variant>_over_fleet` and `<variant>_faster` ("none" inside the spread of the rounds).
 
 Per batch and mode the two variants' x, z, y, xs, us and per-step iteration counts are compared first
@@ -77,8 +81,10 @@ def classes_ab(args):
     print(json.dumps({"plant": f"battery_fleet(4, 10), {K} classes, class_of[b] = b % {K}", "n": n, "m": m,
                       "steps": steps, "rounds": rounds, "device": torch.cuda.get_device_name(0),
                       "cus": torch.cuda.get_device_properties(0).multi_processor_count}))
-    names = ("fleet", "classes", "classes_panel", "classes_async") + (("shared",) if K == 1 else ())
-    want = {"classes_panel": "loop_panel", "classes_async": "loop"}
+    names = ("fleet", "classes", "classes_panel", "classes_async", "classes_fused") + (
+        ("shared", "shared_panel") if K == 1 else ())
+    want = {"classes_panel": "loop_panel", "classes_async": "loop", "classes_fused": "loop_classes",
+            "shared_panel": "loop_panel"}
     for B in args.batches:
         class_of = np.arange(B, dtype=np.int32) % K
         X0 = torch.from_numpy((np.random.default_rng(B).random((B, nx)) - 0.5).astype(np.float32)).to(dev)
@@ -91,13 +97,15 @@ def classes_ab(args):
                 s.setup(f["ML"], f["G"], L, n=n, m=m, batch=B, shared=False)
                 s.setup_plant(f["PM"], f["Pg"], g0=f["g0"], A=f["A"], B=f["B"])
                 del f
-            elif name == "shared":
+            elif name in ("shared", "shared_panel"):
                 s.setup(cls["ML"][0], cls["G"][0], L, n=n, m=m, batch=B, shared=True)
                 s.setup_plant(cls["PM"][0], cls["Pg"][0], g0=cls["g0"][0], A=cls["A"][0], B=cls["B"][0])
+                s.set_options(loop_panel=int(name == "shared_panel"))
             else:
                 s.setup_classes(cls["ML"], cls["G"], L, class_of, n=n, m=m)
                 s.setup_plant(cls["PM"], cls["Pg"], g0=cls["g0"], A=cls["A"], B=cls["B"])
                 s.set_options(loop_panel=int(name == "classes_panel"), loop_async=int(name == "classes_async"))
+                s.set_class_loop_fused(name == "classes_fused")
             buf = dict(x=torch.empty(B, nx, device=dev), z=torch.empty(B, n, device=dev),
                        y=torch.empty(B, m, device=dev), xs=torch.empty(steps, B, nx, device=dev),
                        us=torch.empty(steps, B, nu, device=dev))
@@ -120,7 +128,7 @@ def classes_ab(args):
             bad = [f"{v}.{k}" for k in ("x", "z", "y", "xs", "us") for v in var if v != "fleet"
                    if not torch.equal(var["fleet"][1][k].view(torch.int32), var[v][1][k].view(torch.int32))]
             bad += [f"{v}.iters" for v in var if not np.array_equal(its["fleet"], its[v])]
-            if bad or any(kern[v] is None or (kern[v] in ("loop", "loop_panel")) != (v in want) or
+            if bad or any(kern[v] is None or (kern[v] in ("loop", "loop_panel", "loop_classes")) != (v in want) or
                           (v in want and kern[v] != want[v]) for v in var):
                 print(json.dumps({"batch": B, "mode": mname, "error": "outputs differ" if bad else "wrong kernel",
                                   "differ": bad, "kernels": kern}))
@@ -148,7 +156,12 @@ def classes_ab(args):
                 "median_ms": {k: round(v, 4) for k, v in med.items()},
                 "mpc_steps_per_s": {k: round(v, 1) for k, v in rate.items()},
                 **{f"{v}_over_fleet": round(rate[v] / rate["fleet"], 3) for v in var if v != "fleet"},
-                **{f"{v}_faster": faster(v, "fleet") for v in var if v not in ("fleet", "shared")},
+                **{f"{v}_faster": faster(v, "fleet") for v in var if v not in ("fleet", "shared", "shared_panel")},
+                "classes_fused_over_classes_best": round(
+                    rate["classes_fused"] / max(rate[v] for v in ("classes", "classes_panel", "classes_async")), 3),
+                **({"classes_fused_over_shared_panel": round(rate["classes_fused"] / rate["shared_panel"], 3),
+                    "classes_fused_vs_shared_panel_faster": faster("classes_fused", "shared_panel")}
+                   if "shared_panel" in var else {}),
                 **({"classes_over_shared": round(rate["classes"] / rate["shared"], 3),
                     "classes_vs_shared_faster": faster("classes", "shared")} if "shared" in var else {})}),
                 flush=True)
