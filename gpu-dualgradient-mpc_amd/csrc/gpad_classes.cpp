@@ -28,8 +28,14 @@
 // [steps][batch][len] array in the sorted order and the counts and codes come from that handle.  Every other
 // call still pays each class's own tail.
 //
-// Not in this file: classes running concurrently on several streams, exogenous signals, per-pack true
-// plants under a class binding, Hessian branches.
+// Exogenous signals (gpad_setup_class_signals): child k binds class k's copy of SM, Sg, E with
+// gpad_setup_signals and runs the _signals entry points on its own contiguous [steps][count_k][ns] block of
+// S, which one more launch gathers from the caller's [steps][batch][ns] (launch_class_sig_gather).  The fused
+// loop reads S as one [steps][batch][ns] array in the sorted order and the binding's own packed images
+// [PM SM], [Pg Sg], [A E] (pack_images), a copy per class when the plant or the signals are per class.
+//
+// Not in this file: classes running concurrently on several streams, per-pack true plants under a class
+// binding, Hessian branches.
 #include <algorithm>
 #include <cmath>
 
@@ -59,6 +65,14 @@ struct ClassBinding {
     size_t map_off[6] = {0, 0, 0, 0, 0, 0};  // element offsets in maps
     bool map_has[6] = {false, false, false, false, false, false};
     bool per_class = false;
+    // class signals (classes_setup_signals): ns > 0 while bound.  f32 bindings keep what the fused loop reads,
+    //   [PM SM] | [Pg Sg] | [A E] | M0 | g0 | B
+    // every array K times over when the plant or the signals are per class (img_per_class), else once; M0, g0, B
+    // are there only when they had to be replicated (signals per class over a plant with one copy)
+    int ns = 0;
+    DevBuf simg;
+    size_t img_off[6] = {0, 0, 0, 0, 0, 0};
+    bool img_per_class = false, img_rep = false;
     // the fused class loop (gpad_class_loop_fused): every class in one launch of the class-aware panel loop,
     // run through a handle of the whole batch in the sorted order (shared = 1 with the major class's matrices,
     // which the launch never reads: it takes every class's fragment image from `frags`).  That handle owns
@@ -129,6 +143,7 @@ void classes_free(ClassBinding* cb) {
         if (c) (void)gpad_destroy(c);  // (synchronises the stream first)
     if (cb->fused) (void)gpad_destroy(cb->fused);
     cb->maps.release();
+    cb->simg.release();
     cb->mats.release();
     cb->frags.release();
     cb->ftab.release();
@@ -286,6 +301,12 @@ static int fused_bind_plant(ClassBinding* cb) {
     return gpad_setup_plant(cb->fused, cb->nx, cb->nu, a[0], a[1], a[2], a[3], a[4], a[5]);  // (synchronises)
 }
 
+// The fused handle's signals: it needs ns alone; the launch reads the binding's packed images (ClassLoop), so
+// maps of zeros do.  (ns == 0 unbinds.)
+static int fused_bind_signals(ClassBinding* cb) {
+    return gpad_setup_signals(cb->fused, cb->ns, nullptr, nullptr, nullptr);
+}
+
 // The whole-batch handle of the fused loop with what its launch reads: the K fragment images (copied from
 // the children, which packed them at gpad_setup) and the offsets table.  f64 bindings have none: their
 // loops always run class by class.
@@ -321,7 +342,7 @@ static int fused_create(ClassBinding* cb, const Tuning& tune) {
     }
     cb->fused = f;
     cb->start_grid = 0;
-    if (cb->plant && (rc = fused_bind_plant(cb))) {
+    if (cb->plant && ((rc = fused_bind_plant(cb)) || (rc = fused_bind_signals(cb)))) {
         (void)gpad_destroy(f);
         cb->fused = nullptr;
     }
@@ -351,6 +372,7 @@ int classes_setup_plant(ClassBinding* cb, bool per_class, int nx, int nu, const 
     size_t total = 0;
     for (int i = 0; i < 6; ++i) total += src[i] ? elems[i] * copies : 0;
     cb->plant = false;  // (a failed rebinding leaves none)
+    cb->ns = 0;         // (a new plant unbinds the signals, the children's and the fused handle's with it)
     int rc = cb->maps.ensure(es * total);
     if (rc) return rc;
     const hipMemcpyKind kind = d.memory == GPAD_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
@@ -379,6 +401,105 @@ int classes_setup_plant(ClassBinding* cb, bool per_class, int nx, int nu, const 
     cb->plant = true;
     cb->plant_dyn = A != nullptr;
     return GPAD_OK;
+}
+
+// What the fused loop reads with signals, packed once (f32): per copy [PM SM], [Pg Sg], [A E] over the augmented
+// state, and M0, g0, B replicated where the plant holds one copy under per-class signals -- the kernel indexes
+// all six arrays by the one class id.  SM, Sg, E: device, K copies (per_class) or one; null: zeros.
+static int pack_images(ClassBinding* cb, int ns, bool per_class, const float* SM, const float* Sg, const float* E) {
+    const gpad_dims_t& d = cb->dims;
+    const int nx = cb->nx, nu = cb->nu;
+    const size_t w = (size_t)nx + ns;
+    cb->img_per_class = per_class || cb->per_class;
+    cb->img_rep = per_class && !cb->per_class;
+    const size_t copies = cb->img_per_class ? (size_t)cb->K : 1;
+    const size_t rows[3] = {(size_t)d.n, (size_t)d.m, cb->plant_dyn ? (size_t)nx : 0};
+    const size_t rep[3] = {(size_t)d.n, (size_t)d.m, (size_t)nx * nu};  // M0, g0, B
+    const int rep_map[3] = {1, 3, 5};
+    size_t off = 0;
+    for (int i = 0; i < 3; ++i) {
+        cb->img_off[i] = off;
+        off += copies * rows[i] * w;
+    }
+    for (int i = 0; i < 3; ++i) {
+        cb->img_off[3 + i] = off;
+        if (cb->img_rep && cb->map_has[rep_map[i]]) off += copies * rep[i];
+    }
+    if (int rc = cb->simg.ensure(sizeof(float) * off)) return rc;
+    float* I = (float*)cb->simg.p;
+    const float* S[3] = {SM, Sg, E};
+    const int plant_map[3] = {0, 2, 4};
+    for (size_t k = 0; k < copies; ++k) {
+        const void* a[6];
+        class_maps(cb, (int)k, a);  // (a plant with one copy: that copy for every k)
+        for (int i = 0; i < 3; ++i) {
+            if (!rows[i]) continue;
+            const float* Sk = S[i] ? S[i] + (per_class ? k * rows[i] * ns : 0) : nullptr;
+            HIP_TRY(launch_pack_aug<float>((const float*)a[plant_map[i]], Sk, I + cb->img_off[i] + k * rows[i] * w,
+                                           (long long)rows[i], nx, ns, cb->stream));
+            if (cb->img_rep && cb->map_has[rep_map[i]] && rep[i])
+                HIP_TRY(hipMemcpyAsync(I + cb->img_off[3 + i] + k * rep[i], a[rep_map[i]], sizeof(float) * rep[i],
+                                       hipMemcpyDeviceToDevice, cb->stream));
+        }
+    }
+    HIP_TRY(hipStreamSynchronize(cb->stream));
+    return GPAD_OK;
+}
+
+bool classes_has_plant(const ClassBinding* cb, bool* dyn) {
+    if (dyn) *dyn = cb->plant && cb->plant_dyn;
+    return cb->plant;
+}
+
+static void unbind_signals(ClassBinding* cb) {
+    cb->ns = 0;
+    for (gpad_handle_t c : cb->child)
+        if (c) c->ns = 0;
+    if (cb->fused) cb->fused->ns = 0;
+}
+
+int classes_setup_signals(ClassBinding* cb, int ns, bool per_class, const void* SM, const void* Sg, const void* E) {
+    const gpad_dims_t& d = cb->dims;
+    unbind_signals(cb);  // (a failed rebinding leaves none)
+    if (ns == 0) return GPAD_OK;
+    const size_t es = esize(d.dtype), copies = per_class ? (size_t)cb->K : 1;
+    const void* src[3] = {SM, Sg, E};
+    const size_t elems[3] = {(size_t)d.n * ns, (size_t)d.m * ns, (size_t)cb->nx * ns};
+    // the maps on the device: the children are GPAD_MEM_DEVICE handles
+    const char* dev[3] = {(const char*)SM, (const char*)Sg, (const char*)E};
+    DevBuf up;
+    int rc = GPAD_OK;
+    if (d.memory == GPAD_MEM_HOST) {
+        size_t total = 0;
+        for (int i = 0; i < 3; ++i) total += src[i] ? elems[i] * copies : 0;
+        rc = up.ensure(es * total);
+        hipError_t e = hipSuccess;
+        size_t off = 0;
+        for (int i = 0; i < 3 && !rc && e == hipSuccess; ++i) {
+            if (!src[i]) continue;
+            dev[i] = (const char*)up.p + es * off;
+            e = hipMemcpyAsync((char*)up.p + es * off, src[i], es * elems[i] * copies, hipMemcpyHostToDevice, cb->stream);
+            off += elems[i] * copies;
+        }
+        if (!rc && e == hipSuccess) e = hipStreamSynchronize(cb->stream);
+        if (!rc && e != hipSuccess)
+            rc = fail(GPAD_ERR_HIP, std::string("gpad_setup_class_signals: map upload: ") + hipGetErrorString(e));
+    }
+    for (int k = 0; k < cb->K && !rc; ++k) {
+        if (!cb->child[k]) continue;
+        const void* a[3];
+        for (int i = 0; i < 3; ++i) a[i] = dev[i] ? dev[i] + (per_class ? es * elems[i] * k : 0) : nullptr;
+        rc = gpad_setup_signals(cb->child[k], ns, a[0], a[1], a[2]);  // (synchronises)
+    }
+    if (!rc && d.dtype == GPAD_DTYPE_F32)
+        rc = pack_images(cb, ns, per_class, (const float*)dev[0], (const float*)dev[1], (const float*)dev[2]);
+    if (!rc) {
+        cb->ns = ns;
+        if (cb->fused) rc = fused_bind_signals(cb);
+    }
+    up.release();
+    if (rc) unbind_signals(cb);
+    return rc;
 }
 
 // The stats of the last run from every child (each call synchronises the stream and reports that child's
@@ -550,8 +671,9 @@ int classes_run(ClassBinding* cb, void* z, void* y, const void* M, const void* g
 // The fused class loop: gpad_closed_loop of the whole-batch handle on the sorted arrays, with the class tables
 // attached for the length of the call.  Grid: loop_panel_grid's rule on the classes' panels,
 // min(sum_k ceil(count_k / 16), resident workgroups, kAbsmaxMaxBlocks) capped by GPAD_OPT_PANEL_MAX_GRID.
-static int fused_loop(ClassBinding* cb, float* sx, float* sz, float* sy, int steps, int N, double tol, int warm,
-                      float* sxs, float* sus) {
+// sS: the call's signals [steps][batch][ns] in the sorted order (gpad_closed_loop_signals), or null
+static int fused_loop(ClassBinding* cb, float* sx, float* sz, float* sy, const float* sS, int steps, int N, double tol,
+                      int warm, float* sxs, float* sus) {
     const gpad_dims_t& d = cb->dims;
     const gpad_handle_t f = cb->fused;
     const int K = cb->K;
@@ -585,26 +707,41 @@ static int fused_loop(ClassBinding* cb, float* sx, float* sz, float* sy, int ste
     cl.g0 = (const float*)maps[3];
     cl.A = (const float*)maps[4];
     cl.B = (const float*)maps[5];
+    if (sS) {  // the packed images over [x; s], and M0, g0, B with as many copies as they have
+        const float* I = (const float*)cb->simg.p;
+        cl.ns = cb->ns;
+        cl.per_class = cb->img_per_class ? 1 : 0;
+        cl.PM = I + cb->img_off[0];
+        cl.Pg = I + cb->img_off[1];
+        cl.A = I + cb->img_off[2];
+        if (cb->img_rep) {
+            if (cl.M0) cl.M0 = I + cb->img_off[3];
+            if (cl.g0) cl.g0 = I + cb->img_off[4];
+            if (cl.B) cl.B = I + cb->img_off[5];
+        }
+    }
     f->cloop = &cl;
-    const int rc = gpad_closed_loop(f, sx, sz, sy, steps, N, tol, warm, sxs, sus, nullptr);
+    const int rc = sS ? gpad_closed_loop_signals(f, sx, sz, sy, sS, steps, N, tol, warm, sxs, sus, nullptr)
+                      : gpad_closed_loop(f, sx, sz, sy, steps, N, tol, warm, sxs, sus, nullptr);
     f->cloop = nullptr;
     return rc;
 }
 
 template <typename T>
-static int state_typed(ClassBinding* cb, T* x, T* z, T* y, int steps, int N, double tol, int warm, T* xs, T* us,
-                       gpad_stats_t* st) {
+static int state_typed(ClassBinding* cb, T* x, T* z, T* y, const T* sg, int steps, int N, double tol, int warm, T* xs,
+                       T* us, gpad_stats_t* st) {
     const gpad_dims_t& d = cb->dims;
-    const int nx = cb->nx, nu = cb->nu;
+    const int nx = cb->nx, nu = cb->nu, ns = sg ? cb->ns : 0;
     const bool loop = steps > 0, host = d.memory == GPAD_MEM_HOST;
     // gpad_class_loop_fused: a loop of a shape the panel loop takes runs as one launch over every class; any
     // other call runs class by class as if it were off (as the loop options do)
     const bool fused = loop && cb->fused_on && cb->fused && sizeof(T) == sizeof(float) &&
-                       loop_panel_shape(cb->fused, N, tol, nx);
+                       loop_panel_shape(cb->fused, N, tol, nx + ns);  // (the state and the signals share a row)
     const bool zy_in = !loop || warm;  // a cold loop starts every step from z = y = 0: nothing to bring in
     const size_t batch = (size_t)d.batch, zn = batch * d.n, yn = batch * d.m, xn = batch * nx;
     const size_t xsn = loop && xs ? (size_t)steps * xn : 0, usn = loop && us ? (size_t)steps * batch * nu : 0;
-    const size_t elems = xn + zn + yn + xsn + usn;
+    const size_t sn = (size_t)(loop ? steps : 1) * batch * ns;
+    const size_t elems = xn + zn + yn + xsn + usn + sn;
     int rc = cb->sorted.ensure(sizeof(T) * elems);
     if (rc) return rc;
     T* sx = (T*)cb->sorted.p;
@@ -612,6 +749,8 @@ static int state_typed(ClassBinding* cb, T* x, T* z, T* y, int steps, int N, dou
     T* sy = sz + zn;
     T* sxs = xsn ? sy + yn : nullptr;
     T* sus = usn ? sy + yn + xsn : nullptr;
+    T* sS = sn ? sy + yn + xsn + usn : nullptr;  // a block per class, or (fused) one array in the sorted order
+    const T* cS = sg;
     T *cx = x, *cz = z, *cy = y, *cxs = xs, *cus = us;  // the caller-order arrays on the device
     if (host) {
         if ((rc = cb->stage.ensure(sizeof(T) * elems))) return rc;
@@ -621,6 +760,11 @@ static int state_typed(ClassBinding* cb, T* x, T* z, T* y, int steps, int N, dou
         cxs = xsn ? cy + yn : nullptr;
         cus = usn ? cy + yn + xsn : nullptr;
         HIP_TRY(hipMemcpyAsync(cx, x, sizeof(T) * xn, hipMemcpyHostToDevice, cb->stream));
+        if (sn) {
+            T* up = cy + yn + xsn + usn;
+            HIP_TRY(hipMemcpyAsync(up, sg, sizeof(T) * sn, hipMemcpyHostToDevice, cb->stream));
+            cS = up;
+        }
         if (zy_in) {
             HIP_TRY(hipMemcpyAsync(cz, z, sizeof(T) * zn, hipMemcpyHostToDevice, cb->stream));
             HIP_TRY(hipMemcpyAsync(cy, y, sizeof(T) * yn, hipMemcpyHostToDevice, cb->stream));
@@ -639,19 +783,29 @@ static int state_typed(ClassBinding* cb, T* x, T* z, T* y, int steps, int N, dou
     in.dst[2] = sy;
     in.len[2] = d.m;
     HIP_TRY(launch_class_gather<T>(in, cb->d_perm(), d.batch, cb->stream));
+    if (sn)
+        HIP_TRY(launch_class_sig_gather<T>(cS, sS, ns, cb->d_perm(), fused ? nullptr : cb->d_pos_off(),
+                                           fused ? nullptr : cb->d_pos_cnt(), d.batch, loop ? steps : 1, cb->stream));
     cb->last_steps = loop ? steps : 1;
     cb->timed = false;
     cb->last_fused = fused;
     if constexpr (sizeof(T) == sizeof(float)) {
-        if (fused && (rc = fused_loop(cb, sx, sz, sy, steps, N, tol, warm, sxs, sus))) return rc;
+        if (fused && (rc = fused_loop(cb, sx, sz, sy, sS, steps, N, tol, warm, sxs, sus))) return rc;
     }
     for (int k = 0; k < cb->K && !fused; ++k) {
         if (!cb->child[k]) continue;
         const size_t off = (size_t)cb->offsets[k];
         T *kx = sx + off * nx, *kz = sz + off * d.n, *ky = sy + off * d.m;
-        if (loop)  // class k's trajectories: one contiguous [steps][count_k][len] block
-            rc = gpad_closed_loop(cb->child[k], kx, kz, ky, steps, N, tol, warm, sxs ? sxs + (size_t)steps * off * nx : nullptr,
-                                  sus ? sus + (size_t)steps * off * nu : nullptr, nullptr);
+        // class k's trajectories and signals: one contiguous [steps][count_k][len] block each
+        T* kxs = sxs ? sxs + (size_t)steps * off * nx : nullptr;
+        T* kus = sus ? sus + (size_t)steps * off * nu : nullptr;
+        const T* kS = sS ? sS + (size_t)(loop ? steps : 1) * off * ns : nullptr;
+        if (loop && kS)
+            rc = gpad_closed_loop_signals(cb->child[k], kx, kz, ky, kS, steps, N, tol, warm, kxs, kus, nullptr);
+        else if (loop)
+            rc = gpad_closed_loop(cb->child[k], kx, kz, ky, steps, N, tol, warm, kxs, kus, nullptr);
+        else if (kS)
+            rc = gpad_run_state_signals(cb->child[k], kx, kS, kz, ky, N, tol, nullptr);
         else
             rc = gpad_run_state(cb->child[k], kx, kz, ky, N, tol, nullptr);
         if (rc) return rc;
@@ -697,18 +851,22 @@ static int state_typed(ClassBinding* cb, T* x, T* z, T* y, int steps, int N, dou
     return finish_call(cb, st);
 }
 
-int classes_state(ClassBinding* cb, void* x, void* z, void* y, int steps, int N, double tol, int warm, void* xs,
-                  void* us, gpad_stats_t* st) {
-    const std::string where = steps > 0 ? "gpad_closed_loop" : "gpad_run_state";
+int classes_state(ClassBinding* cb, void* x, void* z, void* y, const void* sg, bool with_sig, const char* fn,
+                  int steps, int N, double tol, int warm, void* xs, void* us, gpad_stats_t* st) {
+    const std::string where(fn);
+    if (with_sig && cb->ns == 0) return no_classes(fn);  // (class signals: gpad_setup_class_signals)
+    if (!with_sig && cb->ns != 0)  // (dropping a disturbance silently is worse than an error)
+        return fail(GPAD_ERR_INVALID, where + ": class signals are bound, call the _signals entry point");
     if (!cb->plant) return fail(GPAD_ERR_NOT_SETUP, where + ": call gpad_setup_plant after gpad_setup_classes");
     if (steps > 0 && !cb->plant_dyn) return fail(GPAD_ERR_NOT_SETUP, where + ": plant bound without A, B");
-    if (!x || !z || !y) return fail(GPAD_ERR_INVALID, where + ": null vector");
+    if (!x || !z || !y || (with_sig && !sg)) return fail(GPAD_ERR_INVALID, where + ": null vector");
     if (N < 0 || steps < 0) return fail(GPAD_ERR_INVALID, where + ": N, steps must be >= 0");
     if (!(tol <= 0.0) && !std::isfinite(tol)) return fail(GPAD_ERR_INVALID, where + ": bad tol");
     if (cb->dims.dtype == GPAD_DTYPE_F64)
-        return state_typed<double>(cb, (double*)x, (double*)z, (double*)y, steps, N, tol, warm, (double*)xs,
-                                   (double*)us, st);
-    return state_typed<float>(cb, (float*)x, (float*)z, (float*)y, steps, N, tol, warm, (float*)xs, (float*)us, st);
+        return state_typed<double>(cb, (double*)x, (double*)z, (double*)y, (const double*)sg, steps, N, tol, warm,
+                                   (double*)xs, (double*)us, st);
+    return state_typed<float>(cb, (float*)x, (float*)z, (float*)y, (const float*)sg, steps, N, tol, warm, (float*)xs,
+                              (float*)us, st);
 }
 
 }  // namespace gpad

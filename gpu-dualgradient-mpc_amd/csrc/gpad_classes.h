@@ -3,8 +3,8 @@
 // here at their top), gpad_classes.cpp (the runtime) and gpad_classes.hip (the row permutations).
 //
 // Not here: classes running concurrently on several streams (they run one after the other on the
-// handle's stream; a closed loop can run them as one launch, gpad_class_loop_fused), exogenous signals,
-// per-pack true plants under a class binding, Hessian branches.
+// handle's stream; a closed loop can run them as one launch, gpad_class_loop_fused), per-pack true plants
+// under a class binding, Hessian branches.  Exogenous signals are here: gpad_setup_class_signals.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -43,6 +43,12 @@ struct TrajMove {
 template <typename T>
 hipError_t launch_class_traj_scatter(const TrajMove<T>& mv, const int* perm, const int* pos_off,
                                      const int* pos_cnt, int batch, int steps, hipStream_t s);
+// Signals, the inverse: src is the caller's [steps][batch][ns]; dst receives class k's contiguous
+// [steps][count_k][ns] block at element steps * offsets[k] * ns, or with pos_off == pos_cnt == null one
+// [steps][batch][ns] array in the sorted order (the fused class loop).  steps = 1: gpad_run_state_signals' s.
+template <typename T>
+hipError_t launch_class_sig_gather(const T* src, T* dst, int ns, const int* perm, const int* pos_off,
+                                   const int* pos_cnt, int batch, int steps, hipStream_t s);
 
 // ---- the fused class loop (gpad_class_loop_fused) ---------------------------------------------------
 // What one launch of the class-aware panel loop (gpad_loop_panel.hip) needs beyond a plain closed loop of
@@ -56,6 +62,9 @@ struct ClassLoop {
     int* qctr;         // [K] claim counters
     const void* frag;  // K fragment images, class k's at k * 2 * T * T * 1024 bytes
     int per_class;     // 1: K copies of every map, 0: one
+    int ns;            // class signals in the call (gpad_closed_loop_signals); 0: none
+    // ns == 0: the plant's maps; ns > 0: PM, Pg, A are the packed images [PM SM], [Pg Sg], [A E], rows of
+    // nx + ns columns, and all six arrays hold K copies when the plant or the signals are per class
     const float *PM, *M0, *Pg, *g0, *A, *B;  // (M0, g0: null when not bound)
 };
 // Host only (gpad_class_loop_deal): the class each of `grid` workgroups starts on, in proportion to the
@@ -82,9 +91,15 @@ int classes_setup_plant(ClassBinding* cb, bool per_class, int nx, int nu, const 
                         const void* Pg, const void* g0, const void* A, const void* B);
 int classes_run(ClassBinding* cb, void* z, void* y, const void* M, const void* g, int N, double tol,
                 gpad_stats_t* st);
-// steps == 0: gpad_run_state; steps >= 1: gpad_closed_loop
-int classes_state(ClassBinding* cb, void* x, void* z, void* y, int steps, int N, double tol, int warm, void* xs,
-                  void* us, gpad_stats_t* st);
+// whether a plant is bound; *dyn (nullable): with A and B
+bool classes_has_plant(const ClassBinding* cb, bool* dyn);
+// gpad_setup_class_signals (the handle class-bound): SM [n][ns], Sg [m][ns], E [nx][ns], per_class: K copies
+// of each; ns == 0 unbinds
+int classes_setup_signals(ClassBinding* cb, int ns, bool per_class, const void* SM, const void* Sg, const void* E);
+// steps == 0: gpad_run_state; steps >= 1: gpad_closed_loop.  with_sig: the _signals entry points (`where`),
+// sg their s [batch][ns] / S [steps][batch][ns] in the caller's order
+int classes_state(ClassBinding* cb, void* x, void* z, void* y, const void* sg, bool with_sig, const char* where,
+                  int steps, int N, double tol, int warm, void* xs, void* us, gpad_stats_t* st);
 int classes_last_stats(ClassBinding* cb, gpad_stats_t* st);
 int classes_accumulate(ClassBinding* cb, long long* acc);
 int classes_sync(ClassBinding* cb);

@@ -7,6 +7,7 @@
 //   gather :  sorted[pos][:]        = caller[perm[pos]][:]     (z, y, M, g  /  x, z, y: one launch)
 //   scatter:  caller[perm[pos]][:]  = sorted[pos][:]           (z, y  /  x, z, y: one launch)
 //   traj   :  caller[t][perm[pos]][:] = class block of pos, row (t, pos - offsets[k])   (xs, us: one launch)
+//   signals:  class block of pos, row (t, pos - offsets[k]) = caller[t][perm[pos]][:]   (s / S: one launch)
 // Pure data movement, O(batch (n + m)) words per call against the O(iterations n m) of the solves:
 // plain grid-stride kernels, one element per thread and trip, coalesced on the sorted side (the
 // caller's side is coalesced within a row).  perm is a permutation, so no two threads write one
@@ -79,6 +80,30 @@ __global__ __launch_bounds__(256) void class_traj_kernel(TrajMove<T> mv, const i
     }
 }
 
+// The inverse of class_traj_kernel for the one array of signals: thread e owns destination word e.  The
+// class blocks [steps][cnt_k][ns] lie one after the other, class k's at steps * off_k * ns, so word e sits
+// in the block of the class that sorted position e / (steps * ns) belongs to (off_k <= that < off_k + cnt_k).
+template <typename T>
+__global__ __launch_bounds__(256) void class_sig_kernel(const T* __restrict__ src, T* __restrict__ dst,
+                                                        const int* __restrict__ perm,
+                                                        const int* __restrict__ pos_off,
+                                                        const int* __restrict__ pos_cnt, int batch, int steps,
+                                                        int ns) {
+    const long long per_pos = (long long)steps * ns, total = per_pos * batch;
+    for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < total;
+         e += (long long)gridDim.x * blockDim.x) {
+        const int q = (int)(e / per_pos);
+        // (no tables: one sorted [steps][batch][ns] array, the fused class loop's)
+        const long long off = pos_off ? pos_off[q] : 0, cnt = pos_cnt ? pos_cnt[q] : batch;
+        const long long local = e - per_pos * off;  // word of the class block [steps][cnt][ns]
+        const long long step_words = cnt * ns;
+        const int t = (int)(local / step_words);
+        const long long r = local - (long long)t * step_words;
+        const int i = (int)(r / ns), j = (int)(r - (long long)i * ns);
+        dst[e] = src[((long long)t * batch + perm[off + i]) * ns + j];
+    }
+}
+
 static unsigned move_grid(long long total) {
     long long blocks = (total + 255) / 256;
     if (blocks > 4096) blocks = 4096;  // grid-stride beyond
@@ -119,6 +144,15 @@ hipError_t launch_class_traj_scatter(const TrajMove<T>& mv, const int* perm, con
     return hipGetLastError();
 }
 
+template <typename T>
+hipError_t launch_class_sig_gather(const T* src, T* dst, int ns, const int* perm, const int* pos_off,
+                                   const int* pos_cnt, int batch, int steps, hipStream_t s) {
+    if (ns == 0 || batch == 0 || steps == 0) return hipSuccess;
+    class_sig_kernel<T><<<move_grid((long long)batch * ns * steps), 256, 0, s>>>(src, dst, perm, pos_off, pos_cnt,
+                                                                                 batch, steps, ns);
+    return hipGetLastError();
+}
+
 template hipError_t launch_class_gather<float>(const RowMove<float>&, const int*, int, hipStream_t);
 template hipError_t launch_class_gather<double>(const RowMove<double>&, const int*, int, hipStream_t);
 template hipError_t launch_class_scatter<float>(const RowMove<float>&, const int*, int, hipStream_t);
@@ -127,5 +161,10 @@ template hipError_t launch_class_traj_scatter<float>(const TrajMove<float>&, con
                                                      int, hipStream_t);
 template hipError_t launch_class_traj_scatter<double>(const TrajMove<double>&, const int*, const int*, const int*,
                                                       int, int, hipStream_t);
+
+template hipError_t launch_class_sig_gather<float>(const float*, float*, int, const int*, const int*, const int*, int,
+                                                   int, hipStream_t);
+template hipError_t launch_class_sig_gather<double>(const double*, double*, int, const int*, const int*, const int*,
+                                                    int, int, hipStream_t);
 
 }  // namespace gpad

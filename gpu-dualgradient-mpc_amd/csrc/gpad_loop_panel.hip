@@ -32,7 +32,11 @@
 // columns), and all columns restart together exactly as at the kernel's start, which is the same
 // mechanism on the class the host dealt (LoopArgs::cls_start).  A full cycle with nothing claimed ends
 // the workgroup.  The columns restart together, so events stay workgroup-uniform by the argument above,
-// and no workgroup waits for another: the scan is bounded by K.
+// and no workgroup waits for another: the scan is bounded by K.  With class signals (la.ns > 0) nothing
+// else changes: S is one [steps][batch][ns] array in the sorted order, read at a column's sorted position
+// with the whole batch's stride; the per-class map copies are the packed images, rows of nx + ns columns
+// at (class * rows + row) * nxa; a restart reloads [x_0; S[0]] of the new columns; an empty column has no
+// refill and reads neither x_in nor S.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -472,8 +476,8 @@ hipError_t launch_loop_panel(const LoopArgs& a, int grid, hipStream_t st) {
         s.N < 1 || a.steps < 1 || s.batch < 1 || s.check_every < 1 || (s.tol > 0.0 && s.N % s.check_every != 0) ||
         grid < 1 || grid > kAbsmaxMaxBlocks || a.cls_K < 0)
         return hipErrorInvalidValue;
-    // the class loop: at most one workgroup per panel of a class (at most batch), the tables given, no signals
-    if (a.cls_K ? (!a.cls_off || !a.cls_start || a.ns || grid > s.batch) : grid > (s.batch + 15) / 16)
+    // the class loop: at most one workgroup per panel of a class (at most batch), the tables given
+    if (a.cls_K ? (!a.cls_off || !a.cls_start || grid > s.batch) : grid > (s.batch + 15) / 16)
         return hipErrorInvalidValue;
     switch (T) {
         case 1: return launch_loop_panel_t<1>(a, grid, st);

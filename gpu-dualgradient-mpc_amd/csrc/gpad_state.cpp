@@ -199,7 +199,9 @@ static int setup_signals_typed(gpad_handle_t h, int ns, const T* SM, const T* Sg
 extern "C" int gpad_setup_signals(gpad_handle_t h, int ns, const void* SM, const void* Sg, const void* E) {
     return gpad::abi_guard("gpad_setup_signals", [&]() -> int {
         if (!h) return fail(GPAD_ERR_INVALID, "gpad_setup_signals: null handle");
-        if (h->cls) return no_classes("gpad_setup_signals");
+        if (h->cls)
+            return fail(GPAD_ERR_UNSUPPORTED, "gpad_setup_signals: not available on a handle with a class binding "
+                                              "(gpad_setup_classes); bind class signals with gpad_setup_class_signals");
         if (!h->ready || !plant_bound(h))
             return fail(GPAD_ERR_NOT_SETUP, "gpad_setup_signals: call gpad_setup_plant first");
         if (ns < 0) return fail(GPAD_ERR_INVALID, "gpad_setup_signals: ns < 0");
@@ -213,6 +215,25 @@ extern "C" int gpad_setup_signals(gpad_handle_t h, int ns, const void* SM, const
         if (h->dims.dtype == GPAD_DTYPE_F64)
             return setup_signals_typed<double>(h, ns, (const double*)SM, (const double*)Sg, (const double*)E);
         return setup_signals_typed<float>(h, ns, (const float*)SM, (const float*)Sg, (const float*)E);
+    });
+}
+
+// gpad_setup_signals for a class-bound handle: one copy of SM, Sg, E per class (per_class) or one for all
+extern "C" int gpad_setup_class_signals(gpad_handle_t h, int ns, int per_class, const void* SM, const void* Sg,
+                                        const void* E) {
+    return gpad::abi_guard("gpad_setup_class_signals", [&]() -> int {
+        if (!h) return fail(GPAD_ERR_INVALID, "gpad_setup_class_signals: null handle");
+        if (!h->cls) return fail(GPAD_ERR_NOT_SETUP, "gpad_setup_class_signals: call gpad_setup_classes first");
+        bool dyn = false;
+        if (!gpad::classes_has_plant(h->cls, &dyn))
+            return fail(GPAD_ERR_NOT_SETUP, "gpad_setup_class_signals: call gpad_setup_plant or gpad_setup_plant_classes first");
+        if (ns < 0) return fail(GPAD_ERR_INVALID, "gpad_setup_class_signals: ns < 0");
+        if (per_class != 0 && per_class != 1)
+            return fail(GPAD_ERR_INVALID, "gpad_setup_class_signals: per_class must be 0 or 1");
+        if (ns > 0 && E && !dyn)
+            return fail(GPAD_ERR_INVALID, "gpad_setup_class_signals: E given, plant bound without A, B");
+        HIP_TRY(hipSetDevice(h->device));
+        return gpad::classes_setup_signals(h->cls, ns, per_class != 0, SM, Sg, E);
     });
 }
 
@@ -496,10 +517,9 @@ static int state_typed(gpad_handle_t h, T* x, T* z, T* y, const T* sg, int steps
 static int state_impl(gpad_handle_t h, void* x, void* z, void* y, const void* sg, bool with_sig, int steps, int N,
                       double tol, int warm, void* xs, void* us, gpad_stats_t* st, const char* where) {
     if (!h) return fail(GPAD_ERR_INVALID, std::string(where) + ": null handle");
-    if (h->cls) {
-        if (with_sig) return no_classes(where);
+    if (h->cls) {  // (with_sig: class signals, gpad_setup_class_signals; without them unsupported as before)
         HIP_TRY(hipSetDevice(h->device));
-        return gpad::classes_state(h->cls, x, z, y, steps, N, tol, warm, xs, us, st);
+        return gpad::classes_state(h->cls, x, z, y, sg, with_sig, where, steps, N, tol, warm, xs, us, st);
     }
     if (!h->ready) return fail(GPAD_ERR_NOT_SETUP, std::string(where) + ": call gpad_setup first");
     if (!plant_bound(h))

@@ -46,7 +46,7 @@ EXPORTS = [
     "gpad_group_rccl_library",
     "gpad_setup_signals", "gpad_run_state_signals", "gpad_closed_loop_signals",
     "gpad_class_order", "gpad_setup_classes", "gpad_setup_plant_classes",
-    "gpad_class_loop_fused", "gpad_class_loop_deal",
+    "gpad_class_loop_fused", "gpad_class_loop_deal", "gpad_setup_class_signals",
 ]
 GROUP_RCCL, GROUP_PEER = 1, 2
 
@@ -206,6 +206,9 @@ def load(path: str | None = None) -> C.CDLL:
         L.gpad_class_loop_deal.argtypes = [C.POINTER(i), i, i, C.POINTER(i)]
         for name in ("gpad_class_loop_fused", "gpad_class_loop_deal"):
             getattr(L, name).restype = i
+    if hasattr(L, "gpad_setup_class_signals"):  # (added within 0.6; absent from older builds under GPAD_LIB_TOLERANT)
+        L.gpad_setup_class_signals.argtypes = [vp, i, i, cvp, cvp, cvp]
+        L.gpad_setup_class_signals.restype = i
     L.gpad_datafile_read.argtypes = [C.c_char_p, i, C.POINTER(DataFile)]
     L.gpad_datafile_write.argtypes = [C.c_char_p, i, C.POINTER(DataFile)]
     L.gpad_datafile_free.argtypes = [C.POINTER(DataFile)]

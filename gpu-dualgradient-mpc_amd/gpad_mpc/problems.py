@@ -246,6 +246,27 @@ def battery_fleet(n_u: int, N: int, caps, **limits):
     return qp, plant
 
 
+def battery_fleet_signals(n_u: int, N: int, caps, **limits):
+    """``battery_fleet`` under load and with state-of-charge references: pack (or class) k is
+    ``battery_plant_signals(n_u, N, capacity_ah=caps[k])``, every array stacked on a leading axis, the
+    signal maps SM (batch, n, 1 + n_u), Sg (batch, m, 1 + n_u), E (batch, n_u, 1 + n_u) included; L is
+    the maximum over the packs.  Minus the signal maps it equals ``battery_fleet(n_u, N, caps)`` bit for
+    bit.  With per-class ``caps`` this is what ``setup_classes`` + a stacked ``setup_plant`` +
+    ``setup_class_signals`` take; ``expand_classes`` gives the ``shared=False`` fleet it equals."""
+    caps = np.asarray(caps, np.float64)
+    if caps.ndim != 2 or caps.shape[1] != n_u:
+        raise ValueError(f"caps must be [batch][{n_u}], got {caps.shape}")
+    packs = [battery_plant_signals(n_u, N, capacity_ah=c, **limits) for c in caps]
+    stack = lambda f: np.stack([f(qp, pl) for qp, pl in packs])  # noqa: E731
+    qp = QP(ML=stack(lambda q, p: q.ML), M=stack(lambda q, p: q.M), G=stack(lambda q, p: q.G),
+            g=stack(lambda q, p: q.g), L=max(q.L for q, _ in packs), H=stack(lambda q, p: q.H),
+            q=stack(lambda q, p: q.q), meta=dict(kind="battery_fleet_signals", n_u=n_u, N=N, caps=caps))
+    plant = Plant(PM=stack(lambda q, p: p.PM), Pg=stack(lambda q, p: p.Pg), A=stack(lambda q, p: p.A),
+                  B=stack(lambda q, p: p.B), M0=None, g0=stack(lambda q, p: p.g0), SM=stack(lambda q, p: p.SM),
+                  Sg=stack(lambda q, p: p.Sg), E=stack(lambda q, p: p.E))
+    return qp, plant
+
+
 def expand_classes(qp: QP, plant: Plant, class_of):
     """The per-instance stacks of the ``shared=False`` binding from per-class stacks: ``qp`` / ``plant``
     stacked over K classes (as ``battery_fleet(n_u, N, class_caps)`` returns them) and ``class_of``

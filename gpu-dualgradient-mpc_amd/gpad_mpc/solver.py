@@ -374,6 +374,30 @@ class GpadSolver:
         opt = lambda a: _ptr(a) if a is not None else None  # noqa: E731
         check(self.lib.gpad_setup_signals(self.h, int(ns), opt(SM), opt(Sg), opt(E)), "gpad_setup_signals")
 
+    def setup_class_signals(self, SM=None, Sg=None, E=None, *, ns: int | None = None) -> None:
+        """``setup_signals`` after ``setup_classes`` and ``setup_plant`` (gpad_setup_class_signals).
+        Stacked maps SM (K, n, ns), Sg (K, m, ns), E (K, nx, ns) bind one copy per class, instance b using
+        copy class_of[b]; 2-d maps serve every class.  Either goes with a stacked or a plain plant.  None is
+        a map of zeros; ``ns`` is read from the maps given (needed when all three are None); ``ns=0``
+        unbinds, as does a later ``setup_plant`` / ``setup_classes`` / ``setup*``.  Then pass ``s=`` to
+        ``run_state`` and ``signals=`` to ``closed_loop`` in the caller's instance order; results are bit
+        for bit those of ``setup(..., shared=False)`` + ``setup_signals`` on the expanded fleet."""
+        given = [a for a in (SM, Sg, E) if a is not None]
+        if ns is None:
+            if not given:
+                raise ValueError("setup_class_signals: give a map or ns")
+            ns = given[0].shape[-1]
+        if any(a.shape[-1] != ns for a in given):
+            raise ValueError(f"setup_class_signals: every map needs {ns} columns")
+        if any(a.ndim not in (2, 3) or a.ndim != given[0].ndim for a in given):
+            raise ValueError("setup_class_signals: the maps must be all 2-dimensional or all stacked (K, rows, ns)")
+        stacked = bool(given) and given[0].ndim == 3
+        if stacked and self._classes and any(a.shape[0] != self._classes for a in given):
+            raise ValueError(f"setup_class_signals: stacked maps must lead with K = {self._classes}")
+        opt = lambda a: _ptr(a) if a is not None else None  # noqa: E731
+        check(self.lib.gpad_setup_class_signals(self.h, int(ns), 1 if stacked else 0, opt(SM), opt(Sg), opt(E)),
+              "gpad_setup_class_signals")
+
     def run_state(self, x, z, y, N: int, tol: float = 0.0, *, stats: bool = True, s=None):
         """GPAD for every instance's state x [batch][nx] (M(x), g(x) formed on the device); with
         signals bound (``setup_signals``), ``s`` [batch][ns] is required."""

@@ -37,7 +37,7 @@ extern "C" {
                               * GPAD_OPT_LOOP_PANEL (option 23) and the reported GPAD_KERNEL_LOOP_PANEL (7);
                               * gpad_class_order, gpad_setup_classes, gpad_setup_plant_classes;
                               * gpad_class_loop_fused, gpad_class_loop_deal and the reported
-                              * GPAD_KERNEL_LOOP_CLASSES (8) */
+                              * GPAD_KERNEL_LOOP_CLASSES (8); gpad_setup_class_signals */
 
 /* status codes */
 #define GPAD_OK 0
@@ -355,8 +355,9 @@ int gpad_closed_loop_signals(gpad_handle_t h, void* x, void* z, void* y, const v
  *     does not qualify runs the lockstep loop); gpad_class_loop_fused, where it takes the call, is
  *     looked at before the forwarded loop options.  The plain gpad_setup_plant binds the same maps for
  *     every class.
- *   - gpad_setup_hessian, gpad_setup_plant_batch, gpad_setup_signals (and the _signals runs) and
- *     gpad_run_scaled return GPAD_ERR_UNSUPPORTED, gpad_last_error naming the class binding.
+ *   - gpad_setup_hessian, gpad_setup_plant_batch, gpad_setup_signals and gpad_run_scaled return
+ *     GPAD_ERR_UNSUPPORTED, gpad_last_error naming the class binding.  Signals are bound with
+ *     gpad_setup_class_signals below; until they are, the _signals runs return GPAD_ERR_UNSUPPORTED too.
  *   - the phase diagnostics (gpad_phase_plan, gpad_phase_counts, gpad_last_phases) return 0.
  *   - a later gpad_setup, gpad_setup_scaled or gpad_setup_flat ends the binding and frees everything
  *     it held; a later gpad_setup_classes replaces it.
@@ -368,8 +369,8 @@ int gpad_closed_loop_signals(gpad_handle_t h, void* x, void* z, void* y, const v
  * The classes run one after the other on the handle's stream (a loop: class 0's `steps` steps, then
  * class 1's); they are independent, so the order changes no result.  Every (class, step) so pays its own
  * launches and its own tail on a part of the GPU; gpad_class_loop_fused below runs a closed loop of every
- * class as one launch instead.  Not provided: classes running concurrently on several streams, signals,
- * per-pack true plants under a class binding, Hessian branches. */
+ * class as one launch instead.  Not provided: classes running concurrently on several streams, per-pack
+ * true plants under a class binding, Hessian branches. */
 
 /* host only, no device work (for tests/tools, like gpad_plan_phases): the class-sorted order.
  * perm[batch]: sorted position -> instance, classes ascending, instances ascending inside a class
@@ -389,6 +390,27 @@ int gpad_setup_classes(gpad_handle_t h, const gpad_dims_t* dims, int K, const in
 int gpad_setup_plant_classes(gpad_handle_t h, int nx, int nu, const void* PM, const void* M0,
                              const void* Pg, const void* g0, const void* A, const void* B);
 
+/* gpad_setup_signals for a class-bound handle with a plant bound (gpad_setup_plant or
+ * gpad_setup_plant_classes; either combines with either per_class).  per_class = 1: every non-NULL map holds
+ * K copies, SM [K][n][ns], Sg [K][m][ns], E [K][nx][ns], and instance b uses copy class_of[b] (an empty
+ * class's copy is present and ignored); per_class = 0: one copy serves every class.  dtype and memory follow
+ * dims; a NULL map is a map of zeros whose terms are evaluated; the evaluation order is gpad_setup_signals'.
+ * ns >= 1 binds, ns == 0 unbinds, ns < 0 and per_class outside {0, 1} are GPAD_ERR_INVALID, as is a non-NULL
+ * E on a plant bound without A, B; GPAD_ERR_NOT_SETUP on a handle that is not class-bound or has no plant.
+ * A later gpad_setup_plant, gpad_setup_plant_classes, gpad_setup_classes or any gpad_setup* unbinds.
+ * With class signals bound, gpad_run_state_signals and gpad_closed_loop_signals take s [batch][ns] and
+ * S [steps][batch][ns] in the caller's instance order (dims.memory), a NULL s / S is GPAD_ERR_INVALID, and
+ * the plain gpad_run_state / gpad_closed_loop return GPAD_ERR_INVALID as on a plain handle.  Class k binds
+ * its copy with gpad_setup_signals and runs on its own rows of S; the forwarded GPAD_OPT_LOOP_ASYNC /
+ * GPAD_OPT_LOOP_PANEL apply by each class's own rules (nx + ns <= 64; ns is unbounded on the lockstep loop),
+ * and gpad_class_loop_fused takes a gpad_closed_loop_signals call by its rules below with nx + ns in the
+ * place of nx.  Results are bit for bit those of the dims.shared = 0 binding of the expanded fleet
+ * (gpad_setup_plant_batch + gpad_setup_signals, instance b holding the copies of class class_of[b]):
+ * outputs, trajectories, per-step counts and codes, stats by the rules above; tol_floor and the flags cover
+ * g(x, s) of every step of every class. */
+int gpad_setup_class_signals(gpad_handle_t h, int ns, int per_class, const void* SM, const void* Sg,
+                             const void* E);
+
 /* The fused class loop (opt-in, off by default): gpad_closed_loop of a class-bound handle as ONE launch of
  * the class-aware MFMA panel loop (the kernel of GPAD_OPT_LOOP_PANEL; reported kernel =
  * GPAD_KERNEL_LOOP_CLASSES).  A workgroup serves one class at a time -- its 16 panel columns hold packs of
@@ -400,8 +422,8 @@ int gpad_setup_plant_classes(gpad_handle_t h, int nx, int nu, const void* PM, co
  * cleared by a later gpad_setup_classes and by every gpad_setup*.
  * It is looked at before the forwarded loop options, and takes a call when steps >= 1 and the shape
  * meets the rules of GPAD_OPT_LOOP_PANEL (the same for every class, which share dims): f32, n, m <= 256,
- * dims.kernel AUTO or PANEL, N >= 1, tol <= 0 or N % check_every == 0, nx <= 64, nu <= min(n, 64), the
- * plant bound with A and B.  Any other call (f64, gpad_run, gpad_run_state, ...) runs class by class exactly as
+ * dims.kernel AUTO or PANEL, N >= 1, tol <= 0 or N % check_every == 0, nx <= 64 (with class signals
+ * nx + ns <= 64), nu <= min(n, 64), the plant bound with A and B.  Any other call (f64, gpad_run, gpad_run_state, ...) runs class by class exactly as
  * if it were off, with that path's results and reported kernel, silently, as the loop options do.
  * Grid: min(sum_k ceil(count_k / 16), resident workgroups, 1024), capped by GPAD_OPT_PANEL_MAX_GRID; the
  * workgroups start on the classes gpad_class_loop_deal gives them.

@@ -5,7 +5,7 @@ modes: eps cold / eps warm (tol 1e-4, N 3000) and fixed N = 100.
 
   python tools/loop_ab.py [--rounds 3] [--steps 20] [--batches 1 64 256 512 2048 8192] [--fleet | --signals]
                           [--panel]
-  python tools/loop_ab.py --classes K [--rounds 3] [--steps 20] [--batches 256 2048 8192]
+  python tools/loop_ab.py --classes K [--signals] [--rounds 3] [--steps 20] [--batches 256 2048 8192]
 
 --panel: a third variant, "panel" (GPAD_OPT_LOOP_PANEL, csrc/gpad_loop_panel.hip: the one-launch loop on the
 MFMA panels), alternated with lockstep and async in the same process and checked against lockstep like
@@ -41,6 +41,15 @@ variants.  With K = 1 two more variants: "shared", the plain shared-matrix handl
 bookkeeping of the fused kernel and the row permutations cost against the plain panel loop.  Every variant's outputs are compared with "fleet" bit for bit first; each line has
 the rates, `<variant>_over_fleet` and `<variant>_faster` ("none" inside the spread of the rounds).
 
+--classes K --signals: the same variants on problems.battery_fleet_signals (class k =
+battery_plant_signals(4, 10, capacity_ah = caps[k]); s = [i_load, r_1 .. r_4] per step and pack, drawn as for
+--signals above): "fleet" binds setup_signals with stacked maps, the class variants setup_class_signals
+(gpad_setup_class_signals) with one copy per class, "shared" / "shared_panel" class 0's maps.  Every variant
+is then also run without signals in the same process (a second set of handles, checked against its own
+"fleet" first); `sig_over_plain` is the rate with signals over the rate without, per variant -- what the
+S gather and the wider state rows cost (informational: the signals change the QPs, so also the counts; the
+fleet's own ratio beside it shows that part).
+
 Per batch and mode the two variants' x, z, y, xs, us and per-step iteration counts are compared first
 (that run is also each variant's warm-up); a mismatch aborts the batch.  Then `rounds` rounds
 alternate the variants.  One JSON line per case: kernel_ms (events around the whole loop) and host
@@ -73,12 +82,17 @@ def classes_ab(args):
     from gpad_mpc import problems
     K, steps, rounds = args.classes, args.steps, max(3, args.rounds)
     dev = torch.device("cuda:0")
-    qp, pl = problems.battery_fleet(4, 10, problems.battery_fleet_caps(K, 4, K))
+    gen = problems.battery_fleet_signals if args.signals else problems.battery_fleet
+    qp, pl = gen(4, 10, problems.battery_fleet_caps(K, 4, K))
     n, m, nx, nu = qp.n, qp.m, pl.nx, pl.nu
     L = float(np.float32(qp.L))
     t32 = lambda a: torch.from_numpy(np.ascontiguousarray(np.asarray(a, np.float64).astype(np.float32))).to(dev)  # noqa: E731
-    cls = {k: t32(a) for k, a in dict(ML=qp.ML, G=qp.G, PM=pl.PM, Pg=pl.Pg, g0=pl.g0, A=pl.A, B=pl.B).items()}
-    print(json.dumps({"plant": f"battery_fleet(4, 10), {K} classes, class_of[b] = b % {K}", "n": n, "m": m,
+    maps = dict(ML=qp.ML, G=qp.G, PM=pl.PM, Pg=pl.Pg, g0=pl.g0, A=pl.A, B=pl.B)
+    if args.signals:
+        maps.update(SM=pl.SM, Sg=pl.Sg, E=pl.E)
+    cls = {k: t32(a) for k, a in maps.items()}
+    gname = "battery_fleet_signals" if args.signals else "battery_fleet"
+    print(json.dumps({"plant": f"{gname}(4, 10), {K} classes, class_of[b] = b % {K}", "n": n, "m": m,
                       "steps": steps, "rounds": rounds, "device": torch.cuda.get_device_name(0),
                       "cus": torch.cuda.get_device_properties(0).multi_processor_count}))
     names = ("fleet", "classes", "classes_panel", "classes_async", "classes_fused") + (
@@ -89,64 +103,100 @@ def classes_ab(args):
         class_of = np.arange(B, dtype=np.int32) % K
         X0 = torch.from_numpy((np.random.default_rng(B).random((B, nx)) - 0.5).astype(np.float32)).to(dev)
         idx = torch.from_numpy(class_of.astype(np.int64)).to(dev)
-        var = {}
-        for name in names:
-            s = gpad_mpc.GpadSolver(0)
-            if name == "fleet":  # expand_classes on the device: instance b holds the arrays of class b % K
-                f = {k: a[idx].contiguous() for k, a in cls.items()}
-                s.setup(f["ML"], f["G"], L, n=n, m=m, batch=B, shared=False)
-                s.setup_plant(f["PM"], f["Pg"], g0=f["g0"], A=f["A"], B=f["B"])
-                del f
-            elif name in ("shared", "shared_panel"):
-                s.setup(cls["ML"][0], cls["G"][0], L, n=n, m=m, batch=B, shared=True)
-                s.setup_plant(cls["PM"][0], cls["Pg"][0], g0=cls["g0"][0], A=cls["A"][0], B=cls["B"][0])
-                s.set_options(loop_panel=int(name == "shared_panel"))
-            else:
-                s.setup_classes(cls["ML"], cls["G"], L, class_of, n=n, m=m)
-                s.setup_plant(cls["PM"], cls["Pg"], g0=cls["g0"], A=cls["A"], B=cls["B"])
-                s.set_options(loop_panel=int(name == "classes_panel"), loop_async=int(name == "classes_async"))
-                s.set_class_loop_fused(name == "classes_fused")
-            buf = dict(x=torch.empty(B, nx, device=dev), z=torch.empty(B, n, device=dev),
-                       y=torch.empty(B, m, device=dev), xs=torch.empty(steps, B, nx, device=dev),
-                       us=torch.empty(steps, B, nu, device=dev))
-            var[name] = (s, buf)
+        sig = None
+        if args.signals:  # (drawn as main()'s --signals draws them)
+            rng = np.random.default_rng([B, 1])
+            sig = torch.from_numpy(np.concatenate([rng.uniform(-5, 5, (steps, B, 1)),
+                                                   rng.uniform(-0.1, 0.1, (steps, B, nx))],
+                                                  axis=-1).astype(np.float32)).to(dev)
 
-        def enqueue(name, mode, **kw):
-            s, b = var[name]
+        def build(with_sig):
+            var = {}
+            for name in names:
+                s = gpad_mpc.GpadSolver(0)
+                if name == "fleet":  # expand_classes on the device: instance b holds the arrays of class b % K
+                    f = {k: a[idx].contiguous() for k, a in cls.items()}
+                    s.setup(f["ML"], f["G"], L, n=n, m=m, batch=B, shared=False)
+                    s.setup_plant(f["PM"], f["Pg"], g0=f["g0"], A=f["A"], B=f["B"])
+                    if with_sig:
+                        s.setup_signals(f["SM"], f["Sg"], f["E"])
+                    del f
+                elif name in ("shared", "shared_panel"):
+                    s.setup(cls["ML"][0], cls["G"][0], L, n=n, m=m, batch=B, shared=True)
+                    s.setup_plant(cls["PM"][0], cls["Pg"][0], g0=cls["g0"][0], A=cls["A"][0], B=cls["B"][0])
+                    if with_sig:
+                        s.setup_signals(cls["SM"][0], cls["Sg"][0], cls["E"][0])
+                    s.set_options(loop_panel=int(name == "shared_panel"))
+                else:
+                    s.setup_classes(cls["ML"], cls["G"], L, class_of, n=n, m=m)
+                    s.setup_plant(cls["PM"], cls["Pg"], g0=cls["g0"], A=cls["A"], B=cls["B"])
+                    if with_sig:
+                        s.setup_class_signals(cls["SM"], cls["Sg"], cls["E"])
+                    s.set_options(loop_panel=int(name == "classes_panel"), loop_async=int(name == "classes_async"))
+                    s.set_class_loop_fused(name == "classes_fused")
+                buf = dict(x=torch.empty(B, nx, device=dev), z=torch.empty(B, n, device=dev),
+                           y=torch.empty(B, m, device=dev), xs=torch.empty(steps, B, nx, device=dev),
+                           us=torch.empty(steps, B, nu, device=dev))
+                var[name] = (s, buf)
+            return var
+
+        var = build(args.signals)
+        plain = build(False) if args.signals else None  # the same variants without signals: sig_over_plain
+
+        def enqueue(vs, name, mode, **kw):
+            s, b = vs[name]
             b["x"].copy_(X0)
             b["z"].zero_()
             b["y"].zero_()
             torch.cuda.synchronize()
             return s.closed_loop(b["x"], b["z"], b["y"], steps, mode["N"], mode["tol"], warm=mode["warm"],
-                                 xs=b["xs"], us=b["us"], **kw)
+                                 xs=b["xs"], us=b["us"], signals=sig if vs is var else None, **kw)
 
-        for mname, mode in MODES.items():
+        def measure(vs, mname, mode):
+            """The output check (each variant's warm-up), then `rounds` alternated rounds: (its, kern, ms,
+            wall), or None after reporting a mismatch."""
             its, kern = {}, {}
-            for name in var:  # the output check, and each variant's warm-up
+            for name in vs:
                 its[name] = np.zeros(steps * B, np.int32)
-                kern[name] = enqueue(name, mode, iters=its[name])["kernel"]
-            bad = [f"{v}.{k}" for k in ("x", "z", "y", "xs", "us") for v in var if v != "fleet"
-                   if not torch.equal(var["fleet"][1][k].view(torch.int32), var[v][1][k].view(torch.int32))]
-            bad += [f"{v}.iters" for v in var if not np.array_equal(its["fleet"], its[v])]
+                kern[name] = enqueue(vs, name, mode, iters=its[name])["kernel"]
+            bad = [f"{v}.{k}" for k in ("x", "z", "y", "xs", "us") for v in vs if v != "fleet"
+                   if not torch.equal(vs["fleet"][1][k].view(torch.int32), vs[v][1][k].view(torch.int32))]
+            bad += [f"{v}.iters" for v in vs if not np.array_equal(its["fleet"], its[v])]
             if bad or any(kern[v] is None or (kern[v] in ("loop", "loop_panel", "loop_classes")) != (v in want) or
-                          (v in want and kern[v] != want[v]) for v in var):
+                          (v in want and kern[v] != want[v]) for v in vs):
                 print(json.dumps({"batch": B, "mode": mname, "error": "outputs differ" if bad else "wrong kernel",
-                                  "differ": bad, "kernels": kern}))
-                break
-            ms = {k: [] for k in var}
-            wall = {k: [] for k in var}
+                                  "differ": bad, "kernels": kern, **({"signals": vs is var} if args.signals else {})}))
+                return None
+            ms = {k: [] for k in vs}
+            wall = {k: [] for k in vs}
             for _ in range(rounds):
-                for name in var:
-                    s = var[name][0]
+                for name in vs:
+                    s = vs[name][0]
                     t0 = time.perf_counter()
-                    enqueue(name, mode, stats=False)
+                    enqueue(vs, name, mode, stats=False)
                     s.sync()
                     wall[name].append((time.perf_counter() - t0) * 1e3)
                     ms[name].append(s.last_stats()["kernel_ms"])
+            return its, kern, ms, wall
+
+        for mname, mode in MODES.items():
+            res = measure(var, mname, mode)
+            if res is None:
+                break
+            its, kern, ms, wall = res
             med = {k: float(np.median(v)) for k, v in ms.items()}
             rate = {k: B * steps / (med[k] / 1e3) for k in var}
             faster = lambda v, ref: (v if max(ms[v]) < min(ms[ref]) else  # noqa: E731
                                      ref if min(ms[v]) > max(ms[ref]) else "none")
+            extra = {}
+            if plain is not None:
+                pres = measure(plain, mname, mode)
+                if pres is None:
+                    break
+                pmed = {k: float(np.median(v)) for k, v in pres[2].items()}
+                extra = {"signals": True, "plain_mean_iters_per_solve": round(float(pres[0]["fleet"].mean()), 1),
+                         "plain_median_ms": {k: round(v, 4) for k, v in pmed.items()},
+                         "sig_over_plain": {k: round(pmed[k] / med[k], 3) for k in var}}
             print(json.dumps({
                 "batch": B, "classes": K, "mode": mname, "kernels": kern,
                 "mean_iters_per_solve": round(float(its["fleet"].mean()), 1),
@@ -163,9 +213,10 @@ def classes_ab(args):
                     "classes_fused_vs_shared_panel_faster": faster("classes_fused", "shared_panel")}
                    if "shared_panel" in var else {}),
                 **({"classes_over_shared": round(rate["classes"] / rate["shared"], 3),
-                    "classes_vs_shared_faster": faster("classes", "shared")} if "shared" in var else {})}),
+                    "classes_vs_shared_faster": faster("classes", "shared")} if "shared" in var else {}),
+                **extra}),
                 flush=True)
-        for s, _ in var.values():
+        for s, _ in list(var.values()) + list((plain or {}).values()):
             s.close()
 
 
@@ -180,8 +231,8 @@ def main():
     ap.add_argument("--classes", type=int, default=0, metavar="K")
     args = ap.parse_args()
     if args.classes:
-        if args.fleet or args.signals or args.panel or args.classes < 1:
-            ap.error("--classes K >= 1 stands alone")
+        if args.fleet or args.panel or args.classes < 1:
+            ap.error("--classes K >= 1 goes with --signals alone")
         if args.batches is None:
             args.batches = [256, 2048, 8192]
         return classes_ab(args)
