@@ -28,11 +28,13 @@
 // [steps][batch][len] array in the sorted order and the counts and codes come from that handle.  Every other
 // call still pays each class's own tail.
 //
-// Exogenous signals (gpad_setup_class_signals): child k binds class k's copy of SM, Sg, E with
-// gpad_setup_signals and runs the _signals entry points on its own contiguous [steps][count_k][ns] block of
-// S, which one more launch gathers from the caller's [steps][batch][ns] (launch_class_sig_gather).  The fused
-// loop reads S as one [steps][batch][ns] array in the sorted order and the binding's own packed images
-// [PM SM], [Pg Sg], [A E] (pack_images), a copy per class when the plant or the signals are per class.
+// The plant maps and the class signals live once, in the binding's plant store (gpad_plant_store.h): one copy
+// of the six maps and of the packed images [PM SM], [Pg Sg], [A E], or one per class.  No handle holds a copy of
+// its own: the binding lends the store (lend_plant), copy k to child k and every copy to the whole-batch handle.
+//
+// Exogenous signals (gpad_setup_class_signals): child k runs the _signals entry points on its own contiguous
+// [steps][count_k][ns] block of S, which one more launch gathers from the caller's [steps][batch][ns]
+// (launch_class_sig_gather).  The fused loop reads S as one [steps][batch][ns] array in the sorted order.
 //
 // Not in this file: classes running concurrently on several streams, per-pack true plants under a class
 // binding, Hessian branches.
@@ -55,24 +57,11 @@ struct ClassBinding {
     DevBuf sorted, stage;                // class-sorted workspace; host callers' staging in caller order
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     bool timed = false;
-    bool plant = false, plant_dyn = false;
-    int nx = 0, nu = 0;
     int last_steps = 0;               // solves per instance of the last run (0: no run yet)
     std::vector<int> it, cd;          // one child's counts and codes on their way to the caller
-    // plant maps (classes_setup_plant): PM | M0 | Pg | g0 | A | B on the device, each array one copy per class
-    // (gpad_setup_plant_classes) or one for all; the children bind their copies from here
-    DevBuf maps;
-    size_t map_off[6] = {0, 0, 0, 0, 0, 0};  // element offsets in maps
-    bool map_has[6] = {false, false, false, false, false, false};
-    bool per_class = false;
-    // class signals (classes_setup_signals): ns > 0 while bound.  f32 bindings keep what the fused loop reads,
-    //   [PM SM] | [Pg Sg] | [A E] | M0 | g0 | B
-    // every array K times over when the plant or the signals are per class (img_per_class), else once; M0, g0, B
-    // are there only when they had to be replicated (signals per class over a plant with one copy)
-    int ns = 0;
-    DevBuf simg;
-    size_t img_off[6] = {0, 0, 0, 0, 0, 0};
-    bool img_per_class = false, img_rep = false;
+    // the plant maps and class signals (classes_setup_plant, classes_setup_signals): one copy, or one per class.
+    // The children and the whole-batch handle read them here (lend_plant)
+    PlantStore plant;
     // the fused class loop (gpad_class_loop_fused): every class in one launch of the class-aware panel loop,
     // run through a handle of the whole batch in the sorted order (shared = 1 with the major class's matrices,
     // which the launch never reads: it takes every class's fragment image from `frags`).  That handle owns
@@ -142,8 +131,7 @@ void classes_free(ClassBinding* cb) {
     for (gpad_handle_t c : cb->child)
         if (c) (void)gpad_destroy(c);  // (synchronises the stream first)
     if (cb->fused) (void)gpad_destroy(cb->fused);
-    cb->maps.release();
-    cb->simg.release();
+    cb->plant.release();
     cb->mats.release();
     cb->frags.release();
     cb->ftab.release();
@@ -282,29 +270,12 @@ int classes_set_option(ClassBinding* cb, int option, int value) {
     return GPAD_OK;
 }
 
-// the maps of class k (or the one copy) as the children and the fused handle bind them
-static void class_maps(const ClassBinding* cb, int k, const void* out[6]) {
-    const gpad_dims_t& d = cb->dims;
-    const size_t es = esize(d.dtype);
-    const size_t elems[6] = {(size_t)d.n * cb->nx, (size_t)d.n, (size_t)d.m * cb->nx, (size_t)d.m,
-                             (size_t)cb->nx * cb->nx, (size_t)cb->nx * cb->nu};
-    for (int i = 0; i < 6; ++i)
-        out[i] = cb->map_has[i] ? (const char*)cb->maps.p + es * (cb->map_off[i] + (cb->per_class ? elems[i] * k : 0))
-                                : nullptr;
-}
-
-// The fused handle's plant: it needs nx, nu and which maps are bound; the launch reads the binding's own
-// per-class copies (ClassLoop), so any class's maps do.
-static int fused_bind_plant(ClassBinding* cb) {
-    const void* a[6];
-    class_maps(cb, 0, a);
-    return gpad_setup_plant(cb->fused, cb->nx, cb->nu, a[0], a[1], a[2], a[3], a[4], a[5]);  // (synchronises)
-}
-
-// The fused handle's signals: it needs ns alone; the launch reads the binding's packed images (ClassLoop), so
-// maps of zeros do.  (ns == 0 unbinds.)
-static int fused_bind_signals(ClassBinding* cb) {
-    return gpad_setup_signals(cb->fused, cb->ns, nullptr, nullptr, nullptr);
+// The binding lends its store: child k runs with copy k of the maps and images (or the one copy), the whole-batch
+// handle with every copy, a copy per class.  Called after every bind, rebind or unbind and for a new handle.
+static void lend_plant(ClassBinding* cb) {
+    for (int k = 0; k < cb->K; ++k)
+        if (cb->child[k]) attach_plant(cb->child[k], &cb->plant, k, false);
+    if (cb->fused) attach_plant(cb->fused, &cb->plant, 0, true);
 }
 
 // The whole-batch handle of the fused loop with what its launch reads: the K fragment images (copied from
@@ -342,11 +313,8 @@ static int fused_create(ClassBinding* cb, const Tuning& tune) {
     }
     cb->fused = f;
     cb->start_grid = 0;
-    if (cb->plant && ((rc = fused_bind_plant(cb)) || (rc = fused_bind_signals(cb)))) {
-        (void)gpad_destroy(f);
-        cb->fused = nullptr;
-    }
-    return rc;
+    lend_plant(cb);
+    return GPAD_OK;
 }
 
 int classes_loop_fused(ClassBinding* cb, bool on, const Tuning& tune) {
@@ -358,147 +326,20 @@ int classes_loop_fused(ClassBinding* cb, bool on, const Tuning& tune) {
 
 int classes_setup_plant(ClassBinding* cb, bool per_class, int nx, int nu, const void* PM, const void* M0,
                         const void* Pg, const void* g0, const void* A, const void* B) {
-    const char* fn = per_class ? "gpad_setup_plant_classes" : "gpad_setup_plant";
-    if (nx <= 0 || nu < 0 || !PM || !Pg) return fail(GPAD_ERR_INVALID, std::string(fn) + ": bad arguments");
-    if ((A == nullptr) != (B == nullptr) || (A && nu == 0))
-        return fail(GPAD_ERR_INVALID, std::string(fn) + ": give A and B together (nu >= 1)");
-    const gpad_dims_t& d = cb->dims;
-    if (nu > d.n) return fail(GPAD_ERR_INVALID, std::string(fn) + ": nu > n");
-    const size_t es = esize(d.dtype), copies = per_class ? (size_t)cb->K : 1;
-    const void* src[6] = {PM, M0, Pg, g0, A, B};
-    const size_t elems[6] = {(size_t)d.n * nx, (size_t)d.n, (size_t)d.m * nx, (size_t)d.m, (size_t)nx * nx,
-                             (size_t)nx * nu};
-    // the maps on the device, kept: the children bind their copies from here, the fused loop reads them in place
-    size_t total = 0;
-    for (int i = 0; i < 6; ++i) total += src[i] ? elems[i] * copies : 0;
-    cb->plant = false;  // (a failed rebinding leaves none)
-    cb->ns = 0;         // (a new plant unbinds the signals, the children's and the fused handle's with it)
-    int rc = cb->maps.ensure(es * total);
-    if (rc) return rc;
-    const hipMemcpyKind kind = d.memory == GPAD_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
-    size_t off = 0;
-    hipError_t e = hipSuccess;
-    for (int i = 0; i < 6 && e == hipSuccess; ++i) {
-        cb->map_has[i] = src[i] != nullptr;
-        cb->map_off[i] = off;
-        if (!src[i] || elems[i] == 0) continue;
-        e = hipMemcpyAsync((char*)cb->maps.p + es * off, src[i], es * elems[i] * copies, kind, cb->stream);
-        off += elems[i] * copies;
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(cb->stream);
-    if (e != hipSuccess) return fail(GPAD_ERR_HIP, std::string(fn) + ": map upload: " + hipGetErrorString(e));
-    cb->per_class = per_class;
-    cb->nx = nx;
-    cb->nu = nu;
-    for (int k = 0; k < cb->K && !rc; ++k) {
-        if (!cb->child[k]) continue;
-        const void* a[6];
-        class_maps(cb, k, a);
-        rc = gpad_setup_plant(cb->child[k], nx, nu, a[0], a[1], a[2], a[3], a[4], a[5]);  // (synchronises)
-    }
-    if (!rc && cb->fused) rc = fused_bind_plant(cb);
-    if (rc) return rc;
-    cb->plant = true;
-    cb->plant_dyn = A != nullptr;
-    return GPAD_OK;
-}
-
-// What the fused loop reads with signals, packed once (f32): per copy [PM SM], [Pg Sg], [A E] over the augmented
-// state, and M0, g0, B replicated where the plant holds one copy under per-class signals -- the kernel indexes
-// all six arrays by the one class id.  SM, Sg, E: device, K copies (per_class) or one; null: zeros.
-static int pack_images(ClassBinding* cb, int ns, bool per_class, const float* SM, const float* Sg, const float* E) {
-    const gpad_dims_t& d = cb->dims;
-    const int nx = cb->nx, nu = cb->nu;
-    const size_t w = (size_t)nx + ns;
-    cb->img_per_class = per_class || cb->per_class;
-    cb->img_rep = per_class && !cb->per_class;
-    const size_t copies = cb->img_per_class ? (size_t)cb->K : 1;
-    const size_t rows[3] = {(size_t)d.n, (size_t)d.m, cb->plant_dyn ? (size_t)nx : 0};
-    const size_t rep[3] = {(size_t)d.n, (size_t)d.m, (size_t)nx * nu};  // M0, g0, B
-    const int rep_map[3] = {1, 3, 5};
-    size_t off = 0;
-    for (int i = 0; i < 3; ++i) {
-        cb->img_off[i] = off;
-        off += copies * rows[i] * w;
-    }
-    for (int i = 0; i < 3; ++i) {
-        cb->img_off[3 + i] = off;
-        if (cb->img_rep && cb->map_has[rep_map[i]]) off += copies * rep[i];
-    }
-    if (int rc = cb->simg.ensure(sizeof(float) * off)) return rc;
-    float* I = (float*)cb->simg.p;
-    const float* S[3] = {SM, Sg, E};
-    const int plant_map[3] = {0, 2, 4};
-    for (size_t k = 0; k < copies; ++k) {
-        const void* a[6];
-        class_maps(cb, (int)k, a);  // (a plant with one copy: that copy for every k)
-        for (int i = 0; i < 3; ++i) {
-            if (!rows[i]) continue;
-            const float* Sk = S[i] ? S[i] + (per_class ? k * rows[i] * ns : 0) : nullptr;
-            HIP_TRY(launch_pack_aug<float>((const float*)a[plant_map[i]], Sk, I + cb->img_off[i] + k * rows[i] * w,
-                                           (long long)rows[i], nx, ns, cb->stream));
-            if (cb->img_rep && cb->map_has[rep_map[i]] && rep[i])
-                HIP_TRY(hipMemcpyAsync(I + cb->img_off[3 + i] + k * rep[i], a[rep_map[i]], sizeof(float) * rep[i],
-                                       hipMemcpyDeviceToDevice, cb->stream));
-        }
-    }
-    HIP_TRY(hipStreamSynchronize(cb->stream));
-    return GPAD_OK;
+    const int rc = cb->plant.bind_plant(per_class ? "gpad_setup_plant_classes" : "gpad_setup_plant", cb->dims,
+                                        per_class ? cb->K : 0, nx, nu, PM, M0, Pg, g0, A, B, cb->stream);
+    lend_plant(cb);
+    return rc;
 }
 
 bool classes_has_plant(const ClassBinding* cb, bool* dyn) {
-    if (dyn) *dyn = cb->plant && cb->plant_dyn;
-    return cb->plant;
-}
-
-static void unbind_signals(ClassBinding* cb) {
-    cb->ns = 0;
-    for (gpad_handle_t c : cb->child)
-        if (c) c->ns = 0;
-    if (cb->fused) cb->fused->ns = 0;
+    if (dyn) *dyn = cb->plant.bound() && cb->plant.dyn;
+    return cb->plant.bound();
 }
 
 int classes_setup_signals(ClassBinding* cb, int ns, bool per_class, const void* SM, const void* Sg, const void* E) {
-    const gpad_dims_t& d = cb->dims;
-    unbind_signals(cb);  // (a failed rebinding leaves none)
-    if (ns == 0) return GPAD_OK;
-    const size_t es = esize(d.dtype), copies = per_class ? (size_t)cb->K : 1;
-    const void* src[3] = {SM, Sg, E};
-    const size_t elems[3] = {(size_t)d.n * ns, (size_t)d.m * ns, (size_t)cb->nx * ns};
-    // the maps on the device: the children are GPAD_MEM_DEVICE handles
-    const char* dev[3] = {(const char*)SM, (const char*)Sg, (const char*)E};
-    DevBuf up;
-    int rc = GPAD_OK;
-    if (d.memory == GPAD_MEM_HOST) {
-        size_t total = 0;
-        for (int i = 0; i < 3; ++i) total += src[i] ? elems[i] * copies : 0;
-        rc = up.ensure(es * total);
-        hipError_t e = hipSuccess;
-        size_t off = 0;
-        for (int i = 0; i < 3 && !rc && e == hipSuccess; ++i) {
-            if (!src[i]) continue;
-            dev[i] = (const char*)up.p + es * off;
-            e = hipMemcpyAsync((char*)up.p + es * off, src[i], es * elems[i] * copies, hipMemcpyHostToDevice, cb->stream);
-            off += elems[i] * copies;
-        }
-        if (!rc && e == hipSuccess) e = hipStreamSynchronize(cb->stream);
-        if (!rc && e != hipSuccess)
-            rc = fail(GPAD_ERR_HIP, std::string("gpad_setup_class_signals: map upload: ") + hipGetErrorString(e));
-    }
-    for (int k = 0; k < cb->K && !rc; ++k) {
-        if (!cb->child[k]) continue;
-        const void* a[3];
-        for (int i = 0; i < 3; ++i) a[i] = dev[i] ? dev[i] + (per_class ? es * elems[i] * k : 0) : nullptr;
-        rc = gpad_setup_signals(cb->child[k], ns, a[0], a[1], a[2]);  // (synchronises)
-    }
-    if (!rc && d.dtype == GPAD_DTYPE_F32)
-        rc = pack_images(cb, ns, per_class, (const float*)dev[0], (const float*)dev[1], (const float*)dev[2]);
-    if (!rc) {
-        cb->ns = ns;
-        if (cb->fused) rc = fused_bind_signals(cb);
-    }
-    up.release();
-    if (rc) unbind_signals(cb);
+    const int rc = cb->plant.bind_signals(cb->dims.memory, ns, per_class ? cb->K : 0, SM, Sg, E, cb->stream);
+    lend_plant(cb);
     return rc;
 }
 
@@ -691,35 +532,13 @@ static int fused_loop(ClassBinding* cb, float* sx, float* sz, float* sy, const f
                                hipMemcpyHostToDevice, cb->stream));
         cb->start_grid = grid;
     }
-    const void* maps[6];
-    class_maps(cb, 0, maps);  // (class 0's copy is where each array starts)
-    ClassLoop cl{};
+    ClassLoop cl{};  // (the maps and images: the handle reads the binding's store, lend_plant)
     cl.K = K;
     cl.grid = grid;
     cl.off = tab;
     cl.qctr = tab + K + 1;
     cl.start = tab + 2 * (size_t)K + 1;
     cl.frag = cb->frags.p;
-    cl.per_class = cb->per_class ? 1 : 0;
-    cl.PM = (const float*)maps[0];
-    cl.M0 = (const float*)maps[1];
-    cl.Pg = (const float*)maps[2];
-    cl.g0 = (const float*)maps[3];
-    cl.A = (const float*)maps[4];
-    cl.B = (const float*)maps[5];
-    if (sS) {  // the packed images over [x; s], and M0, g0, B with as many copies as they have
-        const float* I = (const float*)cb->simg.p;
-        cl.ns = cb->ns;
-        cl.per_class = cb->img_per_class ? 1 : 0;
-        cl.PM = I + cb->img_off[0];
-        cl.Pg = I + cb->img_off[1];
-        cl.A = I + cb->img_off[2];
-        if (cb->img_rep) {
-            if (cl.M0) cl.M0 = I + cb->img_off[3];
-            if (cl.g0) cl.g0 = I + cb->img_off[4];
-            if (cl.B) cl.B = I + cb->img_off[5];
-        }
-    }
     f->cloop = &cl;
     const int rc = sS ? gpad_closed_loop_signals(f, sx, sz, sy, sS, steps, N, tol, warm, sxs, sus, nullptr)
                       : gpad_closed_loop(f, sx, sz, sy, steps, N, tol, warm, sxs, sus, nullptr);
@@ -731,7 +550,7 @@ template <typename T>
 static int state_typed(ClassBinding* cb, T* x, T* z, T* y, const T* sg, int steps, int N, double tol, int warm, T* xs,
                        T* us, gpad_stats_t* st) {
     const gpad_dims_t& d = cb->dims;
-    const int nx = cb->nx, nu = cb->nu, ns = sg ? cb->ns : 0;
+    const int nx = cb->plant.nx, nu = cb->plant.nu, ns = sg ? cb->plant.ns : 0;
     const bool loop = steps > 0, host = d.memory == GPAD_MEM_HOST;
     // gpad_class_loop_fused: a loop of a shape the panel loop takes runs as one launch over every class; any
     // other call runs class by class as if it were off (as the loop options do)
@@ -854,11 +673,11 @@ static int state_typed(ClassBinding* cb, T* x, T* z, T* y, const T* sg, int step
 int classes_state(ClassBinding* cb, void* x, void* z, void* y, const void* sg, bool with_sig, const char* fn,
                   int steps, int N, double tol, int warm, void* xs, void* us, gpad_stats_t* st) {
     const std::string where(fn);
-    if (with_sig && cb->ns == 0) return no_classes(fn);  // (class signals: gpad_setup_class_signals)
-    if (!with_sig && cb->ns != 0)  // (dropping a disturbance silently is worse than an error)
+    if (with_sig && cb->plant.ns == 0) return no_classes(fn);  // (class signals: gpad_setup_class_signals)
+    if (!with_sig && cb->plant.ns != 0)  // (dropping a disturbance silently is worse than an error)
         return fail(GPAD_ERR_INVALID, where + ": class signals are bound, call the _signals entry point");
-    if (!cb->plant) return fail(GPAD_ERR_NOT_SETUP, where + ": call gpad_setup_plant after gpad_setup_classes");
-    if (steps > 0 && !cb->plant_dyn) return fail(GPAD_ERR_NOT_SETUP, where + ": plant bound without A, B");
+    if (!cb->plant.bound()) return fail(GPAD_ERR_NOT_SETUP, where + ": call gpad_setup_plant after gpad_setup_classes");
+    if (steps > 0 && !cb->plant.dyn) return fail(GPAD_ERR_NOT_SETUP, where + ": plant bound without A, B");
     if (!x || !z || !y || (with_sig && !sg)) return fail(GPAD_ERR_INVALID, where + ": null vector");
     if (N < 0 || steps < 0) return fail(GPAD_ERR_INVALID, where + ": N, steps must be >= 0");
     if (!(tol <= 0.0) && !std::isfinite(tol)) return fail(GPAD_ERR_INVALID, where + ": bad tol");

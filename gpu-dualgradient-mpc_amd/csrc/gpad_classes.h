@@ -54,18 +54,14 @@ hipError_t launch_class_sig_gather(const T* src, T* dst, int ns, const int* perm
 // What one launch of the class-aware panel loop (gpad_loop_panel.hip) needs beyond a plain closed loop of
 // the whole batch in the sorted order.  gpad_classes.cpp attaches it to the binding's whole-batch handle
 // (gpad_handle_s::cloop) for the length of one gpad_closed_loop call; gpad_state.cpp reads it.  All
-// pointers are device memory.
+// pointers are device memory.  The class tables only: the maps and signal images come from the binding's
+// plant store, which that handle runs with (gpad_plant_store.h), a copy per class or one for all.
 struct ClassLoop {
     int K, grid;
     const int* off;    // [K + 1] offsets of the sorted order
     const int* start;  // [grid] the class each workgroup starts on (class_loop_deal)
     int* qctr;         // [K] claim counters
     const void* frag;  // K fragment images, class k's at k * 2 * T * T * 1024 bytes
-    int per_class;     // 1: K copies of every map, 0: one
-    int ns;            // class signals in the call (gpad_closed_loop_signals); 0: none
-    // ns == 0: the plant's maps; ns > 0: PM, Pg, A are the packed images [PM SM], [Pg Sg], [A E], rows of
-    // nx + ns columns, and all six arrays hold K copies when the plant or the signals are per class
-    const float *PM, *M0, *Pg, *g0, *A, *B;  // (M0, g0: null when not bound)
 };
 // Host only (gpad_class_loop_deal): the class each of `grid` workgroups starts on, in proportion to the
 // classes' panel counts; false on a negative count or when every class is empty
@@ -76,7 +72,8 @@ bool class_loop_deal(const int* counts, int K, int grid, int* start_class);
 bool class_order(const int* class_of, int batch, int K, int* perm, int* offsets);
 
 // The binding owns one child handle per non-empty class (same device, same stream, shared = 1,
-// GPAD_MEM_DEVICE), perm / offsets on host and device, and the workspaces.  Every function returns a
+// GPAD_MEM_DEVICE), perm / offsets on host and device, the workspaces, and the one plant store
+// (gpad_plant_store.h) whose maps and signal images every one of its handles reads.  Every function returns a
 // GPAD_* status with gpad_last_error set.
 int classes_setup(ClassBinding** out, int device, hipStream_t stream, const Tuning& tune, const gpad_dims_t* dims,
                   int K, const int* class_of, const void* ML, const void* G, double L);

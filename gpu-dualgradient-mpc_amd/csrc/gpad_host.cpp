@@ -221,8 +221,7 @@ int gpad_destroy(gpad_handle_t h) {
         h->counters.release();
         h->pwork.release();
         h->status.release();
-        h->plant.release();
-        h->sig.release();
+        h->own_plant.release();
         h->state.release();
         if (h->ev0) (void)hipEventDestroy(h->ev0);
         if (h->ev1) (void)hipEventDestroy(h->ev1);

@@ -1,5 +1,5 @@
 // gpad_host.h -- what the host translation units share (gpad_host.cpp, gpad_setup.cpp, gpad_run.cpp,
-// gpad_state.cpp, gpad_classes.cpp, gpad_group.cpp): the error plumbing, the device buffer, the handle,
+// gpad_state.cpp, gpad_plant_store.cpp, gpad_classes.cpp, gpad_group.cpp): the error plumbing, the device buffer, the handle,
 // the option table and the few functions that cross files.  Host only: never included by a .hip file.
 #pragma once
 
@@ -58,6 +58,8 @@ struct DevBuf {
         bytes = 0;
     }
 };
+
+#include "gpad_plant_store.h"  // (uses DevBuf)
 
 // gpad_set_option: one line per option -- its id, its Tuning member and the accepted range.  inverted:
 // the member stores 1 - value.  GPAD_OPT_DEFAULT restores the member's Tuning{} value.  Walked by
@@ -172,18 +174,15 @@ struct gpad_handle_s {
     bool plan_pending = false;
     int plan_pending_N = 0, plan_pending_batch = 0;
     bool plan_pending_p64 = false;      // ... the pending counts are an f64 panel solve's (build_p64_order)
-    // plant binding (gpad_setup_plant): affine state maps and dynamics, device copies
-    int nx = 0, nu = 0;
-    bool plant_ready = false, plant_dyn = false;
-    DevBuf plant;                       // [PM n*nx | M0 n | Pg m*nx | g0 m | A nx*nx | B nx*nu], each
-                                        // array plant_batch times over when per instance
-    int plant_batch = 0;                // 0: one plant for the batch; else the dims.batch it was bound for
-    bool has_M0 = false, has_g0 = false;
-    int plant_n = 0, plant_m = 0, plant_dtype = -1;
-    // exogenous signals (gpad_setup_signals): the plant's maps packed over the augmented state [x; s]
-    int ns = 0;                         // 0: none bound
-    DevBuf sig;                         // [PM SM] n*(nx+ns) | [Pg Sg] m*(nx+ns) | [A E] nx*(nx+ns), each
-                                        // array plant_batch times over when per instance
+    // plant maps and exogenous signals (gpad_plant_store.h): what gpad_setup_plant[_batch] and gpad_setup_signals
+    // bind on this handle -- one copy, or dims.batch -- and the store its runs read: its own, unless a class
+    // binding lent it its store (attach_plant below)
+    gpad::PlantStore own_plant;
+    const gpad::PlantStore* plant = &own_plant;
+    int plant_first = 0;                // a run reads copy plant_first of the store ...
+    bool plant_all = true;              // ... or every copy: one per instance, or with the class tables attached
+                                        // (cloop) one per class.  Without them a handle that sees several copies
+                                        // but not dims.batch of them does not run.
     DevBuf state;                       // per-state workspaces (M(x), g(x), x ping-pong, ...)
     int num_cus = 256;
     bool timed = false;
@@ -214,6 +213,9 @@ void unbind_problem(gpad_handle_t h);
 int ensure_schedule(gpad_handle_t h, int N, const void* theta_in, const void* beta_in);
 
 // ---- gpad_state.cpp ---------------------------------------------------------------------------------
+// Internal (not exported): h's runs read `store` from now on -- copy `first` of it, or (all) every copy.  The store
+// must outlive the handle's runs; a class binding lends its own to its children and its whole-batch handle.
+void attach_plant(gpad_handle_t h, const gpad::PlantStore* store, int first, bool all);
 // the shape rules of GPAD_OPT_LOOP_PANEL for a closed loop of h's problem and plant (the option itself aside):
 // what the fused class loop asks of its whole-batch handle
 bool loop_panel_shape(gpad_handle_t h, int N, double tol, int nxa);

@@ -28,7 +28,7 @@ void unbind_problem(gpad_handle_t h) {
     end_classes(h);
     h->ready = false;
     h->flat = false;
-    h->ns = 0;
+    h->own_plant.ns = 0;
     h->shadow_ok = false;
     h->hess_ok = false;
     h->frag64_ok = false;

@@ -6,38 +6,13 @@
 
 #include "gpad_host.h"
 
-namespace {
-struct PlantOffsets {
-    size_t PM, M0, Pg, g0, A, B, total;
-};
-// element offsets of the maps in Handle::plant, each array holding `copies` consecutive instances
-PlantOffsets plant_offsets(int n, int m, int nx, int nu, size_t copies) {
-    PlantOffsets o{};
-    o.PM = 0;
-    o.M0 = o.PM + copies * n * nx;
-    o.Pg = o.M0 + copies * n;
-    o.g0 = o.Pg + copies * m * nx;
-    o.A = o.g0 + copies * m;
-    o.B = o.A + copies * nx * nx;
-    o.total = o.B + copies * nx * nu;
-    return o;
+void attach_plant(gpad_handle_t h, const gpad::PlantStore* store, int first, bool all) {
+    h->plant = store;
+    h->plant_first = first;
+    h->plant_all = all;
 }
-struct SigOffsets {
-    size_t PM, Pg, A, total;
-};
-// element offsets of the packed images in Handle::sig (rows of nx + ns columns)
-SigOffsets sig_offsets(int n, int m, int nx, int ns, size_t copies) {
-    SigOffsets o{};
-    const size_t w = (size_t)nx + ns;
-    o.PM = 0;
-    o.Pg = o.PM + copies * n * w;
-    o.A = o.Pg + copies * m * w;
-    o.total = o.A + copies * nx * w;
-    return o;
-}
-}  // namespace
 
-// gpad_setup_plant (copies == 0: one plant) and gpad_setup_plant_batch (copies == dims.batch)
+// gpad_setup_plant (one plant) and gpad_setup_plant_batch (dims.batch copies) into the handle's own store
 static int setup_plant_impl(gpad_handle_t h, int nx, int nu, const void* PM, const void* M0, const void* Pg,
                             const void* g0, const void* A, const void* B, bool per_instance, const char* fn) {
     const std::string where(fn);
@@ -48,41 +23,9 @@ static int setup_plant_impl(gpad_handle_t h, int nx, int nu, const void* PM, con
         return gpad::classes_setup_plant(h->cls, false, nx, nu, PM, M0, Pg, g0, A, B);  // the same maps for every class
     }
     if (!h->ready) return fail(GPAD_ERR_NOT_SETUP, where + ": call gpad_setup first");
-    if (nx <= 0 || nu < 0 || !PM || !Pg) return fail(GPAD_ERR_INVALID, where + ": bad arguments");
-    if ((A == nullptr) != (B == nullptr) || (A && nu == 0))
-        return fail(GPAD_ERR_INVALID, where + ": give A and B together (nu >= 1)");
-    if (nu > h->dims.n) return fail(GPAD_ERR_INVALID, where + ": nu > n");
     HIP_TRY(hipSetDevice(h->device));
-    const int n = h->dims.n, m = h->dims.m;
-    const size_t es = esize(h->dims.dtype), copies = per_instance ? (size_t)h->dims.batch : 1;
-    const PlantOffsets o = plant_offsets(n, m, nx, nu, copies);
-    int rc;
-    if ((rc = h->plant.ensure(es * o.total))) return rc;
-    char* base = (char*)h->plant.p;
-    const hipMemcpyKind kind = h->dims.memory == GPAD_MEM_HOST ? hipMemcpyHostToDevice
-                                                                : hipMemcpyDeviceToDevice;
-    auto put = [&](size_t off, const void* src, size_t elems) -> int {
-        if (!src || elems == 0) return GPAD_OK;
-        HIP_TRY(hipMemcpyAsync(base + es * off, src, es * copies * elems, kind, h->stream));
-        return GPAD_OK;
-    };
-    if ((rc = put(o.PM, PM, (size_t)n * nx)) || (rc = put(o.M0, M0, n)) ||
-        (rc = put(o.Pg, Pg, (size_t)m * nx)) || (rc = put(o.g0, g0, m)) ||
-        (rc = put(o.A, A, (size_t)nx * nx)) || (rc = put(o.B, B, (size_t)nx * nu)))
-        return rc;
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    h->ns = 0;  // (a new plant unbinds the signals)
-    h->nx = nx;
-    h->nu = nu;
-    h->has_M0 = M0 != nullptr;
-    h->has_g0 = g0 != nullptr;
-    h->plant_dyn = A != nullptr;
-    h->plant_ready = true;
-    h->plant_batch = per_instance ? h->dims.batch : 0;
-    h->plant_n = n;
-    h->plant_m = m;
-    h->plant_dtype = h->dims.dtype;
-    return GPAD_OK;
+    return h->own_plant.bind_plant(fn, h->dims, per_instance ? h->dims.batch : 0, nx, nu, PM, M0, Pg, g0, A, B,
+                                   h->stream);
 }
 
 extern "C" int gpad_setup_plant(gpad_handle_t h, int nx, int nu, const void* PM, const void* M0,
@@ -120,7 +63,7 @@ extern "C" int gpad_setup_classes(gpad_handle_t h, const gpad_dims_t* dims, int 
         if (rc) return rc;  // (the handle keeps what it had)
         // the handle's own problem, plant and last run go too: the binding serves every run from here on
         unbind_problem(h);
-        h->plant_ready = false;
+        h->own_plant.unbind();
         h->last_batch = 0;
         h->cls = cb;
         return GPAD_OK;
@@ -157,43 +100,10 @@ extern "C" int gpad_class_loop_deal(const int* counts, int K, int grid, int* sta
     });
 }
 
+// the store the handle runs with holds a plant of its problem (its own: bound for this batch)
 static bool plant_bound(gpad_handle_t h) {
-    return h->plant_ready && h->plant_n == h->dims.n && h->plant_m == h->dims.m && h->plant_dtype == h->dims.dtype &&
-           !(h->plant_batch && h->plant_batch != h->dims.batch);
-}
-
-// gpad_setup_signals: [PM SM], [Pg Sg], [A E] packed once over the augmented state (zeros for a NULL map)
-template <typename T>
-static int setup_signals_typed(gpad_handle_t h, int ns, const T* SM, const T* Sg, const T* E) {
-    const int n = h->dims.n, m = h->dims.m, nx = h->nx, nu = h->nu;
-    const size_t copies = h->plant_batch ? (size_t)h->plant_batch : 1;
-    const PlantOffsets o = plant_offsets(n, m, nx, nu, copies);
-    const SigOffsets so = sig_offsets(n, m, nx, ns, copies);
-    int rc;
-    if ((rc = h->sig.ensure(sizeof(T) * so.total))) return rc;
-    const T *dSM = SM, *dSg = Sg, *dE = E;
-    if (h->dims.memory == GPAD_MEM_HOST) {  // staged through the per-run workspace
-        const size_t eSM = copies * n * ns, eSg = copies * m * ns, eE = copies * nx * ns;
-        if ((rc = h->state.ensure(sizeof(T) * (eSM + eSg + eE)))) return rc;
-        T* b = (T*)h->state.p;
-        auto up = [&](const T* src, T* dst, size_t elems) -> int {
-            if (src) HIP_TRY(hipMemcpyAsync(dst, src, sizeof(T) * elems, hipMemcpyHostToDevice, h->stream));
-            return GPAD_OK;
-        };
-        if ((rc = up(SM, b, eSM)) || (rc = up(Sg, b + eSM, eSg)) || (rc = up(E, b + eSM + eSg, eE))) return rc;
-        dSM = SM ? b : nullptr;
-        dSg = Sg ? b + eSM : nullptr;
-        dE = E ? b + eSM + eSg : nullptr;
-    }
-    const T* P = (const T*)h->plant.p;
-    T* I = (T*)h->sig.p;
-    HIP_TRY(gpad::launch_pack_aug<T>(P + o.PM, dSM, I + so.PM, (long long)copies * n, nx, ns, h->stream));
-    HIP_TRY(gpad::launch_pack_aug<T>(P + o.Pg, dSg, I + so.Pg, (long long)copies * m, nx, ns, h->stream));
-    if (h->plant_dyn)
-        HIP_TRY(gpad::launch_pack_aug<T>(P + o.A, dE, I + so.A, (long long)copies * nx, nx, ns, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    h->ns = ns;
-    return GPAD_OK;
+    const gpad::PlantStore& ps = *h->plant;
+    return ps.bound_for(h->dims) && (h->plant != &h->own_plant || !ps.stacked || ps.copies == h->dims.batch);
 }
 
 extern "C" int gpad_setup_signals(gpad_handle_t h, int ns, const void* SM, const void* Sg, const void* E) {
@@ -205,16 +115,11 @@ extern "C" int gpad_setup_signals(gpad_handle_t h, int ns, const void* SM, const
         if (!h->ready || !plant_bound(h))
             return fail(GPAD_ERR_NOT_SETUP, "gpad_setup_signals: call gpad_setup_plant first");
         if (ns < 0) return fail(GPAD_ERR_INVALID, "gpad_setup_signals: ns < 0");
-        if (ns == 0) {
-            h->ns = 0;
-            return GPAD_OK;
-        }
-        if (E && !h->plant_dyn) return fail(GPAD_ERR_INVALID, "gpad_setup_signals: E given, plant bound without A, B");
+        gpad::PlantStore& ps = h->own_plant;
+        if (ns > 0 && E && !ps.dyn)
+            return fail(GPAD_ERR_INVALID, "gpad_setup_signals: E given, plant bound without A, B");
         HIP_TRY(hipSetDevice(h->device));
-        h->ns = 0;  // (a failed rebinding leaves none)
-        if (h->dims.dtype == GPAD_DTYPE_F64)
-            return setup_signals_typed<double>(h, ns, (const double*)SM, (const double*)Sg, (const double*)E);
-        return setup_signals_typed<float>(h, ns, (const float*)SM, (const float*)Sg, (const float*)E);
+        return ps.bind_signals(h->dims.memory, ns, ps.stacked ? ps.copies : 0, SM, Sg, E, h->stream);
     });
 }
 
@@ -239,19 +144,18 @@ extern "C" int gpad_setup_class_signals(gpad_handle_t h, int ns, int per_class, 
 
 // The device arrays of one gpad_run_state / gpad_closed_loop call.  Handle::state holds
 //   M(x) | g(x) | x ping | x pong | (signals) x in / out | (host callers) z | y | xs | us | S
-// and the maps are the plant's, or with signals their packed images [PM SM], [Pg Sg], [A E].
+// and the maps are the view `v` of the store the handle runs with: the plant's, or with signals their packed
+// images [PM SM], [Pg Sg], [A E] (v.nxa: columns of an x ping-pong row, nx + ns).
 template <typename T>
 struct StateWork {
-    int ns, nxa;                       // signal columns in use; columns of an x ping-pong row, nx + ns
+    int ns;                            // signal columns in use
     size_t zn, yn, xn, xan, xsn, usn, sn;  // element counts (xan: one x ping-pong array)
     T *Mx, *gx, *xa, *xb;
     T* xd;                             // signals: the dense [batch][nx] states in, then out; else null
     T *dz, *dy, *dxs, *dus;            // the caller's arrays, or (host callers) their staged copies
     T* S_up;                           // host callers with signals: where S is staged; else null
     const T* dS;                       // [nsolve][batch][ns]
-    const T *mPM, *mPg, *mA;           // the maps over the x ping-pong rows
-    const T *M0, *g0, *B;              // (M0, g0: null when not bound)
-    bool per_plant;                    // per-instance maps (gpad_setup_plant_batch)
+    gpad::PlantView<T> v;
 };
 
 // sizes Handle::state for the call and places the arrays in it (nothing is enqueued)
@@ -260,14 +164,17 @@ static int state_work(gpad_handle_t h, T* z, T* y, const T* sg, int steps, T* xs
     const gpad_dims_t& d = h->dims;
     const size_t batch = (size_t)d.batch;
     const bool loop = steps > 0, host = d.memory == GPAD_MEM_HOST;
-    const int ns = w->ns = sg ? h->ns : 0;
-    w->nxa = h->nx + ns;
+    const gpad::PlantStore& ps = *h->plant;
+    const int ns = w->ns = sg ? ps.ns : 0;
+    w->v = ps.view<T>(h->plant_first, h->plant_all, ns > 0);  // (taken per call: a rebinding may move the buffers)
+    if (w->v.per_copy && w->v.copies != d.batch && !h->cloop)
+        return fail(GPAD_ERR_INVALID, "a handle that sees a copy of the maps per class runs only the fused class loop");
     w->zn = batch * d.n;
     w->yn = batch * d.m;
-    w->xn = batch * h->nx;
-    w->xan = batch * w->nxa;
+    w->xn = batch * ps.nx;
+    w->xan = batch * w->v.nxa;
     w->xsn = loop && xs ? (size_t)steps * w->xn : 0;
-    w->usn = loop && us ? (size_t)steps * batch * h->nu : 0;
+    w->usn = loop && us ? (size_t)steps * batch * ps.nu : 0;
     w->sn = (size_t)(loop ? steps : 1) * batch * ns;
     size_t elems = w->zn + w->yn + 2 * w->xan + (ns ? w->xn : 0);
     if (host) elems += w->zn + w->yn + w->xsn + w->usn + w->sn;
@@ -289,29 +196,6 @@ static int state_work(gpad_handle_t h, T* z, T* y, const T* sg, int steps, T* xs
         w->dus = w->usn ? w->dy + w->yn + w->xsn : nullptr;
         if (ns) w->dS = w->S_up = w->dy + w->yn + w->xsn + w->usn;
     }
-    w->per_plant = h->plant_batch != 0;
-    const size_t copies = w->per_plant ? batch : 1;
-    const PlantOffsets o = plant_offsets(d.n, d.m, h->nx, h->nu, copies);
-    const SigOffsets so = sig_offsets(d.n, d.m, h->nx, ns, copies);
-    const T* P = (const T*)h->plant.p;
-    const T* I = (const T*)h->sig.p;
-    w->mPM = ns ? I + so.PM : P + o.PM;
-    w->mPg = ns ? I + so.Pg : P + o.Pg;
-    w->mA = ns ? I + so.A : P + o.A;
-    w->M0 = h->has_M0 ? P + o.M0 : nullptr;
-    w->g0 = h->has_g0 ? P + o.g0 : nullptr;
-    w->B = P + o.B;
-    if constexpr (sizeof(T) == sizeof(float)) {
-        if (const gpad::ClassLoop* cl = h->cloop) {  // the fused class loop: the binding's maps, a copy per class
-            w->per_plant = cl->per_class != 0;
-            w->mPM = cl->PM;
-            w->mPg = cl->Pg;
-            w->mA = cl->A;
-            w->M0 = cl->M0;
-            w->g0 = cl->g0;
-            w->B = cl->B;
-        }
-    }
     return GPAD_OK;
 }
 
@@ -321,7 +205,7 @@ bool loop_panel_shape(gpad_handle_t h, int N, double tol, int nxa) {
     const gpad_dims_t& d = h->dims;
     return d.shared && h->frag_ok && h->frag_tiles >= 1 && h->frag_tiles <= 16 && !h->flat && !h->hess_ok && N >= 1 &&
            (d.kernel == GPAD_KERNEL_AUTO || d.kernel == GPAD_KERNEL_PANEL) &&
-           (!(tol > 0.0) || N % d.check_every == 0) && gpad::loop_panel_supported(d.n, d.m, nxa, h->nu);
+           (!(tol > 0.0) || N % d.check_every == 0) && gpad::loop_panel_supported(d.n, d.m, nxa, h->plant->nu);
 }
 
 // Which one-launch engine serves a closed loop of an f32 handle: GPAD_KERNEL_LOOP_PANEL, GPAD_KERNEL_LOOP, or
@@ -335,7 +219,7 @@ bool loop_panel_shape(gpad_handle_t h, int N, double tol, int nxa) {
 static int one_launch_engine(gpad_handle_t h, bool loop, int N, double tol, int nxa) {
     if (h->cloop) return GPAD_KERNEL_LOOP_CLASSES;
     const gpad_dims_t& d = h->dims;
-    const int n = d.n, m = d.m, nu = h->nu;
+    const int n = d.n, m = d.m, nu = h->plant->nu;
     const bool lpanel = loop && h->tune.loop_panel && loop_panel_shape(h, N, tol, nxa);
     const bool async = lpanel || (loop && h->tune.loop_async && !h->flat && !h->hess_ok && N >= 1 &&
                                   (d.kernel == GPAD_KERNEL_AUTO || d.kernel == GPAD_KERNEL_RESIDENT) &&
@@ -360,12 +244,12 @@ static int run_loop_one_launch(gpad_handle_t h, const StateWork<float>& w, int e
     a.iters = (int*)h->counters.p;
     a.conv = a.iters;  // (the kernel indexes both from the counters' base, [steps][iters | conv])
     a.qctr = static_cast<int*>(h->q64.p);
-    la.PM = w.mPM;
-    la.M0 = w.M0;
-    la.Pg = w.mPg;
-    la.g0 = w.g0;
-    la.A = w.mA;
-    la.B = w.B;
+    la.PM = w.v.PM;
+    la.M0 = w.v.M0;
+    la.Pg = w.v.Pg;
+    la.g0 = w.v.g0;
+    la.A = w.v.A;
+    la.B = w.v.B;
     la.x_in = ns ? w.xd : w.xa;  // (dense rows of nx either way; the kernel reads S itself)
     la.x_out = ns ? w.xa : w.xb;
     la.ns = ns;
@@ -375,11 +259,11 @@ static int run_loop_one_launch(gpad_handle_t h, const StateWork<float>& w, int e
     la.gmax = tol > 0.0 ? reinterpret_cast<double*>((char*)h->status.p + (nsolve > 1 ? offsetof(RunStatus, acc)
                                                                                      : offsetof(RunStatus, part)))
                         : nullptr;
-    la.nx = h->nx;
-    la.nu = h->nu;
+    la.nx = h->plant->nx;
+    la.nu = h->plant->nu;
     la.steps = nsolve;
     la.warm = warm ? 1 : 0;
-    la.per_plant = w.per_plant ? 1 : 0;
+    la.per_plant = w.v.per_copy ? 1 : 0;
     int grid;
     if (cl) {  // every class in one launch: its images, counters and tables (the maps are in w already)
         a.frag = cl->frag;
@@ -411,13 +295,13 @@ static int run_loop_one_launch(gpad_handle_t h, const StateWork<float>& w, int e
 // x <- A x + E S[t] + B u, with S[t + 1] moved in beside it and the last step's dense states written to xd
 template <typename T>
 static hipError_t plant_step(gpad_handle_t h, const StateWork<T>& w, int t, int nsolve, const T* xc, T* xnext) {
-    const int n = h->dims.n, batch = h->dims.batch, nx = h->nx, nu = h->nu, ns = w.ns;
+    const int n = h->dims.n, batch = h->dims.batch, nx = h->plant->nx, nu = h->plant->nu, ns = w.ns;
     T* xs_t = w.dxs ? w.dxs + (size_t)t * w.xn : nullptr;
     T* us_t = w.dus ? w.dus + (size_t)t * batch * nu : nullptr;
-    if (!ns) return gpad::launch_plant_step<T>(w.mA, w.B, xc, w.dz, n, xnext, nx, nu, batch, xs_t, us_t, w.per_plant, h->stream);
+    if (!ns) return gpad::launch_plant_step<T>(w.v.A, w.v.B, xc, w.dz, n, xnext, nx, nu, batch, xs_t, us_t, w.v.per_copy, h->stream);
     const bool last = t + 1 == nsolve;
-    return gpad::launch_plant_step_sig<T>(w.mA, w.B, xc, w.dz, n, xnext, last ? nullptr : w.dS + (size_t)(t + 1) * batch * ns,
-                                          nx, ns, nu, batch, xs_t, us_t, last ? w.xd : nullptr, w.per_plant, h->stream);
+    return gpad::launch_plant_step_sig<T>(w.v.A, w.v.B, xc, w.dz, n, xnext, last ? nullptr : w.dS + (size_t)(t + 1) * batch * ns,
+                                          nx, ns, nu, batch, xs_t, us_t, last ? w.xd : nullptr, w.v.per_copy, h->stream);
 }
 
 // Step by step: the two affine maps, the solve, the fold of its max |g| and the plant step, nsolve times
@@ -431,9 +315,9 @@ static int run_loop_lockstep(gpad_handle_t h, const StateWork<T>& w, bool loop, 
     int* counters = (int*)h->counters.p;
     T* xc = w.xa;
     T* xnext = w.xb;
-    if (ns) HIP_TRY(gpad::launch_sig_state<T>(w.xd, w.dS, w.xa, h->nx, ns, batch, h->stream));  // [x_0; S[0]]
+    if (ns) HIP_TRY(gpad::launch_sig_state<T>(w.xd, w.dS, w.xa, h->plant->nx, ns, batch, h->stream));  // [x_0; S[0]]
     for (int t = 0; t < nsolve; ++t) {
-        HIP_TRY(gpad::launch_affine2<T>(w.mPM, w.M0, n, w.Mx, w.mPg, w.g0, m, w.gx, xc, w.nxa, batch, w.per_plant,
+        HIP_TRY(gpad::launch_affine2<T>(w.v.PM, w.v.M0, n, w.Mx, w.v.Pg, w.v.g0, m, w.gx, xc, w.v.nxa, batch, w.v.per_copy,
                                         h->stream));
         if (loop && !warm) {  // acceldualgrad.m:16-17: every MPC step starts from z = y = 0
             HIP_TRY(hipMemsetAsync(w.dz, 0, sizeof(T) * w.zn, h->stream));
@@ -480,7 +364,7 @@ static int state_typed(gpad_handle_t h, T* x, T* z, T* y, const T* sg, int steps
     }
     const double margin = sizeof(T) == sizeof(float) ? gpad::ViolMargin<float>::value : gpad::ViolMargin<double>::value;
     if ((rc = reset_status(h, tol, margin))) return rc;  // g(x) unscaled: margin * L * (1/L)
-    const int engine = sizeof(T) == sizeof(float) ? one_launch_engine(h, loop, N, tol, w.nxa) : 0;
+    const int engine = sizeof(T) == sizeof(float) ? one_launch_engine(h, loop, N, tol, w.v.nxa) : 0;
     if (engine == GPAD_KERNEL_LOOP_CLASSES) {  // one claim counter per class
         HIP_TRY(hipMemsetAsync(h->cloop->qctr, 0, sizeof(int) * (size_t)h->cloop->K, h->stream));
     } else if (engine) {  // the pack queue counter, zeroed ahead of the timed launch
@@ -524,11 +408,11 @@ static int state_impl(gpad_handle_t h, void* x, void* z, void* y, const void* sg
     if (!h->ready) return fail(GPAD_ERR_NOT_SETUP, std::string(where) + ": call gpad_setup first");
     if (!plant_bound(h))
         return fail(GPAD_ERR_NOT_SETUP, std::string(where) + ": call gpad_setup_plant after gpad_setup");
-    if (with_sig && h->ns == 0)
+    if (with_sig && h->plant->ns== 0)
         return fail(GPAD_ERR_NOT_SETUP, std::string(where) + ": call gpad_setup_signals first");
-    if (!with_sig && h->ns != 0)  // (dropping a disturbance silently is worse than an error)
+    if (!with_sig && h->plant->ns!= 0)  // (dropping a disturbance silently is worse than an error)
         return fail(GPAD_ERR_INVALID, std::string(where) + ": signals are bound, call the _signals entry point");
-    if (steps > 0 && !h->plant_dyn)
+    if (steps > 0 && !h->plant->dyn)
         return fail(GPAD_ERR_NOT_SETUP, std::string(where) + ": plant bound without A, B");
     if (!x || !z || !y || (with_sig && !sg)) return fail(GPAD_ERR_INVALID, std::string(where) + ": null vector");
     if (N < 0 || steps < 0) return fail(GPAD_ERR_INVALID, std::string(where) + ": N, steps must be >= 0");

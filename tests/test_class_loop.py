@@ -15,6 +15,8 @@ full panel, one ragged class that needs queue claims) of test_classes.py, and
       class one short of a panel and a single-pack class
 Checked on the oracle at eps 1e-4: P and Q cold have at least 6 distinct counts at every step, at most
 150 iterations.
+  A-M0  A with a constant term M0 per class (class_m0; the battery plants bind none): the per-class M0 offset
+        of the binding and the class index of M0 in the fused loop (test_m0_oracle_guard, test_per_class_m0)
 """
 from __future__ import annotations
 
@@ -29,7 +31,7 @@ import pytest
 
 from conftest import ROOT
 from test_classes import (MODE_IDS, MODES, _bind_plant, _caps, _L, _make, check_against_references, class_plain,
-                          class_run, class_solver, inputs, mode, oracle_ref, reorder)
+                          class_run, class_solver, fleet_ref, inputs, mode, oracle_ref, reorder)
 from test_loop_async import F32, assert_matches_oracle, assert_same_run, loop, same_bits
 
 FUSED = "loop_classes"
@@ -45,6 +47,34 @@ def input_q():
 
 def get_input(name):
     return input_q() if name == "Q" else inputs(name)
+
+
+M0_SCALE = 0.5
+
+
+def class_m0(K, n, scale=M0_SCALE):
+    """A constant term M0 per class -- the battery plants bind none, so the per-class M0 offset, its replication
+    under per-class signals and the fused loop's M0 index go unread without it."""
+    return (scale * np.random.default_rng(31).standard_normal((K, n))).astype(np.float32)
+
+
+def with_m0(I, M0, tag):
+    """Input I of test_classes with the per-class M0 [K][n] (C) and the fleet expanded from it (E)."""
+    J = SimpleNamespace(**vars(I))
+    J.C = SimpleNamespace(**dict(vars(I.C), M0=M0))
+    J.E = SimpleNamespace(**dict(vars(I.E), M0=np.ascontiguousarray(M0[I.class_of])))
+    J.name = I.name + "-" + tag
+    return J
+
+
+A_M0_SCALE = 4.0  # (raised from 0.5 on the oracle: at 0.5, 1 and 2 no solve of A reaches N, test_m0_oracle_guard)
+
+
+def input_am(roll=0):
+    """A with class_m0 at A_M0_SCALE, rolled by `roll` classes (the guard's wrong class index)."""
+    I = inputs("A")
+    M0 = np.roll(class_m0(I.K, I.C.qp.n, A_M0_SCALE), roll, axis=0)
+    return with_m0(I, M0, "M0" + ("-roll%d" % roll if roll else ""))
 
 
 def fused_solver(I, **kw):
@@ -150,7 +180,70 @@ def test_fused_without_a_handle():
     assert b"gpad_class_loop_fused" in lib.gpad_last_error()
 
 
+def assert_m0_guard(I, base, orc, rolled, N, other=None, differ=None, every_step=True):
+    """What an input with a per-class M0 must show on the oracle (shared with test_class_signals): M0 changes
+    the us bits of every pack against the input without it (base), so does M0 rolled by one class; `other`
+    (the one-plant variant) differs in exactly the packs `differ`; every step has at least 5 distinct counts
+    (every_step = False: some step, test_m0_oracle_guard); the run holds capped and early solves; everything is
+    finite."""
+    packs = range(I.class_of.size)
+    changed = lambda a, b: np.array([a.us[:, p].tobytes() != b.us[:, p].tobytes() for p in packs])  # noqa: E731
+    for k in ("x", "z", "y", "xs", "us"):
+        assert np.isfinite(getattr(orc, k)).all(), k
+    assert changed(orc, base).all(), np.flatnonzero(~changed(orc, base))
+    assert changed(orc, rolled).all(), np.flatnonzero(~changed(orc, rolled))
+    if other is not None:
+        assert np.array_equal(changed(orc, other), differ), np.flatnonzero(changed(orc, other))
+    distinct = [len(set(row)) for row in orc.it.tolist()]
+    assert (min if every_step else max)(distinct) >= 5, distinct
+    assert (orc.it == N).any() and (orc.it < N).any()
+
+
+@pytest.mark.parametrize("warm", [False, True], ids=["cold", "warm"])
+def test_m0_oracle_guard(oracle, warm):
+    """On the oracle alone, at eps 1e-4: A with class_m0 at A_M0_SCALE = 4 meets assert_m0_guard.  Measured,
+    cold: 11 of 11 packs change with M0 and with M0 rolled by one class, 7 to 8 distinct counts at every step,
+    1 of the 66 solves capped at N = 2000 (at scales 0.5, 1 and 2 the largest count is 210, 210 and 320: no
+    capped solve, so the scale was doubled until one appeared).  Warm: the same 11 of 11 and 1 capped solve, but
+    7 distinct counts at step 0 and 1 to 2 afterwards at every scale up to 16 -- without signals nothing
+    disturbs a warm loop, whose later steps start at the solution -- so a warm run must show 5 distinct counts
+    at some step, the rule test_classes.assert_ragged already has for warm runs."""
+    I = inputs("A")
+    cfg = mode(I, warm, 1e-4)
+    assert_m0_guard(I, oracle_ref(oracle, I, cfg), oracle_ref(oracle, input_am(), cfg),
+                    oracle_ref(oracle, input_am(roll=1), cfg), cfg[1], every_step=not warm)
+
+
 # ------------------------------------------------------------------------------ GPU
+M0_MODES = [(False, 1e-4), (True, 1e-4), (False, 0.0)]
+M0_MODE_IDS = ["cold-tol", "warm-tol", "cold-fixed"]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("warm,tol", M0_MODES, ids=M0_MODE_IDS)
+@pytest.mark.parametrize("fused", [False, True], ids=["classes", "fused"])
+def test_per_class_m0(gpu, oracle, fused, warm, tol):
+    """A with a per-class M0 (gpad_setup_plant_classes with all six maps): the shared = 0 fleet and the oracle
+    bit for bit -- outputs, counts, codes, stats, tol_floor and flags; fused also the class handle with
+    everything off.  (The counts reach N here, test_m0_oracle_guard: no assert_ragged.)"""
+    I = input_am()
+    cfg = mode(I, warm, tol)
+    steps, N, _, _ = cfg
+    r = fused_run(I, cfg) if fused else class_plain(I, cfg)
+    assert (r.st["kernel"] == FUSED) == fused and r.st["kernel_ms"] > 0.0
+    if fused:
+        assert_same_run(r, class_plain(I, cfg))
+    ref, orc = fleet_ref(I, cfg), oracle_ref(oracle, I, cfg)
+    assert_same_run(r, ref)
+    assert_matches_oracle(r, orc)
+    for k in ("tol_floor", "below_tol_floor", "nonfinite_g"):
+        assert r.st[k] == ref.st[k], k
+    assert r.st["total_iterations"] == int(orc.it.sum()) == int(r.it.sum())
+    assert r.st["iterations"] == int(r.it.max()) and r.st["converged"] == int((r.cd != 0).sum())
+    if not tol:
+        assert (r.it == N).all() and (r.cd == 0).all()
+
+
 def check_fused(oracle, I, cfg, r):
     """r is a fused run: the class handle with everything off, the shared = 0 fleet and the oracle, bit for
     bit; the stats of the fleet."""

@@ -19,6 +19,12 @@ rng.uniform(-I, I, (steps, B)), references rng.uniform(-0.1, 0.1, (steps, B, n_u
   SQ   test_class_loop Q (33 packs in classes of 17 / 15 / 1), seed 214, 6 steps, HARD, N 2000
 HARD: a = 0.9, I = 12; MILD: a = 0.6, I = 7.  Fixed-N mode: N = 100.  test_oracle_guard asserts on the oracle
 what these inputs must show (ragged counts, capped next to early solves, every fault visible).
+
+The battery plants bind no M0, so SA also runs with a per-class M0 (m0_input: test_class_loop.class_m0 at scale
+0.5) -- through the per-class plant, and through one plant under per-class signals, where M0, g0, B are
+replicated beside the packed images.  test_m0_oracle_guard, on the oracle at eps 1e-4, cold / warm: M0 changes the
+us bits of 11 of 11 packs, so does M0 rolled by one class; the one-plant variant differs in exactly the 7 packs
+outside class 0; 6 to 8 / 6 to 7 distinct counts per step; 3 of the 66 solves capped.
 """
 from __future__ import annotations
 
@@ -34,7 +40,7 @@ import pytest
 
 import test_signals as TS
 from conftest import ROOT
-from test_class_loop import FUSED, input_q
+from test_class_loop import FUSED, M0_MODE_IDS, M0_MODES, assert_m0_guard, class_m0, input_q
 from test_classes import MODE_IDS, MODES, _L, class_solver, inputs as base_inputs
 from test_loop_async import F32, F64, assert_same_run, same_bits
 from test_signals import HARD, MILD
@@ -307,6 +313,76 @@ def test_oracle_guard(oracle, name, warm):
         if fault == "rows":  # (a pack whose sorted position is its own keeps its row)
             moved |= np.argsort(I.class_of, kind="stable") == np.arange(I.class_of.size)
         assert moved.all(), (fault, np.flatnonzero(~moved))
+
+
+PLANT_MAPS = ("PM", "Pg", "M0", "g0", "A", "B")
+
+
+def m0_input(roll=0, one_plant=False):
+    """SA with test_class_loop.class_m0 as a per-class M0 (rolled by `roll` classes: the guard's wrong class
+    index); one_plant: class 0's plant maps, M0[0] among them, for every class under the per-class signals."""
+    I = sig_input("SA")
+    J = with_maps(I, "M0" + ("-roll%d" % roll if roll else ""), M0=np.roll(class_m0(I.K, I.C.qp.n), roll, axis=0))
+    if one_plant:
+        J = with_maps(J, "class0-plant", **{k: np.stack([getattr(J.C, k)[0]] * I.K) for k in PLANT_MAPS})
+    return J
+
+
+@pytest.mark.parametrize("warm", [False, True], ids=["cold", "warm"])
+def test_m0_oracle_guard(oracle, warm):
+    """On the oracle alone, at eps 1e-4: SA with the per-class M0 meets test_class_loop.assert_m0_guard, and the
+    one-plant variant differs from the per-class one in exactly the 7 packs that are not in class 0."""
+    I = sig_input("SA")
+    cfg = mode(I, warm, 1e-4)
+    assert_m0_guard(I, oracle_ref(oracle, I, cfg), oracle_ref(oracle, m0_input(), cfg),
+                    oracle_ref(oracle, m0_input(roll=1), cfg), cfg[1],
+                    other=oracle_ref(oracle, m0_input(one_plant=True), cfg), differ=I.class_of != 0)
+    assert int((I.class_of != 0).sum()) == 7
+
+
+# ------------------------------------------------------------------------------ GPU: a per-class M0
+@pytest.mark.gpu
+@pytest.mark.parametrize("warm,tol", M0_MODES, ids=M0_MODE_IDS)
+@pytest.mark.parametrize("fused", [False, True], ids=["classes", "fused"])
+def test_per_class_m0(gpu, oracle, fused, warm, tol):
+    """A per-class plant with M0 under per-class signals: the fleet and the oracle; fused also the class handle
+    with everything off."""
+    I = m0_input()
+    cfg = mode(I, warm, tol)
+    r = sig_run(I, cfg, fused=True) if fused else class_plain(I, cfg)
+    if fused:
+        check_fused(oracle, I, cfg, r)
+    else:
+        check_against_references(oracle, I, cfg, r)
+        assert r.st["kernel"] not in (None, FUSED) and r.st["kernel_ms"] > 0.0
+
+
+def one_plant_run(I, cfg, fused):
+    """m0_input(one_plant=True) as the binding sees it: class 0's maps and M0[0] through the 2-d setup_plant,
+    then the per-class signals -- M0, g0 and B are replicated to a copy per class beside the packed images."""
+    one = {k: F32(getattr(I.C, k)[0]) for k in PLANT_MAPS}
+    s = class_solver(I, kernel=I.kernel)
+    s.setup_plant(one["PM"], one["Pg"], M0=one["M0"], g0=one["g0"], A=one["A"], B=one["B"])
+    bind_signals(s, I.C)
+    if fused:
+        s.set_class_loop_fused(True)
+    return sig_loop(s, I, cfg)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("warm,tol", M0_MODES, ids=M0_MODE_IDS)
+@pytest.mark.parametrize("fused", [False, True], ids=["classes", "fused"])
+def test_one_plant_with_m0_under_per_class_signals(gpu, oracle, fused, warm, tol):
+    """The replication path: one plant with M0 under per-class signals == the fleet and the oracle with that
+    plant replicated; fused also the same binding run class by class.  Not the per-class plant's bits."""
+    I = m0_input(one_plant=True)
+    cfg = mode(I, warm, tol)
+    plain = cached("one-plant", I, cfg, lambda: one_plant_run(I, cfg, False))
+    r = one_plant_run(I, cfg, True) if fused else plain
+    assert (r.st["kernel"] == FUSED) == fused and r.st["kernel_ms"] > 0.0
+    assert_same_run(r, plain)
+    check_against_references(oracle, I, cfg, r)
+    assert r.us.tobytes() != class_plain(m0_input(), cfg).us.tobytes()
 
 
 # ------------------------------------------------------------------------------ GPU: class by class
