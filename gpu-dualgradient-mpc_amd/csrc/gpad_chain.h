@@ -1,13 +1,13 @@
-// gpad_chain.h -- device helpers shared by the latency kernels (gpad_kernels.hip: stream and
-// resident kernels; gpad_duo.hip: the two-instance ping-pong kernel): fused-arithmetic wrappers,
-// wave64 reductions and the Algorithm-1 test slots, and the register-resident DPP fmaf chains.
-// The MFMA panel kernels' test (gpad_panel_test.h) takes the butterflies, the reduction ops and
-// check_code from here.
+// gpad_chain.h -- device helpers of the row kernels (gpad_stream.hip, gpad_resident.hip, gpad_flat.hip,
+// gpad_duo.hip, gpad_loop.h): fused-arithmetic wrappers, wave64 reductions, the 8d row step and the
+// Algorithm-1 test with its slots, the register-resident DPP fmaf chains and their length buckets.
+// gpad_panel_test.h takes the per-row terms, the butterflies, the reduction ops and check_code from here.
 #pragma once
 
 #include <hip/hip_runtime.h>
 
 #include <cmath>
+#include <type_traits>
 #include <utility>
 
 #include "gpad_internal.h"
@@ -107,15 +107,52 @@ __device__ __forceinline__ double lane_read(double v, int l) {  // lane l's valu
     return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
 }
 
-// Per-wave partials of the Algorithm-1 test -> LDS slot of the wave.
-//   violz: max(u + pD) (recursive G_L z, nominates test A)   violh: max(G_L zhat + pD)
-//   magh:  max(|G_L zhat| + |pD|) (test B's rounding scale)  wmin, gap: test B's other terms
-// The verification of a nominated test A publishes max(G_L z + pD) in violz and
-// max(|G_L z| + |pD|) in magh of a second slot array.
+// ---- the dual row and the Algorithm-1 test, stated once ------------------------------------
+// Row i of an iteration, from c = (G_L zhat)_i:  8d y+ = [w + c + pD]+, 8a w+ = fma(beta, y+ - y, y+)
+// (row_step_dense / row_step_flat: the reference's two roundings), u = fma(1 - theta, u, theta c) (row_u).
+// A test event (every check_every iterations), over the live rows of an instance:
+//   1. TestRows::row: violh = max(c + pD), magh = max(|c| + |pD|) (B's rounding scale), wmin = min w,
+//      gap = -sum w (c + pD) in fp64, violz = max(u + pD)
+//   2. bit 1: (A) nominated by the recursive u: L violz <= tol;  bit 2: (B): viol_ok(violh, magh),
+//      wmin >= 0, L gap <= tol_gap
+//   3. a nominated (A) is decided on the direct chain cz = G_L z, to which the kernel resets u:
+//      VerRows::row: viol = max(cz + pD), mag = max(|cz| + |pD|); viol_ok(viol, mag)
+//   4. check_code(bits, verified): 1 = (A) verified, 2 = (B), 0 = continue
+// Row kernels (a lane owns whole rows) reduce per wave into a CheckSlot: publish, barrier, check_stage1 /
+// check_verify.  gpad_flat_kernel and gpad_duo.h's half-step (duo, loop, fleet kernels) call the texts
+// below; gpad_stream_kernel and gpad_resident_kernel restate them, being slower through them
+// (profiles/r19_row_test_noreg.txt).  The MFMA panels extend TestRows / VerRows: gpad_panel_test.h.
+// One batch of the reference with stage 1, a verified (A) and codes 1 and 2: stream, resident, flat --
+// tests/test_schedule_tables.py test_both_codes_in_one_batch, test_flat_both_codes_in_one_batch,
+// test_seed_f64_both_codes_in_one_panel; gpad_loop_kernel -- tests/test_loop_async.py test_bit_identity
+// [*-warm-0.0001-*] (asserted there); the duo and fleet kernels run its half-step, no case of their own.
+
+// 8d + the next 8a of one row: y+ and w+ from c = (G_L zhat)_i; flat: StepFourGPADFlatSequential's order
+template <typename T> struct RowStep { T y, w; };
+template <typename T>
+__device__ __forceinline__ RowStep<T> row_step_dense(T c, T w, T pd, T y, T beta) {
+    const T sv = (w + pd) + c;                   // seq_functions.cpp:84
+    const T yp = (absd(sv) + sv) * T(0.5);       // seq_functions.cpp:85
+    return {yp, fmad(beta, yp - y, yp)};         // seq_functions.cpp:49 (8a of the next iteration)
+}
+template <typename T>
+__device__ __forceinline__ RowStep<T> row_step_flat(T c, T w, T pd, T y, T beta) {
+    const T sv = (c + w) + pd;                   // seq_functions.cpp:37
+    const T yp = sv < T(0) ? T(0) : sv;          // seq_functions.cpp:40-42
+    return {yp, fmad(beta, yp - y, yp)};
+}
+// u = G_L z by 8c's recursion (seq_functions.cpp:70): exact only in exact arithmetic, so it nominates
+template <typename T>
+__device__ __forceinline__ T row_u(T theta, T u, T c) {
+    return fmad(T(1) - theta, u, theta * c);
+}
+
+// per-wave partials of the test -> the wave's LDS slot (verification: viol in violz, mag in magh)
 struct CheckSlot {
     double violz, violh, wmin, gap, magh;
 };
 
+// the five wave butterflies, then lane 0 writes the wave's slot (TestRows / VerRows::publish)
 template <typename T>
 __device__ __forceinline__ void check_publish(CheckSlot* slots, T violz, T violh, T wmin,
                                               double gap, T magh) {
@@ -130,6 +167,54 @@ __device__ __forceinline__ void check_publish(CheckSlot* slots, T violz, T violh
         s.magh = (double)e;
     }
 }
+
+// The test's per-row terms, the one text of them.  S: the kernel's scalar.  row() folds a live row
+// into the initial values; only_row() assigns, for a lane that has one row per test.  No decision
+// differs: fmax(-inf, x) = x, fmax(0, |c| + |pD|) = the sum, fmin(inf, x) = x for every number x, and
+// 0 - w t differs from -(w t) only in a zero's sign, which `gap L <= tol_gap` does not see.  A NaN row
+// leaves the initial value, assignment NaN: the wave butterfly's fmax / fmin drop a NaN operand, and
+// check_stage1 / check_verify fold an all-NaN slot into the same initial values; gap is NaN in both.
+template <typename S>
+struct TestRows {
+    S violz = -INFINITY, violh = -INFINITY, wmin = INFINITY, magh = 0;
+    double gap = 0.0;
+    // a live row: cv = (G_L zhat)_i, pd = pD_i, w = w_i, u = the recursive (G_L z)_i
+    __device__ __forceinline__ void row(S cv, S pd, S w, S u) {
+        const S tt = cv + pd;
+        violh = fmax(violh, tt);
+        magh = fmax(magh, absd(cv) + absd(pd));
+        wmin = fmin(wmin, w);
+        gap -= (double)w * (double)tt;
+        violz = fmax(violz, u + pd);
+    }
+    // gpad_duo.h's half-step: with row() register-bound gpad_loop_fleet_kernel instantiations spill
+    // more; with this the duo, loop and fleet kernels have the parent's code (r19_row_test_isa.txt)
+    __device__ __forceinline__ void only_row(S cv, S pd, S w, S u) {
+        const S tt = cv + pd;
+        violh = tt;
+        magh = absd(cv) + absd(pd);
+        wmin = w;
+        gap = -((double)w * (double)tt);
+        violz = u + pd;
+    }
+    // row kernels: this wave's partials to its slot (every lane of the wave calls)
+    __device__ __forceinline__ void publish(CheckSlot* slots) const {
+        check_publish<S>(slots, violz, violh, wmin, gap, magh);
+    }
+};
+
+// the verification of a nominated (A) (step 3 above)
+template <typename S>
+struct VerRows {
+    S viol = -INFINITY, mag = 0;
+    __device__ __forceinline__ void row(S cz, S pd) {  // a live row: cz = (G_L z)_i
+        viol = fmax(viol, cz + pd);
+        mag = fmax(mag, absd(cz) + absd(pd));
+    }
+    __device__ __forceinline__ void publish(CheckSlot* slots) const {
+        check_publish<S>(slots, viol, viol, viol, 0.0, mag);
+    }
+};
 
 // Every thread evaluates the decision from the same LDS words -> uniform, no extra barrier.
 // Lane i < nwaves (<= 8) reads slot i -- one LDS round trip instead of one per slot -- the maxima
@@ -285,6 +370,25 @@ inline int res_bucket(int len) {
     if (len > 200) return 208;
     if (len > 192) return 200;
     return (len + 31) / 32 * 32;
+}
+// f(std::integral_constant<int, K>) for the bucket k = res_bucket(.)
+template <typename F>
+inline auto with_bucket(int k, F f) {
+    switch (k) {
+        case 32: return f(std::integral_constant<int, 32>{});
+        case 64: return f(std::integral_constant<int, 64>{});
+        case 96: return f(std::integral_constant<int, 96>{});
+        case 128: return f(std::integral_constant<int, 128>{});
+        case 160: return f(std::integral_constant<int, 160>{});
+        case 192: return f(std::integral_constant<int, 192>{});
+        case 200: return f(std::integral_constant<int, 200>{});
+        default: return f(std::integral_constant<int, 208>{});
+    }
+}
+// f(KA, KB), integral constants, for the bucket pair: the 8 x 8 kernel<KA, KB> instantiations
+template <typename F>
+inline auto with_buckets(int ka, int kb, F f) {
+    return with_bucket(ka, [&](auto A) { return with_bucket(kb, [&](auto B) { return f(A, B); }); });
 }
 
 }  // namespace gpad

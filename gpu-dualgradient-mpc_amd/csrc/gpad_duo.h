@@ -80,30 +80,21 @@ __device__ __forceinline__ void duo_half_a(const DuoCtx& c, DuoSlot& sa, const f
 template <int KB, int K>
 __device__ __forceinline__ void duo_half_b(const DuoCtx& c, DuoSlot& sb, bool chk, const float* zhb_l, float* wb_l,
                                            const float* pdb_l, CheckSlot* slots_b, const float (&r)[K]) {
-    float violz = -INFINITY, violh = -INFINITY, wmin = INFINITY, magh = 0.0f;
-    double gap = 0.0;
+    TestRows<float> tp;
     const float th = sb.th, bn = sb.bn;
     const float pdv = pdb_l[c.row];  // (before the chain, as gpv)
     const float cv = chain_regs<KB, K>(r, zhb_l);
     GPAD_DSTAMP(1);
     if (c.live) {
-        const float pdi = pdv, wi = sb.x1;
-        const float sv = (wi + pdi) + cv;                     // seq_functions.cpp:84
-        const float yp = (__builtin_fabsf(sv) + sv) * 0.5f;   // seq_functions.cpp:85
-        if (c.use_tol) sb.x2 = __builtin_fmaf(1.0f - th, sb.x2, th * cv);
-        if (chk) {
-            const float t = cv + pdi;
-            violh = t;
-            magh = __builtin_fabsf(cv) + __builtin_fabsf(pdi);
-            wmin = wi;
-            gap = -((double)wi * (double)t);
-            violz = sb.x2 + pdi;
-        }
-        sb.x1 = __builtin_fmaf(bn, yp - sb.x0, yp);
-        sb.x0 = yp;
+        const float wi = sb.x1;
+        if (c.use_tol) sb.x2 = row_u(th, sb.x2, cv);
+        if (chk) tp.only_row(cv, pdv, wi, sb.x2);
+        const RowStep<float> nx = row_step_dense(cv, wi, pdv, sb.x0, bn);
+        sb.x1 = nx.w;
+        sb.x0 = nx.y;
         wb_l[c.row] = sb.x1;
     }
-    if (chk) check_publish<float>(slots_b, violz, violh, wmin, gap, magh);
+    if (chk) tp.publish(slots_b);
 }
 
 // after the barrier that closes slot sb's 8d half (every wave): iteration count, schedule and the
@@ -133,6 +124,8 @@ __device__ __forceinline__ int duo_test_b(const SolveArgs<float>& a, const DuoCt
         if (st1 & 1) {  // (A) nominated: decide on the direct chain G_L z, reset u to it
             if (c.isA && c.live) z_l[c.row] = sb.x0;
             __syncthreads();
+            // (VerRows::row / publish of the lane's one row, written out: through the struct 13 register-
+            // bound gpad_loop_fleet_kernel instantiations spill 8 more bytes, r19_row_test_isa.txt)
             float vc = -INFINITY, mc = 0.0f;
             if (!c.isA) {
                 const float cz = chain_regs<KB, K>(r, z_l);

@@ -1,5 +1,5 @@
 // gpad_duo.hip -- the two-instance ping-pong latency kernel (shared matrices), separate from
-// gpad_kernels.hip so the two sets of template instantiations compile in parallel.
+// gpad_resident.hip so the two sets of template instantiations compile in parallel.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -299,38 +299,16 @@ __global__ __launch_bounds__(kResidentMaxThreads) void gpad_duo_kernel(SolveArgs
     }
 }
 
-template <int KA>
-static void launch_duo_b(int kb, dim3 g, dim3 bl, hipStream_t st, const SolveArgs<float>& a) {
-    switch (kb) {
-        case 32: hipLaunchKernelGGL((gpad_duo_kernel<KA, 32>), g, bl, 0, st, a); break;
-        case 64: hipLaunchKernelGGL((gpad_duo_kernel<KA, 64>), g, bl, 0, st, a); break;
-        case 96: hipLaunchKernelGGL((gpad_duo_kernel<KA, 96>), g, bl, 0, st, a); break;
-        case 128: hipLaunchKernelGGL((gpad_duo_kernel<KA, 128>), g, bl, 0, st, a); break;
-        case 160: hipLaunchKernelGGL((gpad_duo_kernel<KA, 160>), g, bl, 0, st, a); break;
-        case 192: hipLaunchKernelGGL((gpad_duo_kernel<KA, 192>), g, bl, 0, st, a); break;
-        case 200: hipLaunchKernelGGL((gpad_duo_kernel<KA, 200>), g, bl, 0, st, a); break;
-        default: hipLaunchKernelGGL((gpad_duo_kernel<KA, 208>), g, bl, 0, st, a); break;
-    }
-}
-
 hipError_t launch_duo(const SolveArgs<float>& a, int grid, hipStream_t st) {
     if (!resident_supported(a.n, a.m) || a.strideA || a.strideB || !a.qctr || grid < 1)
         return hipErrorInvalidValue;
     const int threads = 64 * (((a.n + 63) >> 6) + ((a.m + 63) >> 6));
     const dim3 g(grid), bl(threads);
     const int ka = res_bucket(a.m), kb = res_bucket(a.n);
-    switch (ka) {
-        case 32: launch_duo_b<32>(kb, g, bl, st, a); break;
-        case 64: launch_duo_b<64>(kb, g, bl, st, a); break;
-        case 96: launch_duo_b<96>(kb, g, bl, st, a); break;
-        case 128: launch_duo_b<128>(kb, g, bl, st, a); break;
-        case 160: launch_duo_b<160>(kb, g, bl, st, a); break;
-        case 192: launch_duo_b<192>(kb, g, bl, st, a); break;
-        case 200: launch_duo_b<200>(kb, g, bl, st, a); break;
-        default: launch_duo_b<208>(kb, g, bl, st, a); break;
-    }
+    with_buckets(ka, kb, [&](auto KA, auto KB) {
+        hipLaunchKernelGGL((gpad_duo_kernel<decltype(KA)::value, decltype(KB)::value>), g, bl, 0, st, a);
+    });
     return hipGetLastError();
 }
-
 
 }  // namespace gpad

@@ -120,44 +120,34 @@ __global__ __launch_bounds__(kFlatBlock) void gpad_flat_kernel(SolveArgs<float> 
         __syncthreads();
         // ---- 8d + next 8a (StepFourGPADFlatSequential) ----------------------------------
         const bool chk = use_tol && ((v + 1) % a.check_every) == 0;
-        float violz = -INFINITY, violh = -INFINITY, wmin = INFINITY, magh = 0.0f;
-        double gap = 0.0;
+        TestRows<float> tp;
         for (int r = tid; r < m; r += kFlatBlock) {
             const float s = flat_row4(GLT, zh, r, Nh, n_u, mc, m);
             const float wi = w[r], pdi = pd[r], yi = ys[r];
-            const float sv = (s + wi) + pdi;        // seq_functions.cpp:37
-            const float yp = sv < 0.0f ? 0.0f : sv;  // seq_functions.cpp:40-42
             if (use_tol) {
-                const float ui = __builtin_fmaf(omt, us[r], th * s);
+                const float ui = row_u(th, us[r], s);
                 us[r] = ui;
-                if (chk) {
-                    const float t = s + pdi;
-                    violh = fmaxf(violh, t);
-                    magh = fmaxf(magh, __builtin_fabsf(s) + __builtin_fabsf(pdi));
-                    wmin = fminf(wmin, wi);
-                    gap -= (double)wi * (double)t;
-                    violz = fmaxf(violz, ui + pdi);
-                }
+                if (chk) tp.row(s, pdi, wi, ui);
             }
-            w[r] = __builtin_fmaf(bnext, yp - yi, yp);
-            ys[r] = yp;
+            const RowStep<float> nx = row_step_flat(s, wi, pdi, yi, bnext);
+            w[r] = nx.w;
+            ys[r] = nx.y;
         }
         constexpr int nw = kFlatBlock / 64;
-        if (chk) check_publish<float>(slots, violz, violh, wmin, gap, magh);
+        if (chk) tp.publish(slots);
         __syncthreads();
         it = v + 1;
         if (chk) {
             const int st1 = check_stage1<float>(slots, nw, a.L, a.tol, a.tol_gap);
             bool verified = false;
             if (st1 & 1) {  // (A) nominated: decide on the direct flat chain G_L z, reset u to it
-                float vc = -INFINITY, mcz = 0.0f;
+                VerRows<float> vp;
                 for (int r = tid; r < m; r += kFlatBlock) {
                     const float cz = flat_row4(GLT, zs, r, Nh, n_u, mc, m);
                     us[r] = cz;
-                    vc = fmaxf(vc, cz + pd[r]);
-                    mcz = fmaxf(mcz, __builtin_fabsf(cz) + __builtin_fabsf(pd[r]));
+                    vp.row(cz, pd[r]);
                 }
-                check_publish<float>(slots + nw, vc, vc, vc, 0.0, mcz);
+                vp.publish(slots + nw);
                 __syncthreads();
                 verified = check_verify<float>(slots + nw, nw, a.L, a.tol);
             }

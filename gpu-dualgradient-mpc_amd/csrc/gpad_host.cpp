@@ -350,7 +350,7 @@ int gpad_phase_counts(gpad_handle_t h, int* counts, int cap) {
 }  // extern "C"
 namespace gpad {
 hipError_t read_stamps(unsigned long long* out, size_t bytes);      // gpad_pairs.hip (diagnostic builds)
-hipError_t read_res_stamps(unsigned long long* out, size_t bytes);  // gpad_kernels.hip
+hipError_t read_res_stamps(unsigned long long* out, size_t bytes);  // gpad_resident.hip
 hipError_t read_duo_stamps(unsigned long long* out, size_t bytes);  // gpad_duo.hip
 }
 extern "C" {

@@ -1,5 +1,5 @@
 // gpad_internal.h -- device-side argument blocks and kernel launchers shared by the
-// HIP kernels (gpad_kernels.hip, the panel units, ...) and the host runtime (gpad_host.h and its units).
+// HIP kernels (gpad_stream.hip, gpad_resident.hip, the panel units, ...) and the host runtime (gpad_host.h and its units).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -147,7 +147,7 @@ struct SolveArgs {
 template <typename T>
 hipError_t launch_stream(const SolveArgs<T>& a, hipStream_t s);
 hipError_t launch_resident(const SolveArgs<float>& a, hipStream_t s, bool* supported);
-// two-instance ping-pong kernel over a work list (shared matrices; gpad_kernels.hip): the
+// two-instance ping-pong kernel over a work list (shared matrices; gpad_duo.hip): the
 // list is idx_in/count_in (a no-op unless *count_in <= a.fin_thresh) or 0..batch-1; needs a
 // zeroed a.qctr.  Persistent grid of `grid` workgroups (one per CU).
 hipError_t launch_duo(const SolveArgs<float>& a, int grid, hipStream_t s);
@@ -327,7 +327,7 @@ hipError_t launch_plant_step_sig(const T* AE, const T* B, const T* xt, const T* 
 
 // gpad_flat.hip (flat battery path; MGt = flat -ML [Nh][m], GLt = flat G_L t-major [Nh][m])
 hipError_t launch_flat(const SolveArgs<float>& a, hipStream_t s);
-// register-resident flat variant (gpad_kernels.hip): a.MGt = flat -ML (Nh x m), a.GLt = the
+// register-resident flat variant (gpad_resident.hip): a.MGt = flat -ML (Nh x m), a.GLt = the
 // flat G_L expanded to the full k-major image [n][ldm]
 bool flat_resident_supported(int n, int m, int n_u);
 hipError_t launch_flat_resident(const SolveArgs<float>& a, hipStream_t s);

@@ -505,32 +505,12 @@ LoopFn loop_fn_ab() {
     if constexpr (MODE == kLoopFleet) return gpad_loop_fleet_kernel<KA, KB>;
     else return gpad_loop_kernel<KA, KB, MODE>;
 }
-template <int MODE, int KA>
-LoopFn loop_fn_b(int kb) {
-    switch (kb) {
-        case 32: return loop_fn_ab<MODE, KA, 32>();
-        case 64: return loop_fn_ab<MODE, KA, 64>();
-        case 96: return loop_fn_ab<MODE, KA, 96>();
-        case 128: return loop_fn_ab<MODE, KA, 128>();
-        case 160: return loop_fn_ab<MODE, KA, 160>();
-        case 192: return loop_fn_ab<MODE, KA, 192>();
-        case 200: return loop_fn_ab<MODE, KA, 200>();
-        default: return loop_fn_ab<MODE, KA, 208>();
-    }
-}
 // ka = res_bucket(m), kb = res_bucket(n)
 template <int MODE>
 LoopFn loop_fn_of(int ka, int kb) {
-    switch (ka) {
-        case 32: return loop_fn_b<MODE, 32>(kb);
-        case 64: return loop_fn_b<MODE, 64>(kb);
-        case 96: return loop_fn_b<MODE, 96>(kb);
-        case 128: return loop_fn_b<MODE, 128>(kb);
-        case 160: return loop_fn_b<MODE, 160>(kb);
-        case 192: return loop_fn_b<MODE, 192>(kb);
-        case 200: return loop_fn_b<MODE, 200>(kb);
-        default: return loop_fn_b<MODE, 208>(kb);
-    }
+    return with_buckets(ka, kb, [](auto KA, auto KB) {
+        return loop_fn_ab<MODE, decltype(KA)::value, decltype(KB)::value>();
+    });
 }
 // defined in gpad_loop_plant.hip / gpad_loop_fleet.hip
 LoopFn loop_fn_per_plant(int ka, int kb);

@@ -1,28 +1,21 @@
 // gpad_panel_test.h -- the Algorithm-1 termination test of the MFMA panel kernels, written once
-// (gfx950).  The register-resident family has gpad_chain.h's check_publish / check_stage1 /
-// check_verify; this is the same test for kernels whose wave holds four rows of each of a panel's
-// 16 columns: lane (j = lane >> 4, c = lane & 15) has rows 4r + j of column c.  S is the kernels'
-// scalar (float: gpad_panel.hip, gpad_loop_panel.hip, gpad_bigpanel.hip, gpad_flatpanel.hip;
-// double: gpad_panel64.hip).  The panel pairs (gpad_pairs.h) keep their own packed slots and
-// branch-free reduction, which were measured into place.
+// (gfx950).  gpad_chain.h states the test and holds its per-row terms (TestRows / VerRows); this is
+// the rest of it for kernels whose wave holds four rows of each of a panel's 16 columns: lane
+// (j = lane >> 4, c = lane & 15) has rows 4r + j of column c.  S is the kernels' scalar (float:
+// gpad_panel.hip, gpad_loop_panel.hip, gpad_bigpanel.hip, gpad_flatpanel.hip; double: gpad_panel64.hip).
+// The panel pairs (gpad_pairs.h) keep their own packed slots and reduction, measured into place.
 //
-// One test event, per column:
-//   1. every live row adds to the five partials                      TestPart::row
-//   2. they meet over the column's four lane groups (xor 16, xor 32) TestPart::fold
-//   3. and go to the slot of the wave (row tile, unit)               TestPart::put
+// One test event, per column (the numbers are gpad_chain.h's):
+//   1. every live row adds to the five partials (TestPart::row), they meet over the column's four
+//      lane groups, xor 16, xor 32 (fold), and go to the slot of the wave (row tile, unit) (put)
 //      -- barrier --
-//   4. the column's slots are reduced and decided on                 stage1
-//        bit 1: test (A) nominated by the recursive u = G_L z:  L max(u + pD) <= tol
-//        bit 2: test (B):  viol_ok(max(G_L zhat + pD), max(|G_L zhat| + |pD|)), w >= 0,
-//               -L w'(G_L zhat + pD) <= tol_gap
-//   5. a nominated (A) is decided on the direct chain cz = G_L z of a verification GEMM, through
-//      violz / magh of the same slots       VerPart::row / fold / put, -- barrier --, verified
-//      (the kernel resets u to cz in the rows it hands to VerPart::row)
-//   6. the code: gpad_chain.h check_code(bits, verified) -- as ballot masks where lanes 0..15 /
-//      0..63 decide for the columns: m1 = verified, m2 = (B) & ~m1
-// What stays in the kernels: which rows are live, which slot a wave writes, who reduces and how
-// the outcome becomes uniform (__syncthreads_or, or ballots of lanes 0..15 / 0..63), and the
-// bookkeeping of zhat in LDS.  viol_ok and ViolMargin are gpad_internal.h's.
+//   2. the column's slots are reduced and decided on: stage1
+//   3. a nominated (A) is decided on cz = G_L z of a verification GEMM, through violz / magh of the
+//      same slots: VerPart::row / fold / put, -- barrier --, verified (the kernel resets u to cz)
+//   4. check_code(bits, verified) -- as ballot masks where lanes 0..15 / 0..63 decide for the
+//      columns: m1 = verified, m2 = (B) & ~m1
+// What stays in the kernels: which rows are live, which slot a wave writes, who reduces and how the
+// outcome becomes uniform (__syncthreads_or, or ballots), and the bookkeeping of zhat in LDS.
 //
 // Every step in one workgroup -- stage 1, the verification GEMM and both codes 1 and 2 in one
 // 16-column panel of the reference -- is exercised by:
@@ -37,7 +30,7 @@
 
 #include <cmath>
 
-#include "gpad_chain.h"  // (bfly, OpMax / OpMin / OpAdd, absd, check_code)
+#include "gpad_chain.h"  // (TestRows / VerRows, bfly, OpMax / OpMin / OpAdd, absd, check_code)
 #include "gpad_internal.h"
 
 namespace gpad {
@@ -65,34 +58,24 @@ __device__ __forceinline__ V col_fold(V v, Op op) {
     }
 }
 
+// row(): gpad_chain.h TestRows, the one text of the per-row terms
 template <typename S>
-struct TestPart {
-    S violz = -INFINITY, violh = -INFINITY, wmin = INFINITY, magh = 0;
-    double gap = 0.0;
-    // a live row: cv = (G_L zhat)_i, pd = pD_i, w = w_i, u = the recursive (G_L z)_i
-    __device__ __forceinline__ void row(S cv, S pd, S w, S u) {
-        const S tt = cv + pd;
-        violh = fmax(violh, tt);
-        magh = fmax(magh, absd(cv) + absd(pd));
-        wmin = fmin(wmin, w);
-        gap -= (double)w * (double)tt;
-        violz = fmax(violz, u + pd);
-    }
+struct TestPart : TestRows<S> {
     template <bool SHFL = false>
     __device__ __forceinline__ void fold() {
-        violz = col_fold<SHFL>(violz, OpMax{});
-        violh = col_fold<SHFL>(violh, OpMax{});
-        magh = col_fold<SHFL>(magh, OpMax{});
-        wmin = col_fold<SHFL>(wmin, OpMin{});
-        gap = col_fold<SHFL>(gap, OpAdd{});
+        this->violz = col_fold<SHFL>(this->violz, OpMax{});
+        this->violh = col_fold<SHFL>(this->violh, OpMax{});
+        this->magh = col_fold<SHFL>(this->magh, OpMax{});
+        this->wmin = col_fold<SHFL>(this->wmin, OpMin{});
+        this->gap = col_fold<SHFL>(this->gap, OpAdd{});
     }
     __device__ __forceinline__ void put(TestSlot<S>& s, int c, bool lead) const {  // lead: lane group j == 0
         if (lead) {
-            s.violz[c] = violz;
-            s.violh[c] = violh;
-            s.magh[c] = magh;
-            s.wmin[c] = wmin;
-            s.gap[c] = gap;
+            s.violz[c] = this->violz;
+            s.violh[c] = this->violh;
+            s.magh[c] = this->magh;
+            s.wmin[c] = this->wmin;
+            s.gap[c] = this->gap;
         }
     }
 };
@@ -134,23 +117,19 @@ __device__ __forceinline__ Stage1 stage1(const TestSlot<S>* slots, int first, in
     return r;
 }
 
+// row(): gpad_chain.h VerRows, on the live rows of a nominated column
 template <typename S>
-struct VerPart {
-    S viol = -INFINITY, mag = 0;
-    __device__ __forceinline__ void row(S cz, S pd) {  // a live row of a nominated column: cz = (G_L z)_i
-        viol = fmax(viol, cz + pd);
-        mag = fmax(mag, absd(cz) + absd(pd));
-    }
+struct VerPart : VerRows<S> {
     template <bool SHFL = false>
     __device__ __forceinline__ void fold() {
-        viol = col_fold<SHFL>(viol, OpMax{});
-        mag = col_fold<SHFL>(mag, OpMax{});
+        this->viol = col_fold<SHFL>(this->viol, OpMax{});
+        this->mag = col_fold<SHFL>(this->mag, OpMax{});
     }
     // (every wave's stage-1 reads of the slots precede the barrier before the verification GEMM)
     __device__ __forceinline__ void put(TestSlot<S>& s, int c, bool lead) const {
         if (lead) {
-            s.violz[c] = viol;
-            s.magh[c] = mag;
+            s.violz[c] = this->viol;
+            s.magh[c] = this->mag;
         }
     }
 };

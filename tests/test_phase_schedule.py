@@ -83,7 +83,7 @@ def _default_ends(N, length):
 
 
 def _fin_supported(n, m):
-    """The resident finisher's shapes (csrc/gpad_kernels.hip resident_supported: rows up to 208, one
+    """The resident finisher's shapes (csrc/gpad_resident.hip resident_supported: rows up to 208, one
     lane per row of z and of y in at most 512 threads)."""
     return max(n, m) <= 208 and 64 * ((n + 63) // 64 + (m + 63) // 64) <= 512
 

@@ -21,8 +21,8 @@ f32 results are bit-identical to the oracle's; f64 counts and codes are equal an
 Where each seed u = G_L z_{-1} and z0 load is observed (the engine that ran is st["kernel"], with the
 option that selects the variant):
 
-* gpad_kernels.hip stream (f32 and f64): test_seed[*-stream], test_seed_f64 ("stream");
-  resident: test_seed[*-resident] ("resident");
+* gpad_stream.hip (f32 and f64): test_seed[*-stream], test_seed_f64 ("stream");
+  gpad_resident.hip: test_seed[*-resident] ("resident");
 * gpad_panel.hip small panels (T <= 8): test_seed[37x53-panel]; gpad_pairs.hip panel pairs (T > 8), one panel per
   workgroup: test_seed[*-panel-onepanel]; pair layout (panel_max_grid = 2 for three panels):
   test_seed[*-panel-pair] and test_seed_mixed_batches, whose case (iii) depends on the per-wave znz
@@ -286,6 +286,44 @@ def flat_tol_reference(name):
     f = flat_feasible(n_u, Nh, B)
     th, be = tables(f"shift{s}", NMAX)
     return flat_oracle_solves(f, f.zf, NMAX, TOL, K, th, be)
+
+
+# Both codes in one batch of the row kernels (csrc/gpad_chain.h lists the cases per kernel): eight
+# instances of a case above, the even ones from z_f -- test (A) nominated by the recursion, verified on
+# the direct chain, code 1 -- and the odd ones from z0 = 0 -- test (B), code 2 -- under the case's table.
+BOTH_B = 8
+
+
+def _both_starts(zf):
+    z0 = np.array(zf[:BOTH_B])
+    z0[1::2] = 0.0
+    z0.setflags(write=False)
+    return z0
+
+
+def _both_codes_checked(what, ref):
+    """At least three instances of the oracle's batch end with each code."""
+    codes = ref[3]
+    assert int((codes == 1).sum()) >= 3 and int((codes == 2).sum()) >= 3, (what, codes.tolist(), ref[2].tolist())
+    assert ref[2].max() < NMAX
+
+
+@functools.lru_cache(maxsize=None)
+def both_codes_reference(name):
+    n, m, Bp, s, K = SEED_CASES[name]
+    p = problem(n, m, Bp)
+    th, be = tables(f"shift{s}", NMAX)
+    z0 = _both_starts(p.zf)
+    return z0, oracle_solves(p, z0, NMAX, TOL, K, th, be)
+
+
+@functools.lru_cache(maxsize=None)
+def flat_both_codes_reference(name):
+    n_u, Nh, B, s, K = FLAT_TOL[name]
+    f = flat_feasible(n_u, Nh, B)
+    th, be = tables(f"shift{s}", NMAX)
+    z0 = _both_starts(f.zf)
+    return z0, flat_oracle_solves(f, z0, NMAX, TOL, K, th, be)
 
 
 # ------------------------------------------------------------------------------------ CPU
@@ -583,6 +621,37 @@ def test_seed(gpu, oracle, name, kernel, opts):
     got = gpu_solve(p, B, kernel, p.zf, NMAX, TOL, K, th, be, opts=opts)
     assert got[4]["kernel"] == kernel
     same(got, seed_reference(name), f"{name} {kernel}")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name,kernel", [("37x53", "stream"), ("37x53", "resident"), ("136x136", "resident")],
+                         ids=["37x53-stream", "37x53-resident", "136x136-resident"])
+def test_both_codes_in_one_batch(gpu, oracle, name, kernel):
+    """The row kernels on one batch that the oracle ends with code 1 and with code 2 (test_seed's
+    instances all end with code 1 on them): stage 1, the verification of a nominated (A) and both codes
+    in one launch.  Counts, codes, z*, y* bit-identical to the oracle."""
+    n, m, Bp, s, K = SEED_CASES[name]
+    z0, ref = both_codes_reference(name)
+    _both_codes_checked(name, ref)
+    th, be = tables(f"shift{s}", NMAX)
+    got = gpu_solve(problem(n, m, Bp), BOTH_B, kernel, z0, NMAX, TOL, K, th, be)
+    assert got[4]["kernel"] == kernel
+    same(got, ref, f"both codes {name} {kernel}")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("engine", ["lds", "chains"])
+def test_flat_both_codes_in_one_batch(gpu, oracle, engine):
+    """As test_both_codes_in_one_batch on the LDS flat kernel and the register-resident flat chains
+    (flat 3x4; test_flat_seed's instances all end with code 1 on them)."""
+    n_u, Nh, _, s, K = FLAT_TOL["3x4"]
+    z0, ref = flat_both_codes_reference("3x4")
+    _both_codes_checked("flat 3x4", ref)
+    th, be = tables(f"shift{s}", NMAX)
+    kernel, opts = FLAT_ENGINES[engine]
+    got = flat_solve(flat_feasible(n_u, Nh, FLAT_TOL["3x4"][2]), BOTH_B, kernel, opts, z0, NMAX, TOL, K, th, be)
+    assert got[4]["kernel"] == "flat" and got[5] == 0
+    same(got, ref, f"flat both codes 3x4 {engine}")
 
 
 @pytest.mark.gpu

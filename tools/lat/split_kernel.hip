@@ -6,7 +6,7 @@
 // lds-bcast rows of profiles/r01_dpp_chain.txt), not the 5.9 of a register-operand chain, so the
 // plain half is the slower one; see DESIGN.md §5a.
 //
-// The bit-exact resident kernel (gpad_kernels.hip) keeps one matrix row per lane and runs each
+// The bit-exact resident kernel (gpad_resident.hip) keeps one matrix row per lane and runs each
 // row's dot product as ONE sequential fmaf chain -- the reference's order (seq_functions.cpp:61,
 // 82) -- so an iteration is 2 x K dependent `v_fmac_f32_dpp` steps on one wave per SIMD:
 // ~5.9 cycles each, 1.18 us per iteration at C2 (n = m = 200).  The DPP broadcast is a per-SIMD
