@@ -52,6 +52,7 @@ struct ClassBinding {
     int K = 0;
     std::vector<int> perm, offsets;   // class_order
     std::vector<gpad_handle_t> child; // [K]; null for an empty class
+    double zbound = 0.0;              // gpad_setup_infeasibility, for the whole-batch handle made later
     int major = 0;                    // the class with the most instances (ties: the lowest): stats kernel
     DevBuf idx;                          // device: perm[batch] | pos_off[batch] | pos_cnt[batch]
     DevBuf sorted, stage;                // class-sorted workspace; host callers' staging in caller order
@@ -292,6 +293,7 @@ static int fused_create(ClassBinding* cb, const Tuning& tune) {
     int rc = gpad_create(&f, cb->device, cb->stream);
     if (!rc) rc = gpad_setup(f, &fd, cb->mats.p, (const char*)cb->mats.p + mat, cb->child[cb->major]->L);
     if (!rc) rc = apply_tuning(f, tune);
+    if (!rc && cb->zbound > 0.0) rc = gpad_setup_infeasibility(f, cb->zbound);
     const int K = cb->K;
     const size_t image = f && f->frag_ok && f->frag_tiles >= 1 && f->frag_tiles <= 16
                              ? (size_t)2 * f->frag_tiles * f->frag_tiles * 1024
@@ -341,6 +343,17 @@ int classes_setup_signals(ClassBinding* cb, int ns, bool per_class, const void* 
     const int rc = cb->plant.bind_signals(cb->dims.memory, ns, per_class ? cb->K : 0, SM, Sg, E, cb->stream);
     lend_plant(cb);
     return rc;
+}
+
+int classes_setup_infeasibility(ClassBinding* cb, double zbound) {
+    for (gpad_handle_t c : cb->child) {
+        if (!c) continue;
+        if (const int rc = gpad_setup_infeasibility(c, zbound)) return rc;
+    }
+    if (cb->fused)  // (the fused loop then runs the certificate variant of the panel loop)
+        if (const int rc = gpad_setup_infeasibility(cb->fused, zbound)) return rc;
+    cb->zbound = zbound;
+    return GPAD_OK;
 }
 
 // The stats of the last run from every child (each call synchronises the stream and reports that child's

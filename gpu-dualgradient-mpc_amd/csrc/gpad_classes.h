@@ -97,6 +97,8 @@ int classes_setup_signals(ClassBinding* cb, int ns, bool per_class, const void* 
 // sg their s [batch][ns] / S [steps][batch][ns] in the caller's order
 int classes_state(ClassBinding* cb, void* x, void* z, void* y, const void* sg, bool with_sig, const char* where,
                   int steps, int N, double tol, int warm, void* xs, void* us, gpad_stats_t* st);
+// gpad_setup_infeasibility on every class (and the whole-batch handle of the fused loop)
+int classes_setup_infeasibility(ClassBinding* cb, double zbound);
 int classes_last_stats(ClassBinding* cb, gpad_stats_t* st);
 int classes_accumulate(ClassBinding* cb, long long* acc);
 int classes_sync(ClassBinding* cb);

@@ -118,13 +118,15 @@ int collect_stats(gpad_handle_t h, gpad_stats_t* st) {
         const int* cv = it + batch;
         for (int b = 0; b < batch; ++b) {
             st->iterations = std::max(st->iterations, it[b]);
-            st->converged += cv[b] != 0;
+            st->converged += cv[b] != 0 && cv[b] != GPAD_CODE_INFEASIBLE;  // (a certificate is no convergence)
             st->total_iterations += it[b];
             if (st->iters) st->iters[(size_t)t * batch + b] = it[b];
             if (st->codes) st->codes[(size_t)t * batch + b] = cv[b];
         }
     }
-    if (h->last_phased && h->last_steps == 1) {
+    // (a run with an infeasibility bound in force plans nothing: its phases have no pairs and no finisher, which
+    // the planner models, and its counts are cut short by code 5)
+    if (h->last_phased && h->last_steps == 1 && !(h->zbound > 0.0 && h->last_tol > 0.0)) {
         update_plan(h, h->h_counts.data(), batch, h->last_N);
         h->plan_pending = false;  // these counts are at least as recent as any copy in flight
     }
@@ -209,6 +211,7 @@ int gpad_destroy(gpad_handle_t h) {
         h->GLt.release();
         h->GLx.release();
         h->Hq.release();
+        h->frows.release();
         h->frag64.release();
         h->hfrag64.release();
         h->q64.release();

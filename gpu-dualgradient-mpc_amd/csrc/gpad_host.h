@@ -129,6 +129,9 @@ struct gpad_handle_s {
     DevBuf GLx;  // flat path: flat G_L expanded to the full k-major image (flat resident kernel)
     DevBuf Hq;           // gpad_setup_hessian: H, k-major [n][ldn] per matrix (value-function branches)
     bool hess_ok = false;
+    double zbound = 0.0;  // gpad_setup_infeasibility: the bound R on |z|_inf (0: none); a class-bound handle keeps
+                         // it for the handles its binding makes later
+    DevBuf frows;        // ... and r_i = sum_j |G_L[i][j]| per bound matrix, fp64 [copies][ldm] (gpad_farkas.h)
     DevBuf frag64;       // f64 panels (gpad_panel64.hip): -ML | G_L fragment images, shared f64 matrices
     bool frag64_ok = false;
     int frag64_tiles = 0;

@@ -144,8 +144,10 @@ struct SolveArgs {
 };
 
 // launchers (return hipError_t of the launch)
+// fk: the infeasibility certificate of the run (gpad_farkas.h), or null: the kernel without it
+struct FarkasArgs;
 template <typename T>
-hipError_t launch_stream(const SolveArgs<T>& a, hipStream_t s);
+hipError_t launch_stream(const SolveArgs<T>& a, hipStream_t s, const FarkasArgs* fk = nullptr);
 hipError_t launch_resident(const SolveArgs<float>& a, hipStream_t s, bool* supported);
 // two-instance ping-pong kernel over a work list (shared matrices; gpad_duo.hip): the
 // list is idx_in/count_in (a no-op unless *count_in <= a.fin_thresh) or 0..batch-1; needs a
@@ -206,7 +208,8 @@ bool loop_panel_supported(int n, int m, int nx, int nu);
 int loop_panel_grid(int n, int m, int batch, int num_cus, const Tuning* t);
 // persistent grid of `grid` <= min(ceil(batch / 16), kAbsmaxMaxBlocks) workgroups; with a.cls_K set the
 // class loop, grid <= min(sum_k ceil(count_k / 16), kAbsmaxMaxBlocks)
-hipError_t launch_loop_panel(const LoopArgs& a, int grid, hipStream_t s);
+// fk (with s.tol > 0): the kernel variant with the infeasibility certificate (gpad_farkas.h), fk->R the bound
+hipError_t launch_loop_panel(const LoopArgs& a, int grid, hipStream_t s, const FarkasArgs* fk = nullptr);
 // f64 panels on the f64 MFMA pipe (gpad_panel64.hip): shared matrices, n, m <= 256, one panel of 16
 // instances per workgroup, value-function branches when a.hfrag64 is set; a.frag = the -ML | G_L
 // images of launch_pack_panel64, a.frag_tiles = panel64_tiles(n, m)
@@ -256,7 +259,9 @@ __device__ __forceinline__ void list_survivors(const Args& a, int P, bool park, 
 // launch_panel: every launch of a solve -- one phase, or with tol > 0 and a.pwork the phases with
 // their boundaries and finisher; *supported false (and nothing launched): no fragment image for
 // this geometry
-hipError_t launch_panel(const SolveArgs<float>& a, hipStream_t s, bool* supported);
+// fk: the infeasibility certificate of the run (gpad_farkas.h) -- the T-wave kernel's variant for every
+// T <= 16 (n, m <= 256), no pair layout and no finisher; *supported false beyond -- or null
+hipError_t launch_panel(const SolveArgs<float>& a, hipStream_t s, bool* supported, const FarkasArgs* fk = nullptr);
 // launch_panel at (n, m) runs the panel pairs, which fold max |g| into their loads (gmax_part)
 bool panel_folds_gmax(int n, int m);
 size_t panel_work_bytes(int m, int batch);
@@ -279,7 +284,8 @@ size_t panel_frag_bytes(int n, int m, int batch);
 int panel_tiles(int n, int m, int batch);
 hipError_t launch_pack_panel(const float* ML, const float* G, int n, int m, int batch, float mg_sign,
                              double g_scale, void* frag, hipStream_t s);
-hipError_t launch_panel_single(int T, const SolveArgs<float>& a, int grid, hipStream_t s);
+hipError_t launch_panel_single(int T, const SolveArgs<float>& a, int grid, hipStream_t s,
+                               const FarkasArgs* fk = nullptr);
 // gpad_pairs.hip: one phase launch of the pair / relay kernel, T = 9..16 (picks the KQ / DROP instantiation)
 hipError_t launch_panel_pairs(int T, const SolveArgs<float>& a, int grid, hipStream_t s);
 // gpad_compact.hip: the boundary before phase ph >= 1: the survivors phase ph - 1 listed per panel

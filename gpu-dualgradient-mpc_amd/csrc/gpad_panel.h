@@ -122,10 +122,12 @@ __device__ __forceinline__ void panel_primal(f32x4 acc, const float4* Gp4, float
 }
 // GEMM 2 (acc = G_L zhat): y+ = [w + acc + p_D]+ (8d), the next w (8a) into Wl, the recursion
 // u = (1-th) u + th acc; at a test event (chk) the partials of the column's live rows (< m)
+// FK: the kernel variant with the infeasibility certificate; at a certificate event (cert) fq gets q
+template <bool FK = false>
 __device__ __forceinline__ TestPart<float> panel_dual(f32x4 acc, float4* Wl4, const float4* Pd4, int slot,
                                                       float omt, float th, float bn, bool use_tol, bool chk,
                                                       bool active, int row0, int m, float (&y)[4],
-                                                      float (&u)[4]) {
+                                                      float (&u)[4], bool cert = false, FarkasPart* fq = nullptr) {
     TestPart<float> part;
     const float4 w4 = Wl4[slot];
     const float wv[4] = {w4.x, w4.y, w4.z, w4.w};
@@ -142,6 +144,8 @@ __device__ __forceinline__ TestPart<float> panel_dual(f32x4 acc, float4* Wl4, co
             const float un = __builtin_fmaf(omt, u[r], th * cv);
             if (active) u[r] = un;
             if (chk && active && (row0 + 4 * r) < m) part.row(cv, pd[r], wv[r], u[r]);
+            if constexpr (FK)
+                if (cert && active && (row0 + 4 * r) < m) fq->row(yp, pd[r]);
         }
         if (active) y[r] = yp;
     }

@@ -80,6 +80,15 @@ struct TestPart : TestRows<S> {
     }
 };
 
+// The infeasibility certificate's nomination partial (gpad_farkas.h): q = sum y+ pD over a column's live
+// rows at a certificate event, folded and summed as gap is (lane groups, then the slots ascending).  Only
+// the kernel variants that carry the certificate hold one; the others' code does not change.
+struct FarkasPart {
+    double q = 0.0;
+    __device__ __forceinline__ void row(float yp, float pd) { q += (double)yp * (double)pd; }
+    __device__ __forceinline__ void fold() { q = col_fold<false>(q, OpAdd{}); }
+};
+
 // f(s) for the slots s of [first, first + count) in ascending order (the fp64 gap sum's order is
 // part of the result); N > 0: count == N at compile time, unrolled
 template <int N, typename F>

@@ -8,6 +8,7 @@
 #include <mutex>
 #include <tuple>
 
+#include "gpad_farkas.h"
 #include "gpad_host.h"
 
 // Shape-keyed plan prior.  A handle plans a phased solve from its OWN previous
@@ -150,6 +151,41 @@ int launch_solve(gpad_handle_t h, T* dz, T* dy, const T* dM, const T* dg, int N,
         HIP_TRY(hipMemsetAsync(a.iters, 0, sizeof(int) * (size_t)batch, h->stream));
         HIP_TRY(hipMemsetAsync(a.conv, 0, sizeof(int) * (size_t)batch, h->stream));
         *kernel_out = d.kernel == GPAD_KERNEL_AUTO ? GPAD_KERNEL_STREAM : d.kernel;
+        return finish(GPAD_OK);
+    }
+    // The infeasibility certificate (gpad_setup_infeasibility) is carried by the stream kernel and by the f32
+    // T-wave panels (shared matrices, n, m <= 256).  With a bound in force (tol > 0) AUTO and PANEL run those
+    // panels where they apply -- no pair layout, no finisher -- AUTO else the stream kernel, and a forced engine
+    // without the branch is refused rather than run without it
+    const bool fk_on = h->zbound > 0.0 && tol > 0.0;
+    const gpad::FarkasArgs fk{(const double*)h->frows.p, d.shared ? 0 : (long long)h->ldm, h->zbound};
+    if (fk_on) {
+        if (kernel == GPAD_KERNEL_RESIDENT)
+            return fail(GPAD_ERR_UNSUPPORTED, "the infeasibility certificate (gpad_setup_infeasibility) runs on the "
+                                              "stream kernel and the f32 T-wave panels, not on the resident kernel");
+        bool pok = false;
+        if constexpr (sizeof(T) == sizeof(float)) {
+            if (kernel != GPAD_KERNEL_STREAM && d.shared && h->frag_ok) {
+                int rc = h->pwork.ensure(gpad::panel_work_bytes(m, batch));
+                if (rc) return rc;
+                a.pwork = h->pwork.p;
+                a.used = &h->last_phases;  // (no plan: the planner models the pairs and the finisher)
+                e = gpad::launch_panel(a, h->stream, &pok, &fk);
+                if (e != hipSuccess) return fail(GPAD_ERR_HIP, std::string("panel: ") + hipGetErrorString(e));
+                if (!pok) a.pwork = nullptr, a.used = nullptr;
+            }
+        }
+        if (!pok && kernel == GPAD_KERNEL_PANEL)
+            return fail(GPAD_ERR_UNSUPPORTED, "the infeasibility certificate on the panels needs shared f32 matrices "
+                                              "with n, m <= 256");
+        if (!pok) {
+            e = gpad::launch_stream<T>(a, h->stream, &fk);
+            if (e != hipSuccess)
+                return fail(e == hipErrorInvalidValue ? GPAD_ERR_UNSUPPORTED : GPAD_ERR_HIP,
+                            std::string("stream kernel: ") + hipGetErrorString(e) + " (n+m beyond the LDS budget?)");
+        }
+        *kernel_out = pok ? GPAD_KERNEL_PANEL : GPAD_KERNEL_STREAM;
+        h->last_phased = pok;
         return finish(GPAD_OK);
     }
     if constexpr (sizeof(T) == sizeof(double)) {
@@ -312,7 +348,8 @@ static int run_typed(gpad_handle_t h, T* z, T* y, const T* M, const T* g, int N,
     h->last_kernel = kernel;
     h->last_batch = batch;
     h->last_steps = 1;
-    if (!st && ((h->last_phased && h->tune.plan) || (h->last_p64 && h->tune.lpt))) {  // asynchronous run: counts
+    const bool bound_run = h->zbound > 0.0 && tol > 0.0;  // (plans nothing: collect_stats)
+    if (!st && ((h->last_phased && h->tune.plan && !bound_run) || (h->last_p64 && h->tune.lpt))) {  // asynchronous run: counts
         // to the host behind it
         const size_t want = sizeof(int) * (size_t)batch;
         if (h->plan_pin_cap < want) {
@@ -355,6 +392,9 @@ static int run_impl(gpad_handle_t h, void* z0, void* y0, const void* M, const vo
     if (!z0 || !y0 || !M || !g) return fail(GPAD_ERR_INVALID, "gpad_run: null vector");
     if (N < 0) return fail(GPAD_ERR_INVALID, "gpad_run: N < 0");
     if (!(tol <= 0.0) && !std::isfinite(tol)) return fail(GPAD_ERR_INVALID, "gpad_run: bad tol");
+    if ((theta || beta) && h->zbound > 0.0 && tol > 0.0)  // (the certificate's events follow the library's schedule)
+        return fail(GPAD_ERR_UNSUPPORTED, "gpad_run_scaled: caller theta / beta tables with an infeasibility bound "
+                                          "in force (gpad_setup_infeasibility)");
     HIP_TRY(hipSetDevice(h->device));
     if (h->dims.dtype == GPAD_DTYPE_F64)
         return run_typed<double>(h, (double*)z0, (double*)y0, (const double*)M, (const double*)g, N,

@@ -5,6 +5,7 @@
 #include <algorithm>
 #include <cmath>
 
+#include "gpad_farkas.h"
 #include "gpad_host.h"
 
 int validate_dims(const gpad_dims_t* d) {
@@ -31,6 +32,7 @@ void unbind_problem(gpad_handle_t h) {
     h->own_plant.ns = 0;
     h->shadow_ok = false;
     h->hess_ok = false;
+    h->zbound = 0.0;
     h->frag64_ok = false;
     h->hfrag64_ok = false;
     h->plan.nph = 0;
@@ -186,6 +188,9 @@ int gpad_setup_hessian(gpad_handle_t h, const void* H) {
         if (h->cls) return no_classes("gpad_setup_hessian");
         if (!h->ready) return fail(GPAD_ERR_NOT_SETUP, "gpad_setup_hessian: call gpad_setup first");
         if (h->flat) return fail(GPAD_ERR_UNSUPPORTED, "gpad_setup_hessian: not on the flat battery path");
+        if (H && h->zbound > 0.0)
+            return fail(GPAD_ERR_UNSUPPORTED, "gpad_setup_hessian: an infeasibility bound is in force "
+                                              "(gpad_setup_infeasibility); unbind it first");
         h->hess_ok = false;
         h->hfrag64_ok = false;
         if (!H) return GPAD_OK;
@@ -216,6 +221,64 @@ int gpad_setup_hessian(gpad_handle_t h, const void* H) {
         }
         HIP_TRY(hipStreamSynchronize(h->stream));
         h->hess_ok = true;
+        return GPAD_OK;
+    });
+}
+
+int gpad_setup_infeasibility(gpad_handle_t h, double zbound) {
+    return gpad::abi_guard("gpad_setup_infeasibility", [&]() -> int {
+        if (!h) return fail(GPAD_ERR_INVALID, "gpad_setup_infeasibility: null handle");
+        if (!h->cls && !h->ready) return fail(GPAD_ERR_NOT_SETUP, "gpad_setup_infeasibility: call gpad_setup first");
+        if (!(zbound >= 0.0) || !std::isfinite(zbound))
+            return fail(GPAD_ERR_INVALID, "gpad_setup_infeasibility: zbound must be finite and >= 0");
+        HIP_TRY(hipSetDevice(h->device));
+        if (h->cls) {  // every class binds it, and the handles the binding makes later
+            if (const int rc = gpad::classes_setup_infeasibility(h->cls, zbound)) return rc;
+            h->zbound = zbound;
+            return GPAD_OK;
+        }
+        if (zbound > 0.0 && h->flat)
+            return fail(GPAD_ERR_UNSUPPORTED, "gpad_setup_infeasibility: not on the flat battery path");
+        if (zbound > 0.0 && h->hess_ok)
+            return fail(GPAD_ERR_UNSUPPORTED, "gpad_setup_infeasibility: a Hessian is bound (gpad_setup_hessian); "
+                                              "unbind it first");
+        h->zbound = 0.0;
+        if (zbound == 0.0) return GPAD_OK;
+        const gpad_dims_t& d = h->dims;
+        const int nmats = d.shared ? 1 : d.batch;
+        if (int rc = h->frows.ensure(sizeof(double) * (size_t)h->ldm * nmats)) return rc;
+        HIP_TRY(gpad::launch_farkas_rows(h->GLt.p, d.dtype == GPAD_DTYPE_F64, d.n, d.m, h->ldm, nmats,
+                                         (double*)h->frows.p, h->stream));
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        h->zbound = zbound;
+        return GPAD_OK;
+    });
+}
+
+// -(g'y) - R |G'y|_1 in fp64 on host arrays (no device): > 0 exactly when y >= 0 proves that no z with
+// |z|_inf <= R satisfies G z <= g; -inf when y has a negative entry (or a NaN)
+int gpad_farkas_margin(int n, int m, int dtype, const void* G, const void* g, const void* y, double zbound,
+                       double* margin) {
+    return gpad::abi_guard("gpad_farkas_margin", [&]() -> int {
+        if (n <= 0 || m <= 0 || !G || !g || !y || !margin || (dtype != GPAD_DTYPE_F32 && dtype != GPAD_DTYPE_F64) ||
+            !(zbound >= 0.0) || !std::isfinite(zbound))
+            return fail(GPAD_ERR_INVALID, "gpad_farkas_margin: bad arguments");
+        const bool f64 = dtype == GPAD_DTYPE_F64;
+        auto at = [&](const void* p, size_t i) { return f64 ? ((const double*)p)[i] : (double)((const float*)p)[i]; };
+        std::vector<double> t((size_t)n, 0.0);
+        double gy = 0.0;
+        for (int i = 0; i < m; ++i) {
+            const double yi = at(y, i);
+            if (!(yi >= 0.0)) {
+                *margin = -INFINITY;
+                return GPAD_OK;
+            }
+            gy += at(g, i) * yi;
+            for (int j = 0; j < n; ++j) t[j] += yi * at(G, (size_t)i * n + j);
+        }
+        double a = 0.0;
+        for (int j = 0; j < n; ++j) a += std::fabs(t[j]);
+        *margin = -gy - zbound * a;
         return GPAD_OK;
     });
 }

@@ -4,6 +4,7 @@
 #include <algorithm>
 #include <cmath>
 
+#include "gpad_farkas.h"
 #include "gpad_host.h"
 
 void attach_plant(gpad_handle_t h, const gpad::PlantStore* store, int first, bool all) {
@@ -222,6 +223,7 @@ static int one_launch_engine(gpad_handle_t h, bool loop, int N, double tol, int 
     const int n = d.n, m = d.m, nu = h->plant->nu;
     const bool lpanel = loop && h->tune.loop_panel && loop_panel_shape(h, N, tol, nxa);
     const bool async = lpanel || (loop && h->tune.loop_async && !h->flat && !h->hess_ok && N >= 1 &&
+                                  !(h->zbound > 0.0 && tol > 0.0) &&
                                   (d.kernel == GPAD_KERNEL_AUTO || d.kernel == GPAD_KERNEL_RESIDENT) &&
                                   gpad::loop_supported(n, m, nxa, nu));
     return lpanel ? GPAD_KERNEL_LOOP_PANEL : async ? GPAD_KERNEL_LOOP : 0;
@@ -282,7 +284,10 @@ static int run_loop_one_launch(gpad_handle_t h, const StateWork<float>& w, int e
         if (h->tune.duo_max_grid > 0 && h->tune.duo_max_grid < grid) grid = h->tune.duo_max_grid;
         grid = std::min(grid, (int)gpad::kAbsmaxMaxBlocks);
     }
-    const hipError_t e = lpanel ? gpad::launch_loop_panel(la, grid, h->stream) : gpad::launch_loop(la, grid, h->stream);
+    // (the panel loop carries the infeasibility certificate; gpad_loop_kernel does not: one_launch_engine)
+    const gpad::FarkasArgs fk{nullptr, 0, h->zbound};
+    const hipError_t e = lpanel ? gpad::launch_loop_panel(la, grid, h->stream, h->zbound > 0.0 && tol > 0.0 ? &fk : nullptr)
+                                : gpad::launch_loop(la, grid, h->stream);
     if (e != hipSuccess) return fail(GPAD_ERR_HIP, std::string("loop kernel: ") + hipGetErrorString(e));
     h->last_phased = false;
     h->last_p64 = false;

@@ -13,6 +13,7 @@
 #include <cmath>
 
 #include "gpad_chain.h"
+#include "gpad_farkas.h"
 #include "gpad_internal.h"
 
 namespace gpad {
@@ -29,7 +30,8 @@ struct StreamLds {
     T *w, *zh, *zs, *ys, *gp, *pd, *us;
     CheckSlot* slots;
     double* red;  // [waves] block-sum partials of the value functions
-    double* zp;   // [ldn] z(y+) of the dual function (value-function branches only)
+    double* zp;   // [ldn] z(y+) of the dual function (value-function branches only); the certificate's
+                  // variant, which excludes them: red = the nomination's wave partials of q, zp = t = G_L'y+
 };
 
 template <typename T>
@@ -48,8 +50,8 @@ __device__ __forceinline__ StreamLds<T> stream_lds(unsigned char* smem, int ldn,
     return s;
 }
 
-// LDS bytes of the stream kernel: the vectors, the test slots and (value branches) the block-sum
-// partials and z(y+)
+// LDS bytes of the stream kernel: the vectors, the test slots and (value branches, or the infeasibility
+// certificate) the block-sum partials and z(y+)
 template <typename T>
 size_t stream_lds_bytes(int ldn, int ldm, bool value) {
     return sizeof(T) * (size_t)(3 * ldn + 4 * ldm) + sizeof(CheckSlot) * 2 * (kStreamBlock / 64) +
@@ -161,161 +163,52 @@ __device__ int stream_value_branch(const SolveArgs<T>& a, const StreamLds<T>& s,
     return V - D <= eV * (D > 1.0 ? D : 1.0) ? 4 : 0;  // :76
 }
 
+// the two variants of the kernel (gpad_stream_solve.inc)
+#define GPAD_STREAM_FK 0
+#include "gpad_stream_solve.inc"
+#undef GPAD_STREAM_FK
+#define GPAD_STREAM_FK 1
+#include "gpad_stream_solve.inc"
+#undef GPAD_STREAM_FK
+
+// fk: the infeasibility certificate of this run, or null (the kernel without it)
 template <typename T>
-__global__ __launch_bounds__(kStreamBlock) void gpad_stream_kernel(SolveArgs<T> a) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int tid = threadIdx.x;
-    const int b = blockIdx.x;
-    const int n = a.n, m = a.m, ldn = a.ldn, ldm = a.ldm;
-    const StreamLds<T> s = stream_lds<T>(smem, ldn, ldm);
-    const T* __restrict__ MGt = a.MGt + (size_t)b * a.strideA;
-    const T* __restrict__ GLt = a.GLt + (size_t)b * a.strideB;
-    T* zg = a.z + (size_t)b * n;
-    T* yg = a.y + (size_t)b * m;
-    const T* gPg = a.gP + (size_t)b * a.ld_gP;
-    const T* gg = a.g + (size_t)b * a.ld_g;
-    const T beta0 = a.beta[0];
-
-    for (int i = tid; i < ldn; i += kStreamBlock) {
-        s.zs[i] = i < n ? zg[i] : T(0);
-        s.gp[i] = i < n ? gPg[i] : T(0);
-        s.zh[i] = T(0);
-    }
-    for (int i = tid; i < ldm; i += kStreamBlock) {
-        const T yv = i < m ? yg[i] : T(0);
-        s.ys[i] = yv;
-        s.pd[i] = i < m ? (T)(a.gscale * (double)gg[i]) : T(0);
-        s.w[i] = fmad(beta0, yv - yv, yv);  // 8a with y_0 = y_{-1} (acceldualgrad.m:16,43)
-    }
-    __syncthreads();
-    const bool use_tol = a.tol > 0.0;
-    if (use_tol) {  // u = G_L z_{-1}; afterwards u follows the 8c recursion (u = G_L z exactly)
-        for (int r0 = 4 * tid; r0 < m; r0 += 4 * kStreamBlock) {
-            T c[4] = {T(0), T(0), T(0), T(0)};
-            chain4<T>(GLt, ldm, r0, s.zs, n, c);
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-                if (r0 + r < m) s.us[r0 + r] = c[r];
-        }
-    }
-
-    const int nwaves = kStreamBlock / 64;
-    int it = 0;
-    int done = 0;
-    for (int v = 0; v < a.N; ++v) {
-        const T th = a.theta[v];
-        const T omt = T(1) - th;
-        const T bnext = a.beta[v + 1];
-        // ---- phase 1: 8b + 8c, rows of -ML ----------------------------------------------
-        for (int r0 = 4 * tid; r0 < n; r0 += 4 * kStreamBlock) {
-            T acc[4] = {T(0), T(0), T(0), T(0)};
-            chain4<T>(MGt, ldn, r0, s.w, m, acc);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int i = r0 + r;
-                if (i < n) {
-                    const T zhv = acc[r] - s.gp[i];                 // seq_functions.cpp:63
-                    s.zh[i] = zhv;
-                    s.zs[i] = fmad(omt, s.zs[i], th * zhv);         // seq_functions.cpp:70
-                }
-            }
-        }
-        __syncthreads();
-        // ---- phase 2: 8d + next 8a, rows of G/L ------------------------------------------
-        // (own text of gpad_chain.h's row step and test terms: slower through them, r19_row_test_noreg.txt)
-        const bool chk = use_tol && ((v + 1) % a.check_every) == 0;
-        T violz = neg_inf<T>(), violh = neg_inf<T>(), wmin = -neg_inf<T>(), magh = T(0);
-        double gap = 0.0;
-        for (int r0 = 4 * tid; r0 < m; r0 += 4 * kStreamBlock) {
-            T c[4] = {T(0), T(0), T(0), T(0)};
-            chain4<T>(GLt, ldm, r0, s.zh, n, c);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int i = r0 + r;
-                if (i < m) {
-                    const T wi = s.w[i], pdi = s.pd[i], yi = s.ys[i];
-                    const T sv = (wi + pdi) + c[r];                 // seq_functions.cpp:84
-                    const T yp = (absd(sv) + sv) * T(0.5);          // seq_functions.cpp:85
-                    if (use_tol) {
-                        const T ui = fmad(omt, s.us[i], th * c[r]);  // u = G_L z (8c form)
-                        s.us[i] = ui;
-                        if (chk) {
-                            const T t = c[r] + pdi;
-                            violh = fmax(violh, t);
-                            magh = fmax(magh, absd(c[r]) + absd(pdi));
-                            wmin = fmin(wmin, wi);
-                            gap -= (double)wi * (double)t;
-                            violz = fmax(violz, ui + pdi);
-                        }
-                    }
-                    s.w[i] = fmad(bnext, yp - yi, yp);               // next 8a
-                    s.ys[i] = yp;
-                }
-            }
-        }
-        if (chk) check_publish<T>(s.slots, violz, violh, wmin, gap, magh);
-        __syncthreads();
-        it = v + 1;
-        if (chk) {
-            const int st1 = check_stage1<T>(s.slots, nwaves, a.L, a.tol, a.tol_gap);
-            bool verified = false;
-            if (st1 & 1) {  // (A) nominated: decide on the direct chain G_L z, reset u to it
-                T vc = neg_inf<T>(), mc = T(0);
-                for (int r0 = 4 * tid; r0 < m; r0 += 4 * kStreamBlock) {
-                    T c[4] = {T(0), T(0), T(0), T(0)};
-                    chain4<T>(GLt, ldm, r0, s.zs, n, c);
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const int i = r0 + r;
-                        if (i < m) {
-                            s.us[i] = c[r];
-                            vc = fmax(vc, c[r] + s.pd[i]);
-                            mc = fmax(mc, absd(c[r]) + absd(s.pd[i]));
-                        }
-                    }
-                }
-                check_publish<T>(s.slots + nwaves, vc, vc, vc, 0.0, mc);
-                __syncthreads();
-                verified = check_verify<T>(s.slots + nwaves, nwaves, a.L, a.tol);
-            }
-            done = check_code(st1, verified);
-            if (!done && a.Hq) {  // value-function branches where the MATLAB test reaches them
-                double vh = -INFINITY, mh = 0.0, wm = INFINITY, gq = 0.0;
-                for (int i = 0; i < nwaves; ++i) {
-                    vh = fmax(vh, s.slots[i].violh);
-                    mh = fmax(mh, s.slots[i].magh);
-                    wm = fmin(wm, s.slots[i].wmin);
-                    gq += s.slots[i].gap;
-                }
-                if (viol_ok(vh, mh, a.L, a.tol, ViolMargin<T>::value))  // uniform
-                    done = stream_value_branch<T>(a, s, MGt, GLt, a.Hq + (size_t)b * a.strideHq, wm >= 0.0,
-                                                  gq * a.L);
-            }
-        }
-        if (done) break;
-    }
-    const T* zout = done >= 2 ? s.zh : s.zs;  // tests (B), (B'), (B'') certify zhat
-    for (int i = tid; i < n; i += kStreamBlock) zg[i] = zout[i];
-    for (int i = tid; i < m; i += kStreamBlock) yg[i] = s.ys[i];
-    if (tid == 0) {
-        a.iters[b] = it;
-        a.conv[b] = done;
-    }
-}
-
-template <typename T>
-hipError_t launch_stream(const SolveArgs<T>& a, hipStream_t st) {
-    const size_t lds = stream_lds_bytes<T>(a.ldn, a.ldm, a.Hq != nullptr);
-    if (lds > 160 * 1024) return hipErrorInvalidValue;
+hipError_t launch_stream(const SolveArgs<T>& a, hipStream_t st, const FarkasArgs* fk) {
+    const size_t lds = stream_lds_bytes<T>(a.ldn, a.ldm, a.Hq != nullptr || fk != nullptr);
+    if (lds > 160 * 1024 || (fk && a.Hq)) return hipErrorInvalidValue;
+    const void* fn = fk ? (const void*)gpad_stream_farkas_kernel<T> : (const void*)gpad_stream_kernel<T>;
     if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void*)gpad_stream_kernel<T>,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL(gpad_stream_kernel<T>, dim3(a.batch), dim3(kStreamBlock), lds, st, a);
+    if (fk)
+        hipLaunchKernelGGL(gpad_stream_farkas_kernel<T>, dim3(a.batch), dim3(kStreamBlock), lds, st, a, *fk);
+    else
+        hipLaunchKernelGGL(gpad_stream_kernel<T>, dim3(a.batch), dim3(kStreamBlock), lds, st, a);
     return hipGetLastError();
 }
-template hipError_t launch_stream<float>(const SolveArgs<float>&, hipStream_t);
-template hipError_t launch_stream<double>(const SolveArgs<double>&, hipStream_t);
+template hipError_t launch_stream<float>(const SolveArgs<float>&, hipStream_t, const FarkasArgs*);
+template hipError_t launch_stream<double>(const SolveArgs<double>&, hipStream_t, const FarkasArgs*);
+
+// r_i = sum_k |G_L[i][k]| of every bound image, fp64, k ascending (the certificate's s term)
+template <typename T>
+__global__ void farkas_rows_kernel(const T* __restrict__ GLt, int n, int m, int ldm, double* __restrict__ rabs) {
+    const T* img = GLt + (size_t)blockIdx.y * n * ldm;
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= ldm) return;
+    double acc = 0.0;
+    if (i < m)
+        for (int k = 0; k < n; ++k) acc += __builtin_fabs((double)img[(size_t)k * ldm + i]);
+    rabs[(size_t)blockIdx.y * ldm + i] = acc;
+}
+hipError_t launch_farkas_rows(const void* GLt, int f64, int n, int m, int ldm, int copies, double* rabs,
+                              hipStream_t s) {
+    const dim3 grid((ldm + 255) / 256, copies);
+    if (f64)
+        hipLaunchKernelGGL(farkas_rows_kernel<double>, grid, dim3(256), 0, s, (const double*)GLt, n, m, ldm, rabs);
+    else
+        hipLaunchKernelGGL(farkas_rows_kernel<float>, grid, dim3(256), 0, s, (const float*)GLt, n, m, ldm, rabs);
+    return hipGetLastError();
+}
 
 }  // namespace gpad

@@ -16,6 +16,7 @@ VERSION_MAJOR, VERSION_MINOR = 0, 6  # include/gpad.h GPAD_VERSION_*: the layout
 GPAD_OK = 0
 ERR_INVALID, ERR_HIP, ERR_NOMEM, ERR_UNSUPPORTED, ERR_NOT_SETUP, ERR_NO_DEVICE = -1, -2, -3, -4, -5, -6
 ERR_DEVICE = -7  # a kernel reported a device-side failure (include/gpad.h)
+CODE_INFEASIBLE = 5  # termination code of an infeasibility certificate (include/gpad.h gpad_setup_infeasibility)
 FLAG_TOL_FLOOR = 1  # gpad_stats_t.flags: tol below the certification floor
 FLAG_NONFINITE_G = 2  # ... g holds a NaN / infinity (tol_floor not finite)
 SCHEDULE_MATLAB, SCHEDULE_PAPER = 0, 1
@@ -47,6 +48,7 @@ EXPORTS = [
     "gpad_setup_signals", "gpad_run_state_signals", "gpad_closed_loop_signals",
     "gpad_class_order", "gpad_setup_classes", "gpad_setup_plant_classes",
     "gpad_class_loop_fused", "gpad_class_loop_deal", "gpad_setup_class_signals",
+    "gpad_setup_infeasibility", "gpad_farkas_margin",
 ]
 GROUP_RCCL, GROUP_PEER = 1, 2
 
@@ -209,6 +211,11 @@ def load(path: str | None = None) -> C.CDLL:
     if hasattr(L, "gpad_setup_class_signals"):  # (added within 0.6; absent from older builds under GPAD_LIB_TOLERANT)
         L.gpad_setup_class_signals.argtypes = [vp, i, i, cvp, cvp, cvp]
         L.gpad_setup_class_signals.restype = i
+    if hasattr(L, "gpad_setup_infeasibility"):  # (added within 0.6; absent from older builds under GPAD_LIB_TOLERANT)
+        L.gpad_setup_infeasibility.argtypes = [vp, d]
+        L.gpad_setup_infeasibility.restype = i
+        L.gpad_farkas_margin.argtypes = [i, i, i, cvp, cvp, cvp, d, C.POINTER(d)]
+        L.gpad_farkas_margin.restype = i
     L.gpad_datafile_read.argtypes = [C.c_char_p, i, C.POINTER(DataFile)]
     L.gpad_datafile_write.argtypes = [C.c_char_p, i, C.POINTER(DataFile)]
     L.gpad_datafile_free.argtypes = [C.POINTER(DataFile)]

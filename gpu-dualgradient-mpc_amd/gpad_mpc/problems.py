@@ -220,6 +220,13 @@ def battery_plant_signals(n_u: int = 4, N: int = 10, **limits):
     return qp, plant
 
 
+def battery_zbound(umax: float = 0.3, umin: float = -0.3, **_limits) -> float:
+    """The bound on |z|_inf that ``GpadSolver.setup_infeasibility`` takes for the battery problems: the
+    input box umin <= u <= umax is part of G, so every feasible z has |z|_inf <= max(|umax|, |umin|).
+    ``limits``: as battery_plant (only the input limits are read)."""
+    return float(max(abs(umax), abs(umin)))
+
+
 def battery_fleet_caps(batch: int, n_u: int, seed: int, spread: float = 0.4) -> np.ndarray:
     """Cell capacities [batch][n_u] in Ah for a fleet of unequal packs: the nominal 0.027 * 4.1 of
     gpad.m:18 times U(1 - spread, 1 + spread), seeded."""

@@ -197,6 +197,16 @@ class GpadSolver:
         unbinds."""
         check(self.lib.gpad_setup_hessian(self.h, _ptr(H) if H is not None else None), "gpad_setup_hessian")
 
+    def setup_infeasibility(self, zbound: float) -> None:
+        """gpad_setup_infeasibility: bind ``zbound`` = R > 0, a bound on |z|_inf over the feasible set
+        (``problems.battery_zbound``), so tol > 0 runs end an infeasible solve early with code
+        ``_lib.CODE_INFEASIBLE`` once its dual iterate certifies that no z of the box meets G z <= g
+        (check it with ``farkas_margin``); 0 unbinds, as does every ``setup*``.  With a bound in force the
+        solves run on the f32 T-wave panels (shared matrices, n, m <= 256) or else the stream kernel, the
+        ``loop_panel`` option and the fused class loop keep their one-launch loops, and ``loop_async`` falls
+        back to lockstep."""
+        check(self.lib.gpad_setup_infeasibility(self.h, float(zbound)), "gpad_setup_infeasibility")
+
     def run(self, z, y, M, g, N: int, tol: float = 0.0, *, stats: bool = True, iters=None,
             scaled: bool = False, theta=None, beta=None, codes=None):
         """Run GPAD in place on z [batch][n] / y [batch][m].  Returns a dict of stats, or None
@@ -205,7 +215,7 @@ class GpadSolver:
         nb = max(1, self.dims.batch if self.dims else 1)
         if iters is not None:
             st.iters = _count_array(iters, "iters", nb)
-        if codes is not None:  # per-instance termination codes 0..4 (host int32 [batch])
+        if codes is not None:  # per-instance termination codes 0..5 (host int32 [batch])
             st.codes = _count_array(codes, "codes", nb)
         want = stats or not _is_torch(z)
         for tab in (theta, beta):  # host tables whatever the memory kind (include/gpad.h)
@@ -537,6 +547,25 @@ class GpadGroup:
         check(self.lib.gpad_group_run(self.g, _ptr(z), _ptr(y), _ptr(M), _ptr(g), int(N), float(tol),
                                       C.byref(st)), "gpad_group_run")
         return GpadSolver._stats_dict(st)
+
+
+def farkas_margin(G, g, y, zbound: float) -> float:
+    """gpad_farkas_margin: -(g'y) - zbound |G'y|_1 in fp64 on host arrays G (m, n), g (m), y (m) of one
+    dtype (float32 or float64); -inf when y has a negative entry.  > 0 exactly when y proves that no z with
+    |z|_inf <= zbound satisfies G z <= g.  Host only: runs without a GPU."""
+    lib = _lib.load()
+    G = np.ascontiguousarray(G)
+    dt = G.dtype if G.dtype in (np.float32, np.float64) else np.float64
+    G = np.ascontiguousarray(G, dt)
+    g = np.ascontiguousarray(g, dt).reshape(-1)
+    y = np.ascontiguousarray(y, dt).reshape(-1)
+    m, n = G.shape
+    if g.size != m or y.size != m:
+        raise ValueError(f"farkas_margin: G is ({m}, {n}), so g and y need {m} entries")
+    out = C.c_double(0.0)
+    check(lib.gpad_farkas_margin(n, m, _dtype_code(G), _ptr(G), _ptr(g), _ptr(y), float(zbound), C.byref(out)),
+          "gpad_farkas_margin")
+    return out.value
 
 
 def schedule(N: int, kind: int = _lib.SCHEDULE_MATLAB):

@@ -37,7 +37,9 @@ extern "C" {
                               * GPAD_OPT_LOOP_PANEL (option 23) and the reported GPAD_KERNEL_LOOP_PANEL (7);
                               * gpad_class_order, gpad_setup_classes, gpad_setup_plant_classes;
                               * gpad_class_loop_fused, gpad_class_loop_deal and the reported
-                              * GPAD_KERNEL_LOOP_CLASSES (8); gpad_setup_class_signals */
+                              * GPAD_KERNEL_LOOP_CLASSES (8); gpad_setup_class_signals;
+                              * gpad_setup_infeasibility, gpad_farkas_margin and the termination code
+                              * GPAD_CODE_INFEASIBLE (5), returned only with a bound in force */
 
 /* status codes */
 #define GPAD_OK 0
@@ -112,7 +114,8 @@ typedef struct gpad_stats {
     int* codes;                  /* optional caller array (host) or NULL, sized as iters:
                                   * [batch]; gpad_closed_loop: [steps][batch].  Per-instance
                                   * termination code, 0 = ran to N, 1..4 = the test that
-                                  * stopped it (gpad_run)                                   */
+                                  * stopped it (gpad_run), 5 = GPAD_CODE_INFEASIBLE
+                                  * (gpad_setup_infeasibility)                               */
 } gpad_stats_t;
 
 /* gpad_stats_t.flags */
@@ -175,6 +178,60 @@ int gpad_setup_flat(gpad_handle_t h, const gpad_dims_t* dims, int n_u, const flo
  * H = NULL unbinds.  gpad_setup / gpad_setup_scaled unbind as well.
  * Replaces acceldualgrad.m's own H (the MATLAB function receives H, :1). */
 int gpad_setup_hessian(gpad_handle_t h, const void* H);
+
+/* ---- infeasibility certificates ------------------------------------------------------------------
+ * An infeasible QP (no z with G z <= g) never meets Algorithm 1: max(G z - g) stalls at a positive
+ * constant, |y| grows without bound and the solve runs to N and returns code 0, which a caller cannot
+ * tell from a slow one.  The dual iterate is its own Farkas certificate: for y >= 0 and any z with
+ * |z|_inf <= R,  y'(G z - g) >= -(g'y) - R |G'y|_1,  so  g'y + R |G'y|_1 < 0  proves that no z of the box
+ * satisfies G z <= g.  G'y stays bounded while -g'y grows, so on an infeasible QP the test passes eventually.
+ *
+ * gpad_setup_infeasibility binds R = zbound > 0, the caller's bound on |z|_inf over the feasible set (the
+ * battery problem: R = umax, the input box being part of G); zbound == 0 unbinds; zbound < 0 or not finite:
+ * GPAD_ERR_INVALID; before gpad_setup*: GPAD_ERR_NOT_SETUP; every gpad_setup* unbinds, as for the Hessian.  On
+ * a class-bound handle the binding is forwarded to every class.  It takes effect only in runs with tol > 0
+ * (tol <= 0 runs exactly N iterations whatever is bound).
+ *
+ * The rule (one text: csrc/gpad_farkas.h), with K = dims.check_every:
+ *   events     the test events at which the solve's iteration count v is a multiple of 4 K.  Stateless:
+ *              nothing is kept between events.  Algorithm 1 is evaluated first and any code of its wins.
+ *   nomination q = sum_i (double)y+_i (double)pD_i over the live rows, in the test's own reduction and in the
+ *              order of its gap term; y+ is this iteration's projected iterate (>= 0, and what the solve
+ *              returns as y*), pD = -g/L as the device holds it.  Nominated iff q > 0, i.e. g'y+ < 0.
+ *   decision   fp64, on the device's G_L = G/L, pD and y+, sums ascending, products and sums unfused:
+ *              t_j = sum_i y_i G_L[i][j], a = sum_j |t_j|, p = sum_i |y_i pD_i|, s = sum_i y_i r_i with
+ *              r_i = sum_j |G_L[i][j]| (fp64, j ascending: the stream kernel reads them from a table made
+ *              at bind time per matrix copy, the panels sum them from their own image of G_L at a decision --
+ *              the same numbers either way).  Infeasible iff
+ *              q - R a > mu (p + R s), mu = 16 units of 2^-24 (f32) / 2^-53 (f64) as the violation margin
+ *              of gpad_run: it covers the roundings of G/L and -g/L and the fp64 sums.
+ *   result     code GPAD_CODE_INFEASIBLE, z* = z (as the cap exit returns), y* = y+, the iteration count.
+ *              A failed decision changes nothing.
+ * Postcondition (the contract): for every instance that returns code 5, gpad_farkas_margin > 0 on the
+ * caller's own G, g and the returned y.
+ * Stats: code 5 counts as not converged in every aggregate; codes[] carries the 5.  A closed-loop step that
+ * ends with code 5 applies u = z*[0:nu] as a capped step does, and the loop goes on.
+ *
+ * Engines.  Three kernels carry the branch: gpad_stream_kernel (f32 and f64, any shape, shared or distinct
+ * matrices), the f32 T-wave MFMA panel (shared matrices, n, m <= 256: every T <= 16, phased compaction as ever --
+ * a code-5 instance leaves the panel like a converged one -- no pair layout, no finisher) and the panel loop
+ * (GPAD_OPT_LOOP_PANEL and gpad_class_loop_fused: a code-5 column takes its step boundary like any finished
+ * column).  All give the same z, y, counts and codes.  With a bound in force (bound, and tol > 0):
+ *   - dims.kernel AUTO and GPAD_KERNEL_PANEL run those panels where they apply; AUTO else the stream kernel
+ *     (f64, distinct matrices, n or m > 256), whatever the batch -- the resident kernel, the pairs, the finisher,
+ *     the big panels and the f64 panels are not used;
+ *   - GPAD_OPT_LOOP_ASYNC falls back to the lockstep loop, silently as for any shape it does not take;
+ *   - GPAD_ERR_UNSUPPORTED: a forced GPAD_KERNEL_RESIDENT; a forced GPAD_KERNEL_PANEL where those panels do not
+ *     apply; gpad_run_scaled with caller theta / beta tables.  Binding on a flat setup, binding with a Hessian
+ *     bound and gpad_setup_hessian with a bound are GPAD_ERR_UNSUPPORTED at the bind.  gpad_group_* has no
+ *     binding. */
+#define GPAD_CODE_INFEASIBLE 5
+int gpad_setup_infeasibility(gpad_handle_t h, double zbound);
+/* host only, no device: *margin = -(g'y) - zbound |G'y|_1 in fp64 on the caller's arrays (G m x n row-major,
+ * g and y of m; dtype GPAD_DTYPE_*), -inf when some y_i is negative (or NaN).  > 0 exactly when y certifies
+ * that no z with |z|_inf <= zbound satisfies G z <= g: an independent check of a code 5. */
+int gpad_farkas_margin(int n, int m, int dtype, const void* G, const void* g, const void* y, double zbound,
+                       double* margin);
 
 /* Run GPAD on the bound problem for every instance of the batch.
  *   z0: in z_{-1}, out z*      [batch][n]   (acceldualgrad.m:17, :83)

@@ -4,8 +4,8 @@ tensors.  C1 plant (battery_plant(4, 10): n = 40, m = 180), 20 MPC steps, batche
 modes: eps cold / eps warm (tol 1e-4, N 3000) and fixed N = 100.
 
   python tools/loop_ab.py [--rounds 3] [--steps 20] [--batches 1 64 256 512 2048 8192] [--fleet | --signals]
-                          [--panel]
-  python tools/loop_ab.py --classes K [--signals] [--rounds 3] [--steps 20] [--batches 256 2048 8192]
+                          [--panel] [--infeas]
+  python tools/loop_ab.py --classes K [--signals] [--infeas] [--rounds 3] [--steps 20] [--batches 256 2048 8192]
 
 --panel: a third variant, "panel" (GPAD_OPT_LOOP_PANEL, csrc/gpad_loop_panel.hip: the one-launch loop on the
 MFMA panels), alternated with lockstep and async in the same process and checked against lockstep like
@@ -49,6 +49,21 @@ is then also run without signals in the same process (a second set of handles, c
 "fleet" first); `sig_over_plain` is the rate with signals over the rate without, per variant -- what the
 S gather and the wider state rows cost (informational: the signals change the QPs, so also the counts; the
 fleet's own ratio beside it shows that part).
+
+--infeas (without --classes; with --signals the loads make infeasible steps): the variant "infeas" ("sig_infeas"
+with --signals), the lockstep loop with the battery bound bound (setup_infeasibility(problems.battery_zbound())),
+and with --panel "infeas_panel" ("sig_infeas_panel"), the panel loop with it; they are compared with each other
+bit for bit (outputs, counts, codes) instead of with the unbound loop, and every line gains `share_code5`,
+`share_capped`, `infeas_mean_iters_per_solve` and `<bound variant>_over_<variant>`.
+
+--classes K [--signals] --infeas: two more variants with the battery bound bound
+(setup_infeasibility(problems.battery_zbound()), gpad_setup_infeasibility): "classes_infeas", the class binding
+with the options off (lockstep, the certificate panels), and "classes_fused_infeas", the fused class loop.  With a
+tolerance their solves end an infeasible step with code 5, so their outputs are not the fleet's: they are left
+out of that bit-for-bit check and compared with each other instead (outputs, counts, codes); every line gains
+`share_code5` -- per variant the share of (step, pack) codes equal to 5 -- `share_capped` (code 0 at N
+iterations), `infeas_mean_iters_per_solve` / `infeas_max_iters_per_solve` and `<bound variant>_over_<variant>`
+for every unbound variant.
 
 Per batch and mode the two variants' x, z, y, xs, us and per-step iteration counts are compared first
 (that run is also each variant's warm-up); a mismatch aborts the batch.  Then `rounds` rounds
@@ -96,9 +111,10 @@ def classes_ab(args):
                       "steps": steps, "rounds": rounds, "device": torch.cuda.get_device_name(0),
                       "cus": torch.cuda.get_device_properties(0).multi_processor_count}))
     names = ("fleet", "classes", "classes_panel", "classes_async", "classes_fused") + (
-        ("shared", "shared_panel") if K == 1 else ())
+        ("shared", "shared_panel") if K == 1 else ()) + (("classes_infeas", "classes_fused_infeas") if args.infeas else ())
     want = {"classes_panel": "loop_panel", "classes_async": "loop", "classes_fused": "loop_classes",
-            "shared_panel": "loop_panel"}
+            "shared_panel": "loop_panel", "classes_fused_infeas": "loop_classes"}
+    INF = ("classes_infeas", "classes_fused_infeas")
     for B in args.batches:
         class_of = np.arange(B, dtype=np.int32) % K
         X0 = torch.from_numpy((np.random.default_rng(B).random((B, nx)) - 0.5).astype(np.float32)).to(dev)
@@ -133,7 +149,9 @@ def classes_ab(args):
                     if with_sig:
                         s.setup_class_signals(cls["SM"], cls["Sg"], cls["E"])
                     s.set_options(loop_panel=int(name == "classes_panel"), loop_async=int(name == "classes_async"))
-                    s.set_class_loop_fused(name == "classes_fused")
+                    s.set_class_loop_fused(name in ("classes_fused", "classes_fused_infeas"))
+                    if name in INF:
+                        s.setup_infeasibility(problems.battery_zbound())
                 buf = dict(x=torch.empty(B, nx, device=dev), z=torch.empty(B, n, device=dev),
                            y=torch.empty(B, m, device=dev), xs=torch.empty(steps, B, nx, device=dev),
                            us=torch.empty(steps, B, nu, device=dev))
@@ -154,14 +172,22 @@ def classes_ab(args):
 
         def measure(vs, mname, mode):
             """The output check (each variant's warm-up), then `rounds` alternated rounds: (its, kern, ms,
-            wall), or None after reporting a mismatch."""
-            its, kern = {}, {}
+            wall, codes), or None after reporting a mismatch."""
+            its, kern, cds = {}, {}, {}
             for name in vs:
-                its[name] = np.zeros(steps * B, np.int32)
-                kern[name] = enqueue(vs, name, mode, iters=its[name])["kernel"]
-            bad = [f"{v}.{k}" for k in ("x", "z", "y", "xs", "us") for v in vs if v != "fleet"
+                its[name], cds[name] = np.zeros(steps * B, np.int32), np.zeros(steps * B, np.int32)
+                kern[name] = enqueue(vs, name, mode, iters=its[name], codes=cds[name])["kernel"]
+            same = [v for v in vs if v not in INF]  # (the certificate changes results by design)
+            bad = [f"{v}.{k}" for k in ("x", "z", "y", "xs", "us") for v in same if v != "fleet"
                    if not torch.equal(vs["fleet"][1][k].view(torch.int32), vs[v][1][k].view(torch.int32))]
-            bad += [f"{v}.iters" for v in vs if not np.array_equal(its["fleet"], its[v])]
+            bad += [f"{v}.iters" for v in same if not np.array_equal(its["fleet"], its[v])]
+            if "classes_infeas" in vs:  # the two bound variants agree with each other, bit for bit
+                bad += [f"infeas.{k}" for k in ("x", "z", "y", "xs", "us")
+                        if not torch.equal(vs[INF[0]][1][k].view(torch.int32), vs[INF[1]][1][k].view(torch.int32))]
+                if not (np.array_equal(its[INF[0]], its[INF[1]]) and np.array_equal(cds[INF[0]], cds[INF[1]])):
+                    bad.append("infeas.counts")
+                if mode["tol"] > 0 and kern["classes_infeas"] not in ("panel", "stream"):
+                    bad.append("classes_infeas.kernel")
             if bad or any(kern[v] is None or (kern[v] in ("loop", "loop_panel", "loop_classes")) != (v in want) or
                           (v in want and kern[v] != want[v]) for v in vs):
                 print(json.dumps({"batch": B, "mode": mname, "error": "outputs differ" if bad else "wrong kernel",
@@ -177,13 +203,13 @@ def classes_ab(args):
                     s.sync()
                     wall[name].append((time.perf_counter() - t0) * 1e3)
                     ms[name].append(s.last_stats()["kernel_ms"])
-            return its, kern, ms, wall
+            return its, kern, ms, wall, cds
 
         for mname, mode in MODES.items():
             res = measure(var, mname, mode)
             if res is None:
                 break
-            its, kern, ms, wall = res
+            its, kern, ms, wall, cds = res
             med = {k: float(np.median(v)) for k, v in ms.items()}
             rate = {k: B * steps / (med[k] / 1e3) for k in var}
             faster = lambda v, ref: (v if max(ms[v]) < min(ms[ref]) else  # noqa: E731
@@ -214,6 +240,12 @@ def classes_ab(args):
                    if "shared_panel" in var else {}),
                 **({"classes_over_shared": round(rate["classes"] / rate["shared"], 3),
                     "classes_vs_shared_faster": faster("classes", "shared")} if "shared" in var else {}),
+                **({"share_code5": {k: round(float((cds[k] == 5).mean()), 4) for k in var},
+                    "share_capped": {k: round(float(((cds[k] == 0) & (its[k] == mode["N"])).mean()), 4) for k in var},
+                    "infeas_mean_iters_per_solve": round(float(its["classes_infeas"].mean()), 1),
+                    "infeas_max_iters_per_solve": int(its["classes_infeas"].max()),
+                    **{f"{i}_over_{v}": round(rate[i] / rate[v], 3) for i in INF for v in var if v not in INF}}
+                   if args.infeas else {}),
                 **extra}),
                 flush=True)
         for s, _ in list(var.values()) + list((plain or {}).values()):
@@ -229,6 +261,7 @@ def main():
     ap.add_argument("--signals", action="store_true")
     ap.add_argument("--panel", action="store_true")
     ap.add_argument("--classes", type=int, default=0, metavar="K")
+    ap.add_argument("--infeas", action="store_true")
     args = ap.parse_args()
     if args.classes:
         if args.fleet or args.panel or args.classes < 1:
@@ -267,6 +300,10 @@ def main():
             dML, dG, dPM, dPg, dg0, dA, dB = (t32(a) for a in (qp.ML, qp.G, pl.PM, pl.Pg, pl.g0, pl.A, pl.B))
         var = {}
         sig = None
+        # --infeas: the lockstep loop (and with --panel the panel loop) with the battery bound bound, on the plant
+        # with signals when --signals is given (its loads make infeasible steps), else on the plain plant
+        pre = "sig_" if args.signals else ""
+        infeas_names = ((pre + "infeas",) + ((pre + "infeas_panel",) if args.panel else ())) if args.infeas else ()
         if args.signals:
             rng = np.random.default_rng([B, 1])
             sig = torch.from_numpy(np.concatenate([rng.uniform(-5, 5, (steps, B, 1)),
@@ -274,7 +311,7 @@ def main():
                                                   axis=-1).astype(np.float32)).to(dev)
         for name in ("lockstep", "async") + (("async_1wg",) if args.fleet and not mismatch else ()) + (
                 ("panel",) if args.panel else ()) + (("sig_lockstep", "sig_async") if args.signals else ()) + (
-                ("sig_panel",) if args.signals and args.panel else ()):
+                ("sig_panel",) if args.signals and args.panel else ()) + infeas_names:
             s = gpad_mpc.GpadSolver(0)
             s.setup(dML, dG, float(np.float32(qp.L)), n=n, m=m, batch=B, shared=mismatch or not args.fleet)
             s.setup_plant(dPM, dPg, g0=dg0, A=dA, B=dB)
@@ -283,6 +320,8 @@ def main():
             s.set_option("loop_async", int("async" in name))
             if args.panel:  # (left alone otherwise: the tool also runs on builds older than the option)
                 s.set_option("loop_panel", int(name.endswith("panel")))
+            if name in infeas_names:
+                s.setup_infeasibility(problems.battery_zbound())
             if name == "async_1wg":
                 s.set_option("duo_max_grid", cus)
             buf = dict(x=torch.empty(B, nx, device=dev), z=torch.empty(B, n, device=dev),
@@ -300,14 +339,17 @@ def main():
                                  xs=b["xs"], us=b["us"], signals=sig if name.startswith("sig_") else None, **kw)
 
         for mname, mode in MODES.items():
-            its, kern = {}, {}
+            its, kern, cds = {}, {}, {}
             for name in var:  # the output check, and each variant's warm-up
-                its[name] = np.zeros(steps * B, np.int32)
-                kern[name] = enqueue(name, mode, iters=its[name])["kernel"]
-            base = lambda v: "sig_lockstep" if v.startswith("sig_") else "lockstep"  # noqa: E731
+                its[name], cds[name] = np.zeros(steps * B, np.int32), np.zeros(steps * B, np.int32)
+                kern[name] = enqueue(name, mode, iters=its[name], codes=cds[name])["kernel"]
+            # (a bound variant's outputs are not the unbound loop's by design: the bound variants are compared
+            # with the first of them)
+            base = lambda v: (infeas_names[0] if v in infeas_names else  # noqa: E731
+                              "sig_lockstep" if v.startswith("sig_") else "lockstep")
             bad = [k for k in ("x", "z", "y", "xs", "us") for v in var if v != base(v)
                    if not torch.equal(var[base(v)][1][k].view(torch.int32), var[v][1][k].view(torch.int32))]
-            if any(not np.array_equal(its[base(v)], its[v]) for v in var):
+            if any(not np.array_equal(its[base(v)], its[v]) or not np.array_equal(cds[base(v)], cds[v]) for v in var):
                 bad.append("iters")
             want = lambda v: "loop_panel" if v.endswith("panel") else "loop"  # noqa: E731
             if bad or any((kern[v] == want(v)) != (v != base(v)) or kern[v] is None for v in var):
@@ -344,6 +386,11 @@ def main():
                    if args.panel else {}),
                 **({"sig_panel_over_sig_lockstep": round(rate["sig_panel"] / rate["sig_lockstep"], 3)}
                    if args.panel and args.signals else {}),
+                **({"share_code5": {k: round(float((cds[k] == 5).mean()), 4) for k in var},
+                    "share_capped": {k: round(float(((cds[k] == 0) & (its[k] == mode["N"])).mean()), 4) for k in var},
+                    "infeas_mean_iters_per_solve": round(float(its[infeas_names[0]].mean()), 1),
+                    **{f"{i}_over_{v}": round(rate[i] / rate[v], 3) for i in infeas_names for v in var
+                       if v not in infeas_names and v.startswith("sig_") == bool(pre)}} if args.infeas else {}),
                 **({"sig_mean_iters_per_solve": round(float(its["sig_async"].mean()), 1),
                     "sig_async_over_sig_lockstep": round(rate["sig_async"] / rate["sig_lockstep"], 3),
                     "sig_over_plain": {"lockstep": round(rate["sig_lockstep"] / rate["lockstep"], 3),
