@@ -364,6 +364,7 @@ __device__ __forceinline__ float chain_regs(const float (&r)[K], const float* v)
 constexpr int kResidentMaxThreads = 512;
 static_assert(kResidentMaxThreads / 64 <= 8, "check_stage1 / check_verify reduce one slot per lane over lanes 0..7");
 constexpr int kResidentMaxRow = 208;
+constexpr int kFlatMaxCells = 16;  // the flat resident variant's cells n_u (gpad_resident.hip)
 
 // chain-length buckets (multiples of 32 up to 192, then 200 and the 208 cap)
 inline int res_bucket(int len) {

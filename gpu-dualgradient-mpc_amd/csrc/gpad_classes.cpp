@@ -152,7 +152,7 @@ static int apply_tuning(gpad_handle_t c, const Tuning& t) {
         const int rc = gpad_set_option(c, o.id, v == def.*o.field ? GPAD_OPT_DEFAULT : o.inverted ? 1 - v : v);
         if (rc) return rc;
     }
-    return GPAD_OK;
+    return gpad_infeasibility_resident(c, t.fk_resident);  // (a handle setting that is no option)
 }
 
 static int setup_body(ClassBinding* cb, const Tuning& tune, const void* ML, const void* G, double L) {
@@ -268,6 +268,15 @@ int classes_set_option(ClassBinding* cb, int option, int value) {
         if (rc) return rc;
     }
     if (cb->fused) return gpad_set_option(cb->fused, option, value);  // (GPAD_OPT_PANEL_MAX_GRID caps its grid)
+    return GPAD_OK;
+}
+
+int classes_infeasibility_resident(ClassBinding* cb, int on) {
+    for (gpad_handle_t c : cb->child) {
+        if (!c) continue;
+        if (const int rc = gpad_infeasibility_resident(c, on)) return rc;
+    }
+    if (cb->fused) return gpad_infeasibility_resident(cb->fused, on);  // (its loop keeps its own kernel)
     return GPAD_OK;
 }
 

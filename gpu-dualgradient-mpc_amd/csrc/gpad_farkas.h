@@ -13,9 +13,10 @@
 //     infeasible  <=>  q - R a > mu (p + R s),  mu = ViolMargin (16 units of 2^-24 / 2^-53): the roundings of
 //     G/L and -g/L and the fp64 sums, so the certificate holds on the caller's own G, g (gpad_farkas_margin).
 // Code 5 returns z* = z (as the cap exit), y* = y+ and the iteration count.  The rule keeps no state between
-// events.  Three kernels carry it, each as a second variant of its one text: gpad_stream_farkas_kernel,
-// gpad_panel_farkas_kernel, gpad_loop_panel_farkas_kernel.  Kernels without it never see a bound: the host routes
-// (gpad_run.cpp launch_solve, gpad_state.cpp).
+// events.  Four kernels carry it, each as a second variant of its one text: gpad_stream_farkas_kernel,
+// gpad_panel_farkas_kernel, gpad_loop_panel_farkas_kernel, gpad_resident_farkas_kernel (opt-in per handle,
+// gpad_infeasibility_resident).  Kernels without it never see a bound: the host routes (gpad_run.cpp launch_solve,
+// gpad_state.cpp).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -34,6 +35,9 @@ struct FarkasArgs {
 
 // r[i] = sum_k |GLt[k ldm + i]| (k ascending, fp64) for every image: GLt k-major [n][ldm] per copy
 hipError_t launch_farkas_rows(const void* GLt, int f64, int n, int m, int ldm, int copies, double* rabs, hipStream_t s);
+// gpad_resident_farkas.hip: one launch of the (ka, kb) bucket pair's gpad_resident_farkas_kernel (launch_resident)
+hipError_t launch_resident_farkas(const SolveArgs<float>& a, const FarkasArgs& fk, int ka, int kb, int threads,
+                                  hipStream_t s);
 
 #ifdef __HIPCC__
 // The decision for a workgroup that holds y+ and pD of one instance in LDS.  Every thread calls it with the

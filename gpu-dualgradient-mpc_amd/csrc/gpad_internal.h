@@ -37,6 +37,8 @@ struct Tuning {
     int p64_no_refill = 0;    // GPAD_OPT_P64_REFILL = 0: f64 panels without column refills
     int loop_async = 0;       // GPAD_OPT_LOOP_ASYNC: gpad_closed_loop in one launch, packs step on their own
     int loop_panel = 0;       // GPAD_OPT_LOOP_PANEL: gpad_closed_loop in one launch on the MFMA panels
+    int fk_resident = 0;      // gpad_infeasibility_resident (an entry point, no GPAD_OPT_*): with a bound in force
+                              // the resident kernel carries the certificate where unbound runs take that kernel
 };
 
 // Device error word of a run (SolveArgs::err): kernels OR these bits in with a vector atomic;
@@ -148,7 +150,8 @@ struct SolveArgs {
 struct FarkasArgs;
 template <typename T>
 hipError_t launch_stream(const SolveArgs<T>& a, hipStream_t s, const FarkasArgs* fk = nullptr);
-hipError_t launch_resident(const SolveArgs<float>& a, hipStream_t s, bool* supported);
+// fk: the non-flat kernel's variant with the infeasibility certificate (gpad_resident_farkas.hip), or null
+hipError_t launch_resident(const SolveArgs<float>& a, hipStream_t s, bool* supported, const FarkasArgs* fk = nullptr);
 // two-instance ping-pong kernel over a work list (shared matrices; gpad_duo.hip): the
 // list is idx_in/count_in (a no-op unless *count_in <= a.fin_thresh) or 0..batch-1; needs a
 // zeroed a.qctr.  Persistent grid of `grid` workgroups (one per CU).

@@ -156,13 +156,28 @@ int launch_solve(gpad_handle_t h, T* dz, T* dy, const T* dM, const T* dg, int N,
     // The infeasibility certificate (gpad_setup_infeasibility) is carried by the stream kernel and by the f32
     // T-wave panels (shared matrices, n, m <= 256).  With a bound in force (tol > 0) AUTO and PANEL run those
     // panels where they apply -- no pair layout, no finisher -- AUTO else the stream kernel, and a forced engine
-    // without the branch is refused rather than run without it
+    // without the branch is refused rather than run without it.  On a handle with gpad_infeasibility_resident on,
+    // the resident kernel carries it too (f32, n, m <= 208): forced, and by AUTO exactly where unbound AUTO runs
+    // the resident kernel -- distinct matrices at any batch, shared ones up to 4 instances per CU
     const bool fk_on = h->zbound > 0.0 && tol > 0.0;
     const gpad::FarkasArgs fk{(const double*)h->frows.p, d.shared ? 0 : (long long)h->ldm, h->zbound};
     if (fk_on) {
+        if constexpr (sizeof(T) == sizeof(float)) {
+            if (h->tune.fk_resident && (kernel == GPAD_KERNEL_RESIDENT ||
+                                        (kernel == GPAD_KERNEL_AUTO && gpad::resident_supported(n, m) &&
+                                         !(d.shared && batch > 4 * h->num_cus)))) {
+                bool rok = false;
+                e = gpad::launch_resident(a, h->stream, &rok, &fk);
+                if (e != hipSuccess) return fail(GPAD_ERR_HIP, std::string("resident: ") + hipGetErrorString(e));
+                if (!rok) return fail(GPAD_ERR_UNSUPPORTED, "resident kernel: needs n, m <= 208");
+                *kernel_out = GPAD_KERNEL_RESIDENT;
+                return finish(GPAD_OK);
+            }
+        }
         if (kernel == GPAD_KERNEL_RESIDENT)
             return fail(GPAD_ERR_UNSUPPORTED, "the infeasibility certificate (gpad_setup_infeasibility) runs on the "
-                                              "stream kernel and the f32 T-wave panels, not on the resident kernel");
+                                              "stream kernel and the f32 T-wave panels, not on the resident kernel "
+                                              "(f32 handles: gpad_infeasibility_resident)");
         bool pok = false;
         if constexpr (sizeof(T) == sizeof(float)) {
             if (kernel != GPAD_KERNEL_STREAM && d.shared && h->frag_ok) {

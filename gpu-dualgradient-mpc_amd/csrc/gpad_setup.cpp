@@ -255,6 +255,19 @@ int gpad_setup_infeasibility(gpad_handle_t h, double zbound) {
     });
 }
 
+// A handle setting, kept in Tuning beside the options: it survives every setup and unbinding, and a class binding
+// hands it to its children as it hands them the options (gpad_classes.cpp apply_tuning, classes_set_option's way)
+int gpad_infeasibility_resident(gpad_handle_t h, int on) {
+    return gpad::abi_guard("gpad_infeasibility_resident", [&]() -> int {
+        if (!h) return fail(GPAD_ERR_INVALID, "gpad_infeasibility_resident: null handle");
+        if (on != 0 && on != 1) return fail(GPAD_ERR_INVALID, "gpad_infeasibility_resident: on must be 0 or 1");
+        h->tune.fk_resident = on;
+        if (!h->cls) return GPAD_OK;
+        HIP_TRY(hipSetDevice(h->device));
+        return gpad::classes_infeasibility_resident(h->cls, on);
+    });
+}
+
 // -(g'y) - R |G'y|_1 in fp64 on host arrays (no device): > 0 exactly when y >= 0 proves that no z with
 // |z|_inf <= R satisfies G z <= g; -inf when y has a negative entry (or a NaN)
 int gpad_farkas_margin(int n, int m, int dtype, const void* G, const void* g, const void* y, double zbound,

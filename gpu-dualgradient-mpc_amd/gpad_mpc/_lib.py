@@ -48,7 +48,7 @@ EXPORTS = [
     "gpad_setup_signals", "gpad_run_state_signals", "gpad_closed_loop_signals",
     "gpad_class_order", "gpad_setup_classes", "gpad_setup_plant_classes",
     "gpad_class_loop_fused", "gpad_class_loop_deal", "gpad_setup_class_signals",
-    "gpad_setup_infeasibility", "gpad_farkas_margin",
+    "gpad_setup_infeasibility", "gpad_farkas_margin", "gpad_infeasibility_resident",
 ]
 GROUP_RCCL, GROUP_PEER = 1, 2
 
@@ -216,6 +216,9 @@ def load(path: str | None = None) -> C.CDLL:
         L.gpad_setup_infeasibility.restype = i
         L.gpad_farkas_margin.argtypes = [i, i, i, cvp, cvp, cvp, d, C.POINTER(d)]
         L.gpad_farkas_margin.restype = i
+    if hasattr(L, "gpad_infeasibility_resident"):  # (added within 0.6; absent from older builds under GPAD_LIB_TOLERANT)
+        L.gpad_infeasibility_resident.argtypes = [vp, i]
+        L.gpad_infeasibility_resident.restype = i
     L.gpad_datafile_read.argtypes = [C.c_char_p, i, C.POINTER(DataFile)]
     L.gpad_datafile_write.argtypes = [C.c_char_p, i, C.POINTER(DataFile)]
     L.gpad_datafile_free.argtypes = [C.POINTER(DataFile)]

@@ -204,8 +204,17 @@ class GpadSolver:
         (check it with ``farkas_margin``); 0 unbinds, as does every ``setup*``.  With a bound in force the
         solves run on the f32 T-wave panels (shared matrices, n, m <= 256) or else the stream kernel, the
         ``loop_panel`` option and the fused class loop keep their one-launch loops, and ``loop_async`` falls
-        back to lockstep."""
+        back to lockstep.  ``set_infeasibility_resident`` lets the resident kernel carry the certificate."""
         check(self.lib.gpad_setup_infeasibility(self.h, float(zbound)), "gpad_setup_infeasibility")
+
+    def set_infeasibility_resident(self, on: bool) -> None:
+        """gpad_infeasibility_resident: with a bound in force (``setup_infeasibility``, tol > 0) the f32 resident
+        kernel carries the certificate where it applies (n, m <= 208): ``kernel=KERNEL_RESIDENT`` runs instead of
+        raising, and AUTO takes the resident kernel where it takes it without a bound -- distinct matrices, or
+        shared ones with batch <= 4 per CU -- lockstep loops and class bindings included (reported kernel
+        "resident").  Results are bit for bit the same.  Off by default; a handle setting like an option: it
+        survives ``setup*`` and unbinding, and a class binding forwards it to every class."""
+        check(self.lib.gpad_infeasibility_resident(self.h, 1 if on else 0), "gpad_infeasibility_resident")
 
     def run(self, z, y, M, g, N: int, tol: float = 0.0, *, stats: bool = True, iters=None,
             scaled: bool = False, theta=None, beta=None, codes=None):

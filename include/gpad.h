@@ -39,7 +39,8 @@ extern "C" {
                               * gpad_class_loop_fused, gpad_class_loop_deal and the reported
                               * GPAD_KERNEL_LOOP_CLASSES (8); gpad_setup_class_signals;
                               * gpad_setup_infeasibility, gpad_farkas_margin and the termination code
-                              * GPAD_CODE_INFEASIBLE (5), returned only with a bound in force */
+                              * GPAD_CODE_INFEASIBLE (5), returned only with a bound in force;
+                              * gpad_infeasibility_resident (off by default: no routing changes) */
 
 /* status codes */
 #define GPAD_OK 0
@@ -212,21 +213,38 @@ int gpad_setup_hessian(gpad_handle_t h, const void* H);
  * Stats: code 5 counts as not converged in every aggregate; codes[] carries the 5.  A closed-loop step that
  * ends with code 5 applies u = z*[0:nu] as a capped step does, and the loop goes on.
  *
- * Engines.  Three kernels carry the branch: gpad_stream_kernel (f32 and f64, any shape, shared or distinct
+ * Engines.  Four kernels carry the branch: gpad_stream_kernel (f32 and f64, any shape, shared or distinct
  * matrices), the f32 T-wave MFMA panel (shared matrices, n, m <= 256: every T <= 16, phased compaction as ever --
- * a code-5 instance leaves the panel like a converged one -- no pair layout, no finisher) and the panel loop
+ * a code-5 instance leaves the panel like a converged one -- no pair layout, no finisher), the panel loop
  * (GPAD_OPT_LOOP_PANEL and gpad_class_loop_fused: a code-5 column takes its step boundary like any finished
- * column).  All give the same z, y, counts and codes.  With a bound in force (bound, and tol > 0):
+ * column) and, opt-in per handle (gpad_infeasibility_resident below), the f32 resident kernel (n, m <= 208,
+ * shared or distinct matrices).  All give the same z, y, counts and codes.  With a bound in force (bound, and
+ * tol > 0):
  *   - dims.kernel AUTO and GPAD_KERNEL_PANEL run those panels where they apply; AUTO else the stream kernel
- *     (f64, distinct matrices, n or m > 256), whatever the batch -- the resident kernel, the pairs, the finisher,
- *     the big panels and the f64 panels are not used;
+ *     (f64, distinct matrices, n or m > 256), whatever the batch -- the pairs, the finisher, the big panels and
+ *     the f64 panels are not used, nor by default the resident kernel;
  *   - GPAD_OPT_LOOP_ASYNC falls back to the lockstep loop, silently as for any shape it does not take;
- *   - GPAD_ERR_UNSUPPORTED: a forced GPAD_KERNEL_RESIDENT; a forced GPAD_KERNEL_PANEL where those panels do not
- *     apply; gpad_run_scaled with caller theta / beta tables.  Binding on a flat setup, binding with a Hessian
- *     bound and gpad_setup_hessian with a bound are GPAD_ERR_UNSUPPORTED at the bind.  gpad_group_* has no
- *     binding. */
+ *   - GPAD_ERR_UNSUPPORTED: a forced GPAD_KERNEL_RESIDENT (by default); a forced GPAD_KERNEL_PANEL where those
+ *     panels do not apply; gpad_run_scaled with caller theta / beta tables.  Binding on a flat setup, binding
+ *     with a Hessian bound and gpad_setup_hessian with a bound are GPAD_ERR_UNSUPPORTED at the bind.
+ *     gpad_group_* has no binding.
+ *
+ * gpad_infeasibility_resident(h, 1): with a bound in force the resident kernel carries the certificate where
+ * it applies.  On an f32 handle a forced GPAD_KERNEL_RESIDENT then runs (n or m > 208: GPAD_ERR_UNSUPPORTED as
+ * without a bound) and AUTO takes the resident kernel exactly where it takes it without a bound -- n, m <= 208
+ * and distinct matrices at any batch, or shared matrices with batch <= 4 per CU; above that AUTO runs the
+ * T-wave panels as before.  Both report GPAD_KERNEL_RESIDENT.  The lockstep loops (gpad_run_state,
+ * gpad_closed_loop and their _signals forms, and what GPAD_OPT_LOOP_ASYNC falls back to) follow, a class
+ * binding per class; GPAD_OPT_LOOP_PANEL and gpad_class_loop_fused keep their kernels, and forced
+ * GPAD_KERNEL_PANEL / GPAD_KERNEL_STREAM, f64 handles and the refusals above stay as they are.  Results are bit
+ * for bit those of the other engines.  on = 0 (the default) restores the routing above; any other value, or a
+ * NULL handle: GPAD_ERR_INVALID.  Valid any time after gpad_create.  A handle setting like an option: it
+ * survives gpad_setup*, gpad_setup_infeasibility and unbinding, changes nothing while no bound is in force, and a
+ * class-bound handle forwards it to every class whether set before or after gpad_setup_classes.  An entry
+ * point rather than a GPAD_OPT_*: it selects the engine family of a run, as gpad_class_loop_fused does. */
 #define GPAD_CODE_INFEASIBLE 5
 int gpad_setup_infeasibility(gpad_handle_t h, double zbound);
+int gpad_infeasibility_resident(gpad_handle_t h, int on);
 /* host only, no device: *margin = -(g'y) - zbound |G'y|_1 in fp64 on the caller's arrays (G m x n row-major,
  * g and y of m; dtype GPAD_DTYPE_*), -inf when some y_i is negative (or NaN).  > 0 exactly when y certifies
  * that no z with |z|_inf <= zbound satisfies G z <= g: an independent check of a code 5. */

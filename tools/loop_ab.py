@@ -5,7 +5,8 @@ modes: eps cold / eps warm (tol 1e-4, N 3000) and fixed N = 100.
 
   python tools/loop_ab.py [--rounds 3] [--steps 20] [--batches 1 64 256 512 2048 8192] [--fleet | --signals]
                           [--panel] [--infeas]
-  python tools/loop_ab.py --classes K [--signals] [--infeas] [--rounds 3] [--steps 20] [--batches 256 2048 8192]
+  python tools/loop_ab.py --classes K [--signals [--skip-plain]] [--infeas] [--rounds 3] [--steps 20]
+                          [--batches 256 2048 8192]
 
 --panel: a third variant, "panel" (GPAD_OPT_LOOP_PANEL, csrc/gpad_loop_panel.hip: the one-launch loop on the
 MFMA panels), alternated with lockstep and async in the same process and checked against lockstep like
@@ -63,7 +64,13 @@ tolerance their solves end an infeasible step with code 5, so their outputs are 
 out of that bit-for-bit check and compared with each other instead (outputs, counts, codes); every line gains
 `share_code5` -- per variant the share of (step, pack) codes equal to 5 -- `share_capped` (code 0 at N
 iterations), `infeas_mean_iters_per_solve` / `infeas_max_iters_per_solve` and `<bound variant>_over_<variant>`
-for every unbound variant.
+for every unbound variant.  Three more bound variants set the certificate beside the resident kernel
+(gpad_infeasibility_resident): "classes_infeas_res", the bound class binding with the flag on (its lockstep loop
+then runs the resident kernel where a class holds at most 4 packs per CU, else the panels as "classes_infeas"),
+"fleet_infeas", the dims.shared = 0 fleet with the bound (the stream kernel), and "fleet_infeas_res", that fleet
+with the flag on (the resident kernel); all five bound variants are compared bit for bit, and
+`infeas_res_over_infeas` is the rate with the flag over the rate without, per binding.  --skip-plain (with
+--signals) leaves out the second set of handles without signals and `sig_over_plain`.
 
 Per batch and mode the two variants' x, z, y, xs, us and per-step iteration counts are compared first
 (that run is also each variant's warm-up); a mismatch aborts the batch.  Then `rounds` rounds
@@ -111,10 +118,13 @@ def classes_ab(args):
                       "steps": steps, "rounds": rounds, "device": torch.cuda.get_device_name(0),
                       "cus": torch.cuda.get_device_properties(0).multi_processor_count}))
     names = ("fleet", "classes", "classes_panel", "classes_async", "classes_fused") + (
-        ("shared", "shared_panel") if K == 1 else ()) + (("classes_infeas", "classes_fused_infeas") if args.infeas else ())
+        ("shared", "shared_panel") if K == 1 else ()) + (
+        ("classes_infeas", "classes_fused_infeas", "classes_infeas_res", "fleet_infeas", "fleet_infeas_res")
+        if args.infeas else ())
     want = {"classes_panel": "loop_panel", "classes_async": "loop", "classes_fused": "loop_classes",
             "shared_panel": "loop_panel", "classes_fused_infeas": "loop_classes"}
-    INF = ("classes_infeas", "classes_fused_infeas")
+    INF = ("classes_infeas", "classes_fused_infeas", "classes_infeas_res", "fleet_infeas", "fleet_infeas_res")
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
     for B in args.batches:
         class_of = np.arange(B, dtype=np.int32) % K
         X0 = torch.from_numpy((np.random.default_rng(B).random((B, nx)) - 0.5).astype(np.float32)).to(dev)
@@ -130,13 +140,16 @@ def classes_ab(args):
             var = {}
             for name in names:
                 s = gpad_mpc.GpadSolver(0)
-                if name == "fleet":  # expand_classes on the device: instance b holds the arrays of class b % K
+                if name.startswith("fleet"):  # expand_classes on the device: instance b holds the arrays of class b % K
                     f = {k: a[idx].contiguous() for k, a in cls.items()}
                     s.setup(f["ML"], f["G"], L, n=n, m=m, batch=B, shared=False)
                     s.setup_plant(f["PM"], f["Pg"], g0=f["g0"], A=f["A"], B=f["B"])
                     if with_sig:
                         s.setup_signals(f["SM"], f["Sg"], f["E"])
                     del f
+                    if name in INF:
+                        s.set_infeasibility_resident(name.endswith("_res"))
+                        s.setup_infeasibility(problems.battery_zbound())
                 elif name in ("shared", "shared_panel"):
                     s.setup(cls["ML"][0], cls["G"][0], L, n=n, m=m, batch=B, shared=True)
                     s.setup_plant(cls["PM"][0], cls["Pg"][0], g0=cls["g0"][0], A=cls["A"][0], B=cls["B"][0])
@@ -151,6 +164,7 @@ def classes_ab(args):
                     s.set_options(loop_panel=int(name == "classes_panel"), loop_async=int(name == "classes_async"))
                     s.set_class_loop_fused(name in ("classes_fused", "classes_fused_infeas"))
                     if name in INF:
+                        s.set_infeasibility_resident(name.endswith("_res"))
                         s.setup_infeasibility(problems.battery_zbound())
                 buf = dict(x=torch.empty(B, nx, device=dev), z=torch.empty(B, n, device=dev),
                            y=torch.empty(B, m, device=dev), xs=torch.empty(steps, B, nx, device=dev),
@@ -159,7 +173,8 @@ def classes_ab(args):
             return var
 
         var = build(args.signals)
-        plain = build(False) if args.signals else None  # the same variants without signals: sig_over_plain
+        # the same variants without signals: sig_over_plain
+        plain = build(False) if args.signals and not args.skip_plain else None
 
         def enqueue(vs, name, mode, **kw):
             s, b = vs[name]
@@ -181,13 +196,18 @@ def classes_ab(args):
             bad = [f"{v}.{k}" for k in ("x", "z", "y", "xs", "us") for v in same if v != "fleet"
                    if not torch.equal(vs["fleet"][1][k].view(torch.int32), vs[v][1][k].view(torch.int32))]
             bad += [f"{v}.iters" for v in same if not np.array_equal(its["fleet"], its[v])]
-            if "classes_infeas" in vs:  # the two bound variants agree with each other, bit for bit
-                bad += [f"infeas.{k}" for k in ("x", "z", "y", "xs", "us")
-                        if not torch.equal(vs[INF[0]][1][k].view(torch.int32), vs[INF[1]][1][k].view(torch.int32))]
-                if not (np.array_equal(its[INF[0]], its[INF[1]]) and np.array_equal(cds[INF[0]], cds[INF[1]])):
-                    bad.append("infeas.counts")
+            if "classes_infeas" in vs:  # the bound variants agree with each other, bit for bit
+                bad += [f"{v}.{k}" for v in INF[1:] for k in ("x", "z", "y", "xs", "us")
+                        if not torch.equal(vs[INF[0]][1][k].view(torch.int32), vs[v][1][k].view(torch.int32))]
+                bad += [f"{v}.counts" for v in INF[1:]
+                        if not (np.array_equal(its[INF[0]], its[v]) and np.array_equal(cds[INF[0]], cds[v]))]
                 if mode["tol"] > 0 and kern["classes_infeas"] not in ("panel", "stream"):
                     bad.append("classes_infeas.kernel")
+                # (the reported kernel is the largest class's: the resident kernel up to 4 packs per CU)
+                res = "resident" if max(np.bincount(class_of)) <= 4 * cus else "panel"
+                if mode["tol"] > 0 and (kern["classes_infeas_res"], kern["fleet_infeas"], kern["fleet_infeas_res"]) != (
+                        res, "stream", "resident"):
+                    bad.append("infeas_res.kernel")
             if bad or any(kern[v] is None or (kern[v] in ("loop", "loop_panel", "loop_classes")) != (v in want) or
                           (v in want and kern[v] != want[v]) for v in vs):
                 print(json.dumps({"batch": B, "mode": mname, "error": "outputs differ" if bad else "wrong kernel",
@@ -244,7 +264,9 @@ def classes_ab(args):
                     "share_capped": {k: round(float(((cds[k] == 0) & (its[k] == mode["N"])).mean()), 4) for k in var},
                     "infeas_mean_iters_per_solve": round(float(its["classes_infeas"].mean()), 1),
                     "infeas_max_iters_per_solve": int(its["classes_infeas"].max()),
-                    **{f"{i}_over_{v}": round(rate[i] / rate[v], 3) for i in INF for v in var if v not in INF}}
+                    **{f"{i}_over_{v}": round(rate[i] / rate[v], 3) for i in INF for v in var if v not in INF},
+                    "infeas_res_over_infeas": {"classes": round(rate["classes_infeas_res"] / rate["classes_infeas"], 3),
+                                               "fleet": round(rate["fleet_infeas_res"] / rate["fleet_infeas"], 3)}}
                    if args.infeas else {}),
                 **extra}),
                 flush=True)
@@ -262,6 +284,7 @@ def main():
     ap.add_argument("--panel", action="store_true")
     ap.add_argument("--classes", type=int, default=0, metavar="K")
     ap.add_argument("--infeas", action="store_true")
+    ap.add_argument("--skip-plain", action="store_true")
     args = ap.parse_args()
     if args.classes:
         if args.fleet or args.panel or args.classes < 1:
