@@ -152,7 +152,9 @@ static int apply_tuning(gpad_handle_t c, const Tuning& t) {
         const int rc = gpad_set_option(c, o.id, v == def.*o.field ? GPAD_OPT_DEFAULT : o.inverted ? 1 - v : v);
         if (rc) return rc;
     }
-    return gpad_infeasibility_resident(c, t.fk_resident);  // (a handle setting that is no option)
+    // (the handle settings that are no options)
+    if (const int rc = gpad_infeasibility_resident(c, t.fk_resident)) return rc;
+    return gpad_infeasibility_loop_async(c, t.fk_loop_async);
 }
 
 static int setup_body(ClassBinding* cb, const Tuning& tune, const void* ML, const void* G, double L) {
@@ -277,6 +279,15 @@ int classes_infeasibility_resident(ClassBinding* cb, int on) {
         if (const int rc = gpad_infeasibility_resident(c, on)) return rc;
     }
     if (cb->fused) return gpad_infeasibility_resident(cb->fused, on);  // (its loop keeps its own kernel)
+    return GPAD_OK;
+}
+
+int classes_infeasibility_loop_async(ClassBinding* cb, int on) {
+    for (gpad_handle_t c : cb->child) {
+        if (!c) continue;
+        if (const int rc = gpad_infeasibility_loop_async(c, on)) return rc;
+    }
+    if (cb->fused) return gpad_infeasibility_loop_async(cb->fused, on);  // (its loop keeps its own kernel)
     return GPAD_OK;
 }
 

@@ -101,6 +101,8 @@ int classes_state(ClassBinding* cb, void* x, void* z, void* y, const void* sg, b
 int classes_setup_infeasibility(ClassBinding* cb, double zbound);
 // gpad_infeasibility_resident on every class (and the whole-batch handle)
 int classes_infeasibility_resident(ClassBinding* cb, int on);
+// gpad_infeasibility_loop_async likewise
+int classes_infeasibility_loop_async(ClassBinding* cb, int on);
 int classes_last_stats(ClassBinding* cb, gpad_stats_t* st);
 int classes_accumulate(ClassBinding* cb, long long* acc);
 int classes_sync(ClassBinding* cb);

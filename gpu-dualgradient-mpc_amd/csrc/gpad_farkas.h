@@ -13,9 +13,10 @@
 //     infeasible  <=>  q - R a > mu (p + R s),  mu = ViolMargin (16 units of 2^-24 / 2^-53): the roundings of
 //     G/L and -g/L and the fp64 sums, so the certificate holds on the caller's own G, g (gpad_farkas_margin).
 // Code 5 returns z* = z (as the cap exit), y* = y+ and the iteration count.  The rule keeps no state between
-// events.  Four kernels carry it, each as a second variant of its one text: gpad_stream_farkas_kernel,
+// events.  Six kernels carry it, each as a second variant of its one text: gpad_stream_farkas_kernel,
 // gpad_panel_farkas_kernel, gpad_loop_panel_farkas_kernel, gpad_resident_farkas_kernel (opt-in per handle,
-// gpad_infeasibility_resident).  Kernels without it never see a bound: the host routes (gpad_run.cpp launch_solve,
+// gpad_infeasibility_resident), gpad_loop_farkas_kernel and gpad_loop_fleet_farkas_kernel (the asynchronous loop,
+// opt-in per handle, gpad_infeasibility_loop_async).  Kernels without it never see a bound: the host routes (gpad_run.cpp launch_solve,
 // gpad_state.cpp).
 #pragma once
 

@@ -39,6 +39,8 @@ struct Tuning {
     int loop_panel = 0;       // GPAD_OPT_LOOP_PANEL: gpad_closed_loop in one launch on the MFMA panels
     int fk_resident = 0;      // gpad_infeasibility_resident (an entry point, no GPAD_OPT_*): with a bound in force
                               // the resident kernel carries the certificate where unbound runs take that kernel
+    int fk_loop_async = 0;    // gpad_infeasibility_loop_async (likewise): with a bound in force GPAD_OPT_LOOP_ASYNC
+                              // runs the asynchronous loop's certificate kernels instead of the lockstep loop
 };
 
 // Device error word of a run (SolveArgs::err): kernels OR these bits in with a vector atomic;
@@ -197,10 +199,12 @@ struct LoopArgs {
 // nx: columns of the state row, nx + ns with signals bound
 bool loop_supported(int n, int m, int nx, int nu);
 // workgroups of a's kernel that fit one CU by the runtime's occupancy figure, clamped to [1, 2]
-// (always 1 for the two-slot kernel, whose grid is one workgroup per CU)
-int loop_blocks_per_cu(const LoopArgs& a);
+// (always 1 for the two-slot kernel, whose grid is one workgroup per CU); farkas: of its certificate twin
+int loop_blocks_per_cu(const LoopArgs& a, bool farkas = false);
 // persistent grid of `grid` <= min(batch, kAbsmaxMaxBlocks) workgroups
-hipError_t launch_loop(const LoopArgs& a, int grid, hipStream_t s);
+// fk (with s.tol > 0): the instantiation's twin with the infeasibility certificate (gpad_farkas.h; rabs, stride
+// and R as launch_solve builds them)
+hipError_t launch_loop(const LoopArgs& a, int grid, hipStream_t s, const FarkasArgs* fk = nullptr);
 // The same loop on the f32 MFMA panels (gpad_loop_panel.hip, GPAD_OPT_LOOP_PANEL): gpad_panel_kernel<T>'s
 // workgroup (a panel of 16 packs) whose columns step to their pack's next MPC solve in place and are
 // refilled from the queue after its last step.  LoopArgs as above, plus s.frag / s.frag_tiles (the

@@ -3,14 +3,18 @@
 // its one-slot variant for fleets of distinct plants.  Templates only: gpad_loop.hip,
 // gpad_loop_plant.hip and gpad_loop_fleet.hip each instantiate one LoopMode's 64 buckets, so the
 // three compile side by side (one file took as long as the rest of the library together).
+// gpad_loop_farkas.hip, gpad_loop_plant_farkas.hip and gpad_loop_fleet_farkas.hip do the same for the
+// variants with the infeasibility certificate (gpad_farkas.h, gpad_infeasibility_loop_async).
 #pragma once
 
 #include <hip/hip_runtime.h>
 
 #include <cmath>
+#include <type_traits>
 
 #include "gpad_chain.h"
 #include "gpad_duo.h"
+#include "gpad_farkas.h"
 #include "gpad_internal.h"
 
 namespace gpad {
@@ -45,6 +49,13 @@ namespace gpad {
 struct LoopSlot : DuoSlot {
     int t;  // MPC step of the pack in this slot (uniform)
 };
+// the slot of a certificate variant.  A type of its own: with the countdown as a member of LoopSlot, unused as
+// it is there, every gpad_loop_kernel instantiation orders a block of register copies differently
+struct LoopSlotFk : LoopSlot {
+    int kf;  // tests to the next certificate event (uniform): cert <=> (vs + 1) % (4 Kc) == 0
+};
+template <bool FK>
+using LoopSlotOf = std::conditional_t<FK, LoopSlotFk, LoopSlot>;
 
 typedef const __attribute__((address_space(4))) LoopArgs LoopKernArgs;
 // the kernel's LoopArgs read afresh from its kernarg segment (as kargs(): nothing kept live in
@@ -53,6 +64,15 @@ __device__ __forceinline__ LoopKernArgs& largs() {
     LoopKernArgs* p = (LoopKernArgs*)__builtin_amdgcn_kernarg_segment_ptr();
     asm volatile("" : "+s"(p));
     return *p;
+}
+// the FarkasArgs of a certificate variant: the kernel's second parameter, behind the LoopArgs
+typedef const __attribute__((address_space(4))) FarkasArgs LoopFarkasKernArgs;
+__device__ __forceinline__ LoopFarkasKernArgs& lfargs() {
+    static_assert(alignof(FarkasArgs) == 8 && sizeof(LoopArgs) % 8 == 0, "FarkasArgs directly behind LoopArgs");
+    const __attribute__((address_space(4))) char* p =
+        (const __attribute__((address_space(4))) char*)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(p));
+    return *(LoopFarkasKernArgs*)(p + sizeof(LoopArgs));
 }
 
 // LDS of the step boundaries
@@ -120,13 +140,14 @@ __device__ __forceinline__ void loop_rows(const DuoCtx& c, int p, float (&r)[K])
 
 // Start the solve of slot s at state x_l (barrier-published by the caller) from (z_{-1}, y_0) = v0
 // of this lane's row: g_P(x) / p_D(x) to the slot's LDS rows, then the fresh path of duo_refill.
-// Uniform, contains barriers.
-template <int KB, int K, int MODE>
-__device__ __forceinline__ void loop_start(const SolveArgs<float>& a, const DuoCtx& c, LoopSlot& s, float v0,
+// Uniform, contains barriers.  FK: a certificate variant (the slot's event countdown starts over).
+template <int KB, int K, int MODE, bool FK = false>
+__device__ __forceinline__ void loop_start(const SolveArgs<float>& a, const DuoCtx& c, LoopSlotOf<FK>& s, float v0,
                                            float* x_l, float* w_l, float* gp_l, float* pd_l, float* z_l,
                                            float* gm_l, const float (&r)[K]) {
     s.vs = 0;
     s.kc = c.Kc;
+    if constexpr (FK) s.kf = 4;
     s.need8d = false;
     s.th = sched(a.theta, 0);
     s.bn = sched(a.beta, 1);
@@ -165,8 +186,8 @@ __device__ __forceinline__ void loop_start(const SolveArgs<float>& a, const DuoC
 // slot s takes pack p at its step 0 (empty if p >= count): x from the input states, (z, y) from the
 // caller's arrays when warm, else zero.  FLEET: the pack brings its own matrices, the rows r are
 // reloaded and stay for its `steps` steps.  Uniform, contains barriers.
-template <int KB, int K, int MODE>
-__device__ __forceinline__ void loop_refill(const SolveArgs<float>& a, const DuoCtx& c, LoopSlot& s, int p,
+template <int KB, int K, int MODE, bool FK = false>
+__device__ __forceinline__ void loop_refill(const SolveArgs<float>& a, const DuoCtx& c, LoopSlotOf<FK>& s, int p,
                                             float* x_s, float* w_l, float* gp_l, float* pd_l, float* z_l,
                                             float* gm_l, float (&r)[K]) {
     s.pos = __builtin_amdgcn_readfirstlane(p);
@@ -182,10 +203,11 @@ __device__ __forceinline__ void loop_refill(const SolveArgs<float>& a, const Duo
     }
     __syncthreads();  // x_s (and the claim cell, loop_claim) published
     if (has) {
-        loop_start<KB, K, MODE>(a, c, s, v0, x_s, w_l, gp_l, pd_l, z_l, gm_l, r);
+        loop_start<KB, K, MODE, FK>(a, c, s, v0, x_s, w_l, gp_l, pd_l, z_l, gm_l, r);
     } else {
         s.vs = 0;
         s.kc = c.Kc;
+        if constexpr (FK) s.kf = 4;
         s.need8d = false;
         s.th = s.bn = 0.0f;
         s.x0 = s.x1 = s.x2 = 0.0f;
@@ -193,27 +215,69 @@ __device__ __forceinline__ void loop_refill(const SolveArgs<float>& a, const Duo
 }
 
 // consume the pre-claimed position of slot s, claim its next one (claim_l: this slot's cell)
-template <int KB, int K, int MODE>
-__device__ __forceinline__ void loop_claim(const SolveArgs<float>& a, const DuoCtx& c, LoopSlot& s, int* claim_l,
+template <int KB, int K, int MODE, bool FK = false>
+__device__ __forceinline__ void loop_claim(const SolveArgs<float>& a, const DuoCtx& c, LoopSlotOf<FK>& s, int* claim_l,
                                            float* x_s, float* w_l, float* gp_l, float* pd_l, float* z_l,
                                            float* gm_l, float (&r)[K]) {
     const int p = s.nextp;
     if (c.tid == 0 && p < c.count) *claim_l = c.claim_base + atomicAdd(a.qctr, 1);
-    loop_refill<KB, K, MODE>(a, c, s, p, x_s, w_l, gp_l, pd_l, z_l, gm_l, r);  // (its barrier publishes *claim_l)
+    loop_refill<KB, K, MODE, FK>(a, c, s, p, x_s, w_l, gp_l, pd_l, z_l, gm_l, r);  // (its barrier publishes *claim_l)
     s.nextp = p < c.count ? __builtin_amdgcn_readfirstlane(*claim_l) : c.count;
+}
+
+// A certificate event of slot sb (gpad_farkas.h; certificate variants only), after Algorithm 1 found no
+// code at a test with (vs + 1) % (4 check_every) == 0: the G/L lanes publish y+ = sb.x0 and reduce
+// q = sum y+ pD as gpad_resident_farkas_kernel does (the wave butterfly, then the G/L waves' partials in
+// wave order); q > 0 nominates and farkas_decide -- the stream kernel's text, on the pack's k-major G_L
+// image in global memory, not on the row registers -- decides.  Returns kCodeInfeasible or 0.  The
+// scratch is one set per workgroup, shared by both slots as vslots and z_l are.  Uniform, contains
+// barriers; rare, so it keeps nothing in registers across the solve loop.
+template <int KA, int KB>
+__device__ __forceinline__ int loop_farkas(const DuoCtx& c, const LoopSlotFk& sb, const float* pdb_l) {
+    __shared__ float yf_l[KA];
+    __shared__ double fq_l[kResidentMaxThreads / 64], ft_l[KB];
+    if (!c.isA) {
+        double fq = 0.0;  // this row's term of q
+        if (c.live) {
+            yf_l[c.row] = sb.x0;
+            fq = (double)sb.x0 * (double)pdb_l[c.row];
+        }
+        fq = wave_sum(fq);
+        if ((c.tid & 63) == 0) fq_l[c.tid >> 6] = fq;
+    }
+    __syncthreads();
+    double q = 0.0;
+    for (int i = 0; i < c.nwaves - c.nA; ++i) q += fq_l[c.b0 + i];
+    if (!(q > 0.0)) return 0;  // (uniform: every thread summed the same words)
+    LoopKernArgs& A = largs();
+    LoopFarkasKernArgs& fk = lfargs();
+    const size_t b = (size_t)sb.pos;
+    return farkas_decide<float>(A.s.GLt + b * A.s.strideB, A.s.ldm, c.n, c.m, yf_l, pdb_l, fk.rabs + b * fk.stride,
+                                fk.R, q, ft_l)
+               ? kCodeInfeasible
+               : 0;
 }
 
 // after the barrier that closes slot sb's 8d half (every wave): the shared test, and when the solve
 // terminates the step boundary -- record the step, x_{t+1} = A x_t + B u, then either the pack's
 // next step in place or, after its last step, the results out and the next pack from the queue.
-// x_b: this slot's two x vectors; u_l: boundary scratch.
-template <int KB, int K, int MODE, bool PRE = false>
-__device__ __forceinline__ void loop_post_b(const SolveArgs<float>& a, const DuoCtx& c, LoopSlot& sb, bool chk,
-                                            float* wb_l, float* gpb_l, float* pdb_l, CheckSlot* slots_b,
+// x_b: this slot's two x vectors; u_l: boundary scratch.  FKA: the KA of a certificate variant (0:
+// none), which holds a certificate event after every fourth test of a solve; its code 5 ends the solve
+// as the cap does (z* = z, y* = y+).
+template <int KB, int K, int MODE, bool PRE = false, int FKA = 0>
+__device__ __forceinline__ void loop_post_b(const SolveArgs<float>& a, const DuoCtx& c, LoopSlotOf<FKA != 0>& sb,
+                                            bool chk, float* wb_l, float* gpb_l, float* pdb_l, CheckSlot* slots_b,
                                             CheckSlot* vslots, int* claim_b, float* z_l, float* x_b, float* u_l,
                                             float* gm_l, float (&r)[K], float th_n = 0.0f,
                                             float bn_n = 0.0f) {
-    const int done = duo_test_b<KB, K, PRE>(a, c, sb, chk, pdb_l, slots_b, vslots, z_l, r, th_n, bn_n);
+    int done = duo_test_b<KB, K, PRE>(a, c, sb, chk, pdb_l, slots_b, vslots, z_l, r, th_n, bn_n);
+    if constexpr (FKA != 0) {
+        if (chk) {
+            const bool cert = sb.kf == 1;
+            sb.kf = cert ? 4 : sb.kf - 1;
+            if (cert && !done) done = loop_farkas<FKA, KB>(c, sb, pdb_l);  // Algorithm 1 first: any code of its wins
+        }
+    }
     const int v = sb.vs;
     if (done || v >= c.N) {
         LoopKernArgs& A = largs();
@@ -253,18 +317,19 @@ __device__ __forceinline__ void loop_post_b(const SolveArgs<float>& a, const Duo
         }
         __syncthreads();  // xn published; xc and u_l free
         if (last) {
-            loop_claim<KB, K, MODE>(a, c, sb, claim_b, x_b, wb_l, gpb_l, pdb_l, z_l, gm_l, r);
+            loop_claim<KB, K, MODE, FKA != 0>(a, c, sb, claim_b, x_b, wb_l, gpb_l, pdb_l, z_l, gm_l, r);
         } else {
             sb.t = t + 1;  // cold: z = y = 0 (acceldualgrad.m:16-17); warm: z_{-1} = z*, y_0 = y*
-            loop_start<KB, K, MODE>(a, c, sb, A.warm ? star : 0.0f, xn, wb_l, gpb_l, pdb_l, z_l, gm_l, r);
+            loop_start<KB, K, MODE, FKA != 0>(a, c, sb, A.warm ? star : 0.0f, xn, wb_l, gpb_l, pdb_l, z_l, gm_l, r);
         }
     }
 }
 
 // one step: -ML waves run 8b+8c of slot sa, G/L waves 8d+8a (+ test) of slot sb (as duo_step)
-template <int KA, int KB, int K, int MODE>
-__device__ __forceinline__ void loop_step(const SolveArgs<float>& a, const DuoCtx& c, LoopSlot& sa, LoopSlot& sb,
-                                          float* wa_l, float* zha_l, const float* gpa_l, float* wb_l,
+template <int KA, int KB, int K, int MODE, int FKA = 0>
+__device__ __forceinline__ void loop_step(const SolveArgs<float>& a, const DuoCtx& c, LoopSlotOf<FKA != 0>& sa,
+                                          LoopSlotOf<FKA != 0>& sb, float* wa_l, float* zha_l,
+                                          const float* gpa_l, float* wb_l,
                                           const float* zhb_l, float* gpb_l, float* pdb_l, CheckSlot* slots_b,
                                           CheckSlot* vslots, int* claim_b, float* z_l, float* x_b, float* u_l,
                                           float* gm_l, float (&r)[K]) {
@@ -279,14 +344,15 @@ __device__ __forceinline__ void loop_step(const SolveArgs<float>& a, const DuoCt
     __syncthreads();
     if (runA) sa.need8d = true;
     if (runB)
-        loop_post_b<KB, K, MODE>(a, c, sb, chk, wb_l, gpb_l, pdb_l, slots_b, vslots, claim_b, z_l, x_b, u_l, gm_l, r);
+        loop_post_b<KB, K, MODE, false, FKA>(a, c, sb, chk, wb_l, gpb_l, pdb_l, slots_b, vslots, claim_b, z_l, x_b, u_l,
+                                             gm_l, r);
 }
 
 // One live slot left, the queue drained: the resident kernel's loop on it (as duo_solo; with at
 // most one pack per workgroup this is the whole run; the fleet kernel's only loop)
-template <int KA, int KB, int K, int MODE>
-__device__ __forceinline__ void loop_solo(const SolveArgs<float>& a, const DuoCtx& c, LoopSlot& s, float* w_l,
-                                          float* zh_l, float* gp_l, float* pd_l, CheckSlot* slots,
+template <int KA, int KB, int K, int MODE, int FKA = 0>
+__device__ __forceinline__ void loop_solo(const SolveArgs<float>& a, const DuoCtx& c, LoopSlotOf<FKA != 0>& s,
+                                          float* w_l, float* zh_l, float* gp_l, float* pd_l, CheckSlot* slots,
                                           CheckSlot* vslots, int* claim, float* z_l, float* x_s, float* u_l,
                                           float* gm_l, float (&r)[K]) {
     float th_n = a.theta[s.vs + 1], bn_n = a.beta[s.vs + 2];
@@ -308,14 +374,14 @@ __device__ __forceinline__ void loop_solo(const SolveArgs<float>& a, const DuoCt
             bn_n = a.beta[s.vs + 2];
         }
         __syncthreads();
-        loop_post_b<KB, K, MODE, true>(a, c, s, chk, w_l, gp_l, pd_l, slots, vslots, claim, z_l, x_s, u_l, gm_l, r, th_n,
-                                 bn_n);
+        loop_post_b<KB, K, MODE, true, FKA>(a, c, s, chk, w_l, gp_l, pd_l, slots, vslots, claim, z_l, x_s, u_l, gm_l, r,
+                                            th_n, bn_n);
     }
 }
 
 // The fleet kernel's context and its max |g| epilogue: gpad_loop_kernel's own text of both, kept
 // apart because that kernel's register allocation moves when they are hoisted out of its body
-// (+1 VGPR in most buckets, other scratch at 208/208).
+// (+1 VGPR in most buckets, other scratch at 208/208).  (The kernels: gpad_loop_kernels.inc, below.)
 // the workgroup's context; claim_base: the queue's first position, after the static starts
 __device__ __forceinline__ DuoCtx loop_ctx(const SolveArgs<float>& a, int claim_base) {
     DuoCtx c;
@@ -362,141 +428,13 @@ __device__ __forceinline__ void loop_gmax_out(const DuoCtx& c, float* gm_l) {
     }
 }
 
-template <int KA, int KB, int MODE = kLoopShared>
-__global__ __launch_bounds__(kResidentMaxThreads) void gpad_loop_kernel(LoopArgs la) {
-    const SolveArgs<float>& a = la.s;
-    constexpr int K = KA > KB ? KA : KB;
-    constexpr int PA = (KA + 63) / 64 * 64, PB = (KB + 63) / 64 * 64;
-    __shared__ __attribute__((aligned(16))) float w_l[2][PA];   // w per slot (broadcast to -ML rows)
-    __shared__ __attribute__((aligned(16))) float zh_l[2][PB];  // zhat per slot (to G/L rows)
-    __shared__ __attribute__((aligned(16))) float z_l[PB];      // z_{-1} of a fresh solve (u seed)
-    __shared__ float gp_l[2][PB];                               // per slot: g_P of the -ML rows
-    __shared__ float pd_l[2][PA];                               //           p_D of the G/L rows
-    __shared__ CheckSlot slots[2][kResidentMaxThreads / 64];
-    __shared__ CheckSlot vslots[kResidentMaxThreads / 64];  // verification of a nominated test (A)
-    __shared__ int claim_l[2];
-    __shared__ LoopLds L;
-
-    DuoCtx c;
-    c.tid = threadIdx.x;
-    c.count = a.batch;
-    c.G = gridDim.x;
-    c.v0 = 0;
-    c.fresh = true;
-    c.use_tol = a.tol > 0.0;
-    c.n = a.n;
-    c.m = a.m;
-    c.N = a.N;
-    c.Kc = a.check_every;
-    c.kc0 = c.Kc;
-    c.nA = (c.n + 63) >> 6;
-    c.nwaves = blockDim.x >> 6;
-    {   // the G/L waves first (the older wave of each SIMD), as gpad_duo_kernel
-        const int nB = c.nwaves - c.nA;
-        c.isA = (c.tid >> 6) >= nB;
-        c.row = c.isA ? c.tid - 64 * nB : c.tid;
-        c.b0 = 0;
-    }
-    c.live = c.isA ? c.row < c.n : c.row < c.m;
-
-    float r[K];
-    {
-        const int len = c.isA ? c.m : c.n;
-        const float* __restrict__ Mt = c.isA ? a.MGt : a.GLt;
-        const int ld = c.isA ? a.ldn : a.ldm;
-#pragma unroll
-        for (int k = 0; k < K; ++k) r[k] = (c.live && k < len) ? Mt[(size_t)k * ld + c.row] : 0.0f;
-    }
-    for (int i = c.tid; i < 2 * PA; i += blockDim.x) (&w_l[0][0])[i] = 0.0f;
-    for (int i = c.tid; i < 2 * PB; i += blockDim.x) (&zh_l[0][0])[i] = 0.0f;
-    for (int i = c.tid; i < PB; i += blockDim.x) z_l[i] = 0.0f;
-    for (int i = c.tid; i < kResidentMaxThreads; i += blockDim.x) L.gm[i] = 0.0f;
-    // Static start: slot 0 of workgroup b takes pack b, slot 1 pack G + b; later packs are claimed
-    // from the counter.  (The grid is at most `batch` workgroups, so every slot 0 has a pack.)
-    c.claim_base = 2 * c.G;
-    if (c.tid == 0) {  // first claims of the queue (positions 2G, ...)
-        claim_l[0] = c.claim_base + atomicAdd(a.qctr, 1);
-        claim_l[1] = c.claim_base + atomicAdd(a.qctr, 1);
-    }
-    __syncthreads();
-    LoopSlot s0, s1;
-    s0.nextp = __builtin_amdgcn_readfirstlane(claim_l[0]);
-    s1.nextp = __builtin_amdgcn_readfirstlane(claim_l[1]);
-    loop_refill<KB, K, MODE>(a, c, s0, blockIdx.x, &L.x[0][0][0], w_l[0], gp_l[0], pd_l[0], z_l, L.gm, r);
-    loop_refill<KB, K, MODE>(a, c, s1, blockIdx.x + c.G, &L.x[1][0][0], w_l[1], gp_l[1], pd_l[1], z_l, L.gm, r);
-    while (s0.pos < c.count || s1.pos < c.count) {
-        if (s0.pos >= c.count) {
-            loop_solo<KA, KB, K, MODE>(a, c, s1, w_l[1], zh_l[1], gp_l[1], pd_l[1], slots[1], vslots, &claim_l[1], z_l,
-                                 &L.x[1][0][0], L.u, L.gm, r);
-            break;
-        }
-        if (s1.pos >= c.count) {
-            loop_solo<KA, KB, K, MODE>(a, c, s0, w_l[0], zh_l[0], gp_l[0], pd_l[0], slots[0], vslots, &claim_l[0], z_l,
-                                 &L.x[0][0][0], L.u, L.gm, r);
-            break;
-        }
-        loop_step<KA, KB, K, MODE>(a, c, s0, s1, w_l[0], zh_l[0], gp_l[0], w_l[1], zh_l[1], gp_l[1], pd_l[1], slots[1],
-                             vslots, &claim_l[1], z_l, &L.x[1][0][0], L.u, L.gm, r);
-        loop_step<KA, KB, K, MODE>(a, c, s1, s0, w_l[1], zh_l[1], gp_l[1], w_l[0], zh_l[0], gp_l[0], pd_l[0], slots[0],
-                             vslots, &claim_l[0], z_l, &L.x[0][0][0], L.u, L.gm, r);
-    }
-    // the run's max |g| (the certification floor): this workgroup's slot, workgroup 0 zeroes the rest
-    LoopKernArgs& A = largs();
-    if (A.gmax) {
-        const float wm = wave_reduce(L.gm[c.tid], OpAbsmaxNan{});
-        __syncthreads();  // (every lane has read its L.gm word)
-        if ((c.tid & 63) == 0) L.gm[c.tid >> 6] = wm;
-        __syncthreads();
-        if (c.tid == 0) {
-            float mx = 0.0f;
-            for (int w = 0; w < c.nwaves; ++w) mx = absmax_nan(mx, L.gm[w]);
-            A.gmax[blockIdx.x] = (double)mx;
-        }
-        if (blockIdx.x == 0)
-            for (int i = c.G + c.tid; i < kAbsmaxMaxBlocks; i += blockDim.x) A.gmax[i] = 0.0;
-    }
-}
-
-// =========================================================================================
-// gpad_loop_fleet_kernel: the same loop for a fleet of distinct plants (per-pack -ML, G/L).
-// =========================================================================================
-// Two packs cannot share one set of row registers, so a workgroup holds ONE live slot and runs
-// loop_solo on it: the resident kernel's loop with the step boundary above.  When the slot takes a
-// pack -- workgroup b starts with pack b, later packs come from the queue (positions G, ...) -- it
-// loads that pack's rows from MGt + p strideA / GLt + p strideB (loop_rows) and keeps them for the
-// pack's `steps` steps, where the lockstep loop re-reads every pack's matrices at every step.  The
-// ping-pong's latency hiding is gone; the host runs two workgroups per CU where they fit instead.
-template <int KA, int KB>
-__global__ __launch_bounds__(kResidentMaxThreads) void gpad_loop_fleet_kernel(LoopArgs la) {
-    const SolveArgs<float>& a = la.s;
-    constexpr int K = KA > KB ? KA : KB;
-    constexpr int PA = (KA + 63) / 64 * 64, PB = (KB + 63) / 64 * 64;
-    __shared__ __attribute__((aligned(16))) float w_l[PA];   // w (broadcast to -ML rows)
-    __shared__ __attribute__((aligned(16))) float zh_l[PB];  // zhat (to G/L rows)
-    __shared__ __attribute__((aligned(16))) float z_l[PB];   // z_{-1} of a fresh solve (u seed)
-    __shared__ float gp_l[PB];                               // g_P of the -ML rows
-    __shared__ float pd_l[PA];                               // p_D of the G/L rows
-    __shared__ CheckSlot slots[kResidentMaxThreads / 64];
-    __shared__ CheckSlot vslots[kResidentMaxThreads / 64];
-    __shared__ int claim_l;
-    __shared__ LoopLds L;  // (x[0], u, gm)
-
-    const DuoCtx c = loop_ctx(a, (int)gridDim.x);
-    float r[K];
-#pragma unroll
-    for (int k = 0; k < K; ++k) r[k] = 0.0f;
-    for (int i = c.tid; i < PA; i += blockDim.x) w_l[i] = 0.0f;
-    for (int i = c.tid; i < PB; i += blockDim.x) zh_l[i] = z_l[i] = 0.0f;
-    for (int i = c.tid; i < kResidentMaxThreads; i += blockDim.x) L.gm[i] = 0.0f;
-    if (c.tid == 0) claim_l = c.claim_base + atomicAdd(a.qctr, 1);  // first claim of the queue
-    __syncthreads();
-    LoopSlot s;
-    s.nextp = __builtin_amdgcn_readfirstlane(claim_l);
-    loop_refill<KB, K, kLoopFleet>(a, c, s, blockIdx.x, &L.x[0][0][0], w_l, gp_l, pd_l, z_l, L.gm, r);
-    loop_solo<KA, KB, K, kLoopFleet>(a, c, s, w_l, zh_l, gp_l, pd_l, slots, vslots, &claim_l, z_l, &L.x[0][0][0], L.u,
-                               L.gm, r);
-    loop_gmax_out(c, L.gm);
-}
+// the kernels: the unbound pair, then the pair with the infeasibility certificate
+#define GPAD_LOOP_FK 0
+#include "gpad_loop_kernels.inc"
+#undef GPAD_LOOP_FK
+#define GPAD_LOOP_FK 1
+#include "gpad_loop_kernels.inc"
+#undef GPAD_LOOP_FK
 
 // ---- host side: the instantiation of a (KA, KB) bucket pair, per translation unit ----------------
 typedef void (*LoopFn)(LoopArgs);
@@ -515,5 +453,23 @@ LoopFn loop_fn_of(int ka, int kb) {
 // defined in gpad_loop_plant.hip / gpad_loop_fleet.hip
 LoopFn loop_fn_per_plant(int ka, int kb);
 LoopFn loop_fn_fleet(int ka, int kb);
+
+// the certificate twins, one unit per mode: gpad_loop_farkas.hip, gpad_loop_plant_farkas.hip,
+// gpad_loop_fleet_farkas.hip
+typedef void (*LoopFarkasFn)(LoopArgs, FarkasArgs);
+template <int MODE, int KA, int KB>
+LoopFarkasFn loop_farkas_fn_ab() {
+    if constexpr (MODE == kLoopFleet) return gpad_loop_fleet_farkas_kernel<KA, KB>;
+    else return gpad_loop_farkas_kernel<KA, KB, MODE>;
+}
+template <int MODE>
+LoopFarkasFn loop_farkas_fn_of(int ka, int kb) {
+    return with_buckets(ka, kb, [](auto KA, auto KB) {
+        return loop_farkas_fn_ab<MODE, decltype(KA)::value, decltype(KB)::value>();
+    });
+}
+LoopFarkasFn loop_farkas_fn_shared(int ka, int kb);
+LoopFarkasFn loop_farkas_fn_per_plant(int ka, int kb);
+LoopFarkasFn loop_farkas_fn_fleet(int ka, int kb);
 
 }  // namespace gpad

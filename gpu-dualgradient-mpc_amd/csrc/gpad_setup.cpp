@@ -268,6 +268,18 @@ int gpad_infeasibility_resident(gpad_handle_t h, int on) {
     });
 }
 
+// gpad_infeasibility_resident's twin for GPAD_OPT_LOOP_ASYNC (gpad_state.cpp one_launch_engine)
+int gpad_infeasibility_loop_async(gpad_handle_t h, int on) {
+    return gpad::abi_guard("gpad_infeasibility_loop_async", [&]() -> int {
+        if (!h) return fail(GPAD_ERR_INVALID, "gpad_infeasibility_loop_async: null handle");
+        if (on != 0 && on != 1) return fail(GPAD_ERR_INVALID, "gpad_infeasibility_loop_async: on must be 0 or 1");
+        h->tune.fk_loop_async = on;
+        if (!h->cls) return GPAD_OK;
+        HIP_TRY(hipSetDevice(h->device));
+        return gpad::classes_infeasibility_loop_async(h->cls, on);
+    });
+}
+
 // -(g'y) - R |G'y|_1 in fp64 on host arrays (no device): > 0 exactly when y >= 0 proves that no z with
 // |z|_inf <= R satisfies G z <= g; -inf when y has a negative entry (or a NaN)
 int gpad_farkas_margin(int n, int m, int dtype, const void* G, const void* g, const void* y, double zbound,

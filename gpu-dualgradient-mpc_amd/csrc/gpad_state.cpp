@@ -223,7 +223,7 @@ static int one_launch_engine(gpad_handle_t h, bool loop, int N, double tol, int 
     const int n = d.n, m = d.m, nu = h->plant->nu;
     const bool lpanel = loop && h->tune.loop_panel && loop_panel_shape(h, N, tol, nxa);
     const bool async = lpanel || (loop && h->tune.loop_async && !h->flat && !h->hess_ok && N >= 1 &&
-                                  !(h->zbound > 0.0 && tol > 0.0) &&
+                                  (!(h->zbound > 0.0 && tol > 0.0) || h->tune.fk_loop_async) &&
                                   (d.kernel == GPAD_KERNEL_AUTO || d.kernel == GPAD_KERNEL_RESIDENT) &&
                                   gpad::loop_supported(n, m, nxa, nu));
     return lpanel ? GPAD_KERNEL_LOOP_PANEL : async ? GPAD_KERNEL_LOOP : 0;
@@ -266,6 +266,7 @@ static int run_loop_one_launch(gpad_handle_t h, const StateWork<float>& w, int e
     la.steps = nsolve;
     la.warm = warm ? 1 : 0;
     la.per_plant = w.v.per_copy ? 1 : 0;
+    const bool fk_on = h->zbound > 0.0 && tol > 0.0;  // the infeasibility certificate (gpad_setup_infeasibility)
     int grid;
     if (cl) {  // every class in one launch: its images, counters and tables (the maps are in w already)
         a.frag = cl->frag;
@@ -280,14 +281,15 @@ static int run_loop_one_launch(gpad_handle_t h, const StateWork<float>& w, int e
         a.frag_tiles = h->frag_tiles;
         grid = gpad::loop_panel_grid(d.n, d.m, d.batch, h->num_cus, &h->tune);
     } else {
-        grid = std::min(d.batch, h->num_cus * gpad::loop_blocks_per_cu(la));
+        grid = std::min(d.batch, h->num_cus * gpad::loop_blocks_per_cu(la, fk_on));
         if (h->tune.duo_max_grid > 0 && h->tune.duo_max_grid < grid) grid = h->tune.duo_max_grid;
         grid = std::min(grid, (int)gpad::kAbsmaxMaxBlocks);
     }
-    // (the panel loop carries the infeasibility certificate; gpad_loop_kernel does not: one_launch_engine)
-    const gpad::FarkasArgs fk{nullptr, 0, h->zbound};
-    const hipError_t e = lpanel ? gpad::launch_loop_panel(la, grid, h->stream, h->zbound > 0.0 && tol > 0.0 ? &fk : nullptr)
-                                : gpad::launch_loop(la, grid, h->stream);
+    // (the panel loop reads the bound alone; gpad_loop_kernel's certificate twins the values launch_solve builds.
+    // A bound reaches launch_loop only with gpad_infeasibility_loop_async on: one_launch_engine)
+    const gpad::FarkasArgs fk{lpanel ? nullptr : (const double*)h->frows.p, d.shared ? 0 : (long long)h->ldm, h->zbound};
+    const hipError_t e = lpanel ? gpad::launch_loop_panel(la, grid, h->stream, fk_on ? &fk : nullptr)
+                                : gpad::launch_loop(la, grid, h->stream, fk_on ? &fk : nullptr);
     if (e != hipSuccess) return fail(GPAD_ERR_HIP, std::string("loop kernel: ") + hipGetErrorString(e));
     h->last_phased = false;
     h->last_p64 = false;

@@ -49,6 +49,7 @@ EXPORTS = [
     "gpad_class_order", "gpad_setup_classes", "gpad_setup_plant_classes",
     "gpad_class_loop_fused", "gpad_class_loop_deal", "gpad_setup_class_signals",
     "gpad_setup_infeasibility", "gpad_farkas_margin", "gpad_infeasibility_resident",
+    "gpad_infeasibility_loop_async",
 ]
 GROUP_RCCL, GROUP_PEER = 1, 2
 
@@ -219,6 +220,9 @@ def load(path: str | None = None) -> C.CDLL:
     if hasattr(L, "gpad_infeasibility_resident"):  # (added within 0.6; absent from older builds under GPAD_LIB_TOLERANT)
         L.gpad_infeasibility_resident.argtypes = [vp, i]
         L.gpad_infeasibility_resident.restype = i
+    if hasattr(L, "gpad_infeasibility_loop_async"):  # (added within 0.6; absent from older builds under GPAD_LIB_TOLERANT)
+        L.gpad_infeasibility_loop_async.argtypes = [vp, i]
+        L.gpad_infeasibility_loop_async.restype = i
     L.gpad_datafile_read.argtypes = [C.c_char_p, i, C.POINTER(DataFile)]
     L.gpad_datafile_write.argtypes = [C.c_char_p, i, C.POINTER(DataFile)]
     L.gpad_datafile_free.argtypes = [C.POINTER(DataFile)]

@@ -204,7 +204,8 @@ class GpadSolver:
         (check it with ``farkas_margin``); 0 unbinds, as does every ``setup*``.  With a bound in force the
         solves run on the f32 T-wave panels (shared matrices, n, m <= 256) or else the stream kernel, the
         ``loop_panel`` option and the fused class loop keep their one-launch loops, and ``loop_async`` falls
-        back to lockstep.  ``set_infeasibility_resident`` lets the resident kernel carry the certificate."""
+        back to lockstep unless ``set_infeasibility_loop_async`` is on.  ``set_infeasibility_resident`` lets the
+        resident kernel carry the certificate."""
         check(self.lib.gpad_setup_infeasibility(self.h, float(zbound)), "gpad_setup_infeasibility")
 
     def set_infeasibility_resident(self, on: bool) -> None:
@@ -215,6 +216,16 @@ class GpadSolver:
         "resident").  Results are bit for bit the same.  Off by default; a handle setting like an option: it
         survives ``setup*`` and unbinding, and a class binding forwards it to every class."""
         check(self.lib.gpad_infeasibility_resident(self.h, 1 if on else 0), "gpad_infeasibility_resident")
+
+    def set_infeasibility_loop_async(self, on: bool) -> None:
+        """gpad_infeasibility_loop_async: with a bound in force (``setup_infeasibility``, tol > 0) the ``loop_async``
+        option keeps its one-launch loop (reported kernel "loop") on kernel variants that carry the certificate:
+        a pack whose solve ends with code 5 applies u = z*[0:nu] and steps on like any other.  Results are bit for
+        bit the lockstep loop's.  Every other condition of ``loop_async`` stands (f32, n, m <= 208, nx + ns <= 64,
+        no forced PANEL / STREAM, no caller schedule tables); what it does not take falls back to lockstep as
+        before.  Off by default and separate from ``set_infeasibility_resident``; a handle setting like an option:
+        it survives ``setup*`` and unbinding, and a class binding forwards it to every class."""
+        check(self.lib.gpad_infeasibility_loop_async(self.h, 1 if on else 0), "gpad_infeasibility_loop_async")
 
     def run(self, z, y, M, g, N: int, tol: float = 0.0, *, stats: bool = True, iters=None,
             scaled: bool = False, theta=None, beta=None, codes=None):
@@ -442,7 +453,8 @@ class GpadSolver:
         (``kernel == "loop"`` in the stats); it applies to f32 setups, shared matrices or per-instance
         ones, no flat setup and no Hessian, n, m <= 208, kernel AUTO or RESIDENT, N >= 1, nx <= 64 and
         nu <= min(n, 64), with one plant or per-instance maps (``setup_plant``), and any other call
-        runs the lockstep loop.  Results are bit-identical.
+        runs the lockstep loop -- also a call with an infeasibility bound in force (``setup_infeasibility``,
+        tol > 0), unless ``set_infeasibility_loop_async(True)``.  Results are bit-identical.
 
         ``set_option("loop_panel", 1)`` is the same one-launch loop for fleets on the MFMA panels
         (``kernel == "loop_panel"``): a panel column whose solve ends steps to its instance's next

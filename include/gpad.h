@@ -40,7 +40,8 @@ extern "C" {
                               * GPAD_KERNEL_LOOP_CLASSES (8); gpad_setup_class_signals;
                               * gpad_setup_infeasibility, gpad_farkas_margin and the termination code
                               * GPAD_CODE_INFEASIBLE (5), returned only with a bound in force;
-                              * gpad_infeasibility_resident (off by default: no routing changes) */
+                              * gpad_infeasibility_resident and gpad_infeasibility_loop_async (off by
+                              * default: no routing changes) */
 
 /* status codes */
 #define GPAD_OK 0
@@ -213,17 +214,19 @@ int gpad_setup_hessian(gpad_handle_t h, const void* H);
  * Stats: code 5 counts as not converged in every aggregate; codes[] carries the 5.  A closed-loop step that
  * ends with code 5 applies u = z*[0:nu] as a capped step does, and the loop goes on.
  *
- * Engines.  Four kernels carry the branch: gpad_stream_kernel (f32 and f64, any shape, shared or distinct
+ * Engines.  Five kernel families carry the branch: gpad_stream_kernel (f32 and f64, any shape, shared or distinct
  * matrices), the f32 T-wave MFMA panel (shared matrices, n, m <= 256: every T <= 16, phased compaction as ever --
  * a code-5 instance leaves the panel like a converged one -- no pair layout, no finisher), the panel loop
  * (GPAD_OPT_LOOP_PANEL and gpad_class_loop_fused: a code-5 column takes its step boundary like any finished
- * column) and, opt-in per handle (gpad_infeasibility_resident below), the f32 resident kernel (n, m <= 208,
- * shared or distinct matrices).  All give the same z, y, counts and codes.  With a bound in force (bound, and
+ * column) and, opt-in per handle, the f32 resident kernel (gpad_infeasibility_resident below; n, m <= 208,
+ * shared or distinct matrices) and the asynchronous closed loop (gpad_infeasibility_loop_async below; the
+ * shapes GPAD_OPT_LOOP_ASYNC takes).  All give the same z, y, counts and codes.  With a bound in force (bound, and
  * tol > 0):
  *   - dims.kernel AUTO and GPAD_KERNEL_PANEL run those panels where they apply; AUTO else the stream kernel
  *     (f64, distinct matrices, n or m > 256), whatever the batch -- the pairs, the finisher, the big panels and
  *     the f64 panels are not used, nor by default the resident kernel;
- *   - GPAD_OPT_LOOP_ASYNC falls back to the lockstep loop, silently as for any shape it does not take;
+ *   - GPAD_OPT_LOOP_ASYNC falls back to the lockstep loop, silently as for any shape it does not take
+ *     (by default: gpad_infeasibility_loop_async below);
  *   - GPAD_ERR_UNSUPPORTED: a forced GPAD_KERNEL_RESIDENT (by default); a forced GPAD_KERNEL_PANEL where those
  *     panels do not apply; gpad_run_scaled with caller theta / beta tables.  Binding on a flat setup, binding
  *     with a Hessian bound and gpad_setup_hessian with a bound are GPAD_ERR_UNSUPPORTED at the bind.
@@ -241,10 +244,25 @@ int gpad_setup_hessian(gpad_handle_t h, const void* H);
  * NULL handle: GPAD_ERR_INVALID.  Valid any time after gpad_create.  A handle setting like an option: it
  * survives gpad_setup*, gpad_setup_infeasibility and unbinding, changes nothing while no bound is in force, and a
  * class-bound handle forwards it to every class whether set before or after gpad_setup_classes.  An entry
- * point rather than a GPAD_OPT_*: it selects the engine family of a run, as gpad_class_loop_fused does. */
+ * point rather than a GPAD_OPT_*: it selects the engine family of a run, as gpad_class_loop_fused does.
+ *
+ * gpad_infeasibility_loop_async(h, 1): with a bound in force GPAD_OPT_LOOP_ASYNC keeps its one-launch loop: the
+ * asynchronous loop kernels (one plant, per-pack plant maps, fleets of distinct matrices) run as variants that
+ * hold the certificate event after every fourth test of a pack's own solve.  A code 5 ends that solve like any
+ * other termination: the pack applies u = z*[0:nu], goes on to its next step (warm from z*, y* when warm) and
+ * the slot is refilled from the queue after its last step.  Reported kernel GPAD_KERNEL_LOOP; z, y, the
+ * trajectories, counts and codes are bit for bit the lockstep loop's.  Every other condition of
+ * GPAD_OPT_LOOP_ASYNC stands -- f32, n, m <= 208, nx + ns <= 64, AUTO or RESIDENT, no caller schedule tables;
+ * GPAD_OPT_LOOP_PANEL and the fused class loop first -- and a run it does not take falls back to the lockstep
+ * loop as before (on the resident certificate kernel with gpad_infeasibility_resident also on).  With tol <= 0
+ * or no bound the unbound kernels run.  A separate flag from gpad_infeasibility_resident (which keeps a bound
+ * GPAD_OPT_LOOP_ASYNC on the lockstep loop), with that function's rules otherwise: off by default, on = 0 / 1,
+ * anything else or a NULL handle GPAD_ERR_INVALID, valid any time after gpad_create, kept across gpad_setup*,
+ * gpad_setup_infeasibility and unbinding, forwarded to every class of a class-bound handle. */
 #define GPAD_CODE_INFEASIBLE 5
 int gpad_setup_infeasibility(gpad_handle_t h, double zbound);
 int gpad_infeasibility_resident(gpad_handle_t h, int on);
+int gpad_infeasibility_loop_async(gpad_handle_t h, int on);
 /* host only, no device: *margin = -(g'y) - zbound |G'y|_1 in fp64 on the caller's arrays (G m x n row-major,
  * g and y of m; dtype GPAD_DTYPE_*), -inf when some y_i is negative (or NaN).  > 0 exactly when y certifies
  * that no z with |z|_inf <= zbound satisfies G z <= g: an independent check of a code 5. */

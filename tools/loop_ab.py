@@ -55,7 +55,10 @@ fleet's own ratio beside it shows that part).
 with --signals), the lockstep loop with the battery bound bound (setup_infeasibility(problems.battery_zbound())),
 and with --panel "infeas_panel" ("sig_infeas_panel"), the panel loop with it; they are compared with each other
 bit for bit (outputs, counts, codes) instead of with the unbound loop, and every line gains `share_code5`,
-`share_capped`, `infeas_mean_iters_per_solve` and `<bound variant>_over_<variant>`.
+`share_capped`, `infeas_mean_iters_per_solve` and `<bound variant>_over_<variant>`.  One more bound variant,
+"infeas_async" ("sig_infeas_async"): the same handle with loop_async = 1 and the certificate in the asynchronous
+loop (gpad_infeasibility_loop_async; kernel "loop"), in the same bit-for-bit check; `infeas_async_over_infeas` is
+its rate over the bound lockstep loop's.
 
 --classes K [--signals] --infeas: two more variants with the battery bound bound
 (setup_infeasibility(problems.battery_zbound()), gpad_setup_infeasibility): "classes_infeas", the class binding
@@ -69,7 +72,12 @@ for every unbound variant.  Three more bound variants set the certificate beside
 then runs the resident kernel where a class holds at most 4 packs per CU, else the panels as "classes_infeas"),
 "fleet_infeas", the dims.shared = 0 fleet with the bound (the stream kernel), and "fleet_infeas_res", that fleet
 with the flag on (the resident kernel); all five bound variants are compared bit for bit, and
-`infeas_res_over_infeas` is the rate with the flag over the rate without, per binding.  --skip-plain (with
+`infeas_res_over_infeas` is the rate with the flag over the rate without, per binding.  Two more carry the
+certificate in the asynchronous loop (gpad_infeasibility_loop_async, loop_async = 1; kernel "loop"):
+"fleet_infeas_async", the bound dims.shared = 0 fleet on the fleet kernel's certificate twin, and
+"classes_infeas_async", the bound class binding with the option and the flag forwarded (K one-launch loops back to
+back); they join the bit-for-bit check of the bound variants, and `infeas_async_over_infeas_res` is their rate
+over the flag-on resident variant's, per binding.  --skip-plain (with
 --signals) leaves out the second set of handles without signals and `sig_over_plain`.
 
 Per batch and mode the two variants' x, z, y, xs, us and per-step iteration counts are compared first
@@ -119,11 +127,14 @@ def classes_ab(args):
                       "cus": torch.cuda.get_device_properties(0).multi_processor_count}))
     names = ("fleet", "classes", "classes_panel", "classes_async", "classes_fused") + (
         ("shared", "shared_panel") if K == 1 else ()) + (
-        ("classes_infeas", "classes_fused_infeas", "classes_infeas_res", "fleet_infeas", "fleet_infeas_res")
+        ("classes_infeas", "classes_fused_infeas", "classes_infeas_res", "fleet_infeas", "fleet_infeas_res",
+         "fleet_infeas_async", "classes_infeas_async")
         if args.infeas else ())
     want = {"classes_panel": "loop_panel", "classes_async": "loop", "classes_fused": "loop_classes",
-            "shared_panel": "loop_panel", "classes_fused_infeas": "loop_classes"}
-    INF = ("classes_infeas", "classes_fused_infeas", "classes_infeas_res", "fleet_infeas", "fleet_infeas_res")
+            "shared_panel": "loop_panel", "classes_fused_infeas": "loop_classes", "fleet_infeas_async": "loop",
+            "classes_infeas_async": "loop"}
+    INF = ("classes_infeas", "classes_fused_infeas", "classes_infeas_res", "fleet_infeas", "fleet_infeas_res",
+           "fleet_infeas_async", "classes_infeas_async")
     cus = torch.cuda.get_device_properties(0).multi_processor_count
     for B in args.batches:
         class_of = np.arange(B, dtype=np.int32) % K
@@ -149,6 +160,9 @@ def classes_ab(args):
                     del f
                     if name in INF:
                         s.set_infeasibility_resident(name.endswith("_res"))
+                        if name.endswith("_async"):
+                            s.set_option("loop_async", 1)
+                            s.set_infeasibility_loop_async(True)
                         s.setup_infeasibility(problems.battery_zbound())
                 elif name in ("shared", "shared_panel"):
                     s.setup(cls["ML"][0], cls["G"][0], L, n=n, m=m, batch=B, shared=True)
@@ -161,10 +175,12 @@ def classes_ab(args):
                     s.setup_plant(cls["PM"], cls["Pg"], g0=cls["g0"], A=cls["A"], B=cls["B"])
                     if with_sig:
                         s.setup_class_signals(cls["SM"], cls["Sg"], cls["E"])
-                    s.set_options(loop_panel=int(name == "classes_panel"), loop_async=int(name == "classes_async"))
+                    s.set_options(loop_panel=int(name == "classes_panel"),
+                                  loop_async=int(name in ("classes_async", "classes_infeas_async")))
                     s.set_class_loop_fused(name in ("classes_fused", "classes_fused_infeas"))
                     if name in INF:
                         s.set_infeasibility_resident(name.endswith("_res"))
+                        s.set_infeasibility_loop_async(name.endswith("_async"))
                         s.setup_infeasibility(problems.battery_zbound())
                 buf = dict(x=torch.empty(B, nx, device=dev), z=torch.empty(B, n, device=dev),
                            y=torch.empty(B, m, device=dev), xs=torch.empty(steps, B, nx, device=dev),
@@ -266,7 +282,10 @@ def classes_ab(args):
                     "infeas_max_iters_per_solve": int(its["classes_infeas"].max()),
                     **{f"{i}_over_{v}": round(rate[i] / rate[v], 3) for i in INF for v in var if v not in INF},
                     "infeas_res_over_infeas": {"classes": round(rate["classes_infeas_res"] / rate["classes_infeas"], 3),
-                                               "fleet": round(rate["fleet_infeas_res"] / rate["fleet_infeas"], 3)}}
+                                               "fleet": round(rate["fleet_infeas_res"] / rate["fleet_infeas"], 3)},
+                    "infeas_async_over_infeas_res": {
+                        "classes": round(rate["classes_infeas_async"] / rate["classes_infeas_res"], 3),
+                        "fleet": round(rate["fleet_infeas_async"] / rate["fleet_infeas_res"], 3)}}
                    if args.infeas else {}),
                 **extra}),
                 flush=True)
@@ -326,7 +345,8 @@ def main():
         # --infeas: the lockstep loop (and with --panel the panel loop) with the battery bound bound, on the plant
         # with signals when --signals is given (its loads make infeasible steps), else on the plain plant
         pre = "sig_" if args.signals else ""
-        infeas_names = ((pre + "infeas",) + ((pre + "infeas_panel",) if args.panel else ())) if args.infeas else ()
+        infeas_names = ((pre + "infeas",) + ((pre + "infeas_panel",) if args.panel else ()) +
+                        (pre + "infeas_async",)) if args.infeas else ()
         if args.signals:
             rng = np.random.default_rng([B, 1])
             sig = torch.from_numpy(np.concatenate([rng.uniform(-5, 5, (steps, B, 1)),
@@ -344,6 +364,8 @@ def main():
             if args.panel:  # (left alone otherwise: the tool also runs on builds older than the option)
                 s.set_option("loop_panel", int(name.endswith("panel")))
             if name in infeas_names:
+                if name.endswith("infeas_async"):
+                    s.set_infeasibility_loop_async(True)
                 s.setup_infeasibility(problems.battery_zbound())
             if name == "async_1wg":
                 s.set_option("duo_max_grid", cus)
@@ -413,7 +435,9 @@ def main():
                     "share_capped": {k: round(float(((cds[k] == 0) & (its[k] == mode["N"])).mean()), 4) for k in var},
                     "infeas_mean_iters_per_solve": round(float(its[infeas_names[0]].mean()), 1),
                     **{f"{i}_over_{v}": round(rate[i] / rate[v], 3) for i in infeas_names for v in var
-                       if v not in infeas_names and v.startswith("sig_") == bool(pre)}} if args.infeas else {}),
+                       if v not in infeas_names and v.startswith("sig_") == bool(pre)},
+                    "infeas_async_over_infeas": round(rate[pre + "infeas_async"] / rate[pre + "infeas"], 3)}
+                   if args.infeas else {}),
                 **({"sig_mean_iters_per_solve": round(float(its["sig_async"].mean()), 1),
                     "sig_async_over_sig_lockstep": round(rate["sig_async"] / rate["sig_lockstep"], 3),
                     "sig_over_plain": {"lockstep": round(rate["sig_lockstep"] / rate["lockstep"], 3),
