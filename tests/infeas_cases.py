@@ -6,6 +6,9 @@ inside the box; an ``edge`` draw moves one cell to within 0.05 of a bound and po
 that the horizon cannot keep xmin <= x <= xmax with |u| <= 0.3: the QP is infeasible.  The other draws keep
 every cell at least 0.25 away from the bound the load pushes to, which the horizon cannot reach (a step
 under load moves a cell by 0.0126), so they are feasible.  R = 0.3 = problems.battery_zbound().
+
+The wide inputs of tests/test_infeasible_panels.py (slab_*) are synthetic QPs of any shape in which two rows of G
+are opposite: their right-hand sides make a slab around a witness or contradict each other (R = SLAB_R).
 """
 from __future__ import annotations
 
@@ -85,3 +88,118 @@ def loop_inputs(batch_size=16, steps=6):
         S[:, b, 0] = 0.0
         S[bad[b]:, b, 0] = sg * LOAD
     return SimpleNamespace(X0=X, S=S, bad=bad, steps=steps, batch=batch_size)
+
+
+# ------------------------------------------------- wide mixed batches (tests/test_infeasible_panels.py)
+SLAB_R = 10.0  # |zf|_inf <= 0.5, and the feasible instances' solutions stay below it (asserted on the CPU)
+
+
+def slab_rows(m):
+    """Row i in row tile 0 and row j in the last row tile of G."""
+    return (min(3, m - 3), m - 2 if (m - 2) // 16 == (m - 1) // 16 else m - 1)
+
+
+@functools.lru_cache(maxsize=None)
+def slab_qp(n, m, seed, rows=None):
+    """problems.synthetic_qp(n, m, seed=seed) with G[j] = -G[i]; ML and L recomputed from the new G."""
+    i, j = rows or slab_rows(m)
+    qp = problems.synthetic_qp(n, m, seed=seed)
+    G = qp.G.copy()
+    G[j] = -G[i]
+    ML = np.linalg.inv(qp.H) @ G.T
+    return problems.QP(ML=ML, M=None, G=G, g=None, L=float(np.linalg.norm(G @ ML, "fro")), H=qp.H)
+
+
+@functools.lru_cache(maxsize=None)
+def slab_batch(n, m, batch, seed, rows=None, bad=None):
+    """A mixed batch with a known answer on the matrices of slab_qp: rows i and j of G are opposite, so the two
+    of them bound G[i] z from both sides.  Every instance draws zf ~ U(-0.5, 0.5)^n, q ~ N(0, 1)^n and
+    g = G zf + U(0.1, 1).  A feasible instance's row j is -G[i] zf + U(0.1, 1): a slab of positive width with the
+    witness zf inside the box.  An infeasible one's (``bad``: a tuple of instances, default every second) is
+    g[j] = -g[i] - 1: no z meets both rows, and y = e_i + e_j certifies it for any R.  Returns the QP (ML, G, L
+    shared), zf [batch][n], the infeasible mask, M = inv(H) q [batch][n] and g [batch][m], all fp64."""
+    i, j = rows or slab_rows(m)
+    qp = slab_qp(n, m, seed, (i, j))
+    mask = np.zeros(batch, bool)
+    mask[list(range(1, batch, 2)) if bad is None else list(bad)] = True
+    Hinv = np.linalg.inv(qp.H)
+    zf, M, g = np.empty((batch, n)), np.empty((batch, n)), np.empty((batch, m))
+    for k in range(batch):  # a generator per instance: a smaller batch is a prefix of a larger one
+        rng = np.random.default_rng([seed, n, m, k])
+        zf[k], M[k] = rng.uniform(-0.5, 0.5, n), Hinv @ rng.normal(0.0, 1.0, n)
+        g[k] = qp.G @ zf[k] + rng.uniform(0.1, 1.0, m)  # (row j: G[j] zf = -G[i] zf)
+    g[mask, j] = -g[mask, i] - 1.0
+    return SimpleNamespace(qp=qp, n=n, m=m, rows=(i, j), zf=zf, bad=mask, M=M, g=g)
+
+
+@functools.lru_cache(maxsize=None)
+def slab_plant(n=70, m=130, nx=5, nu=2, rows=None, packs=16):
+    """test_loop_async.synthetic(n, m, nx, nu) with rows i, j opposite in the matrices and the maps (G[j] = -G[i],
+    Pg[j] = -Pg[i], g0[j] = -g0[i]; ML and L recomputed from the new G) and one signal on row j (ns = 1,
+    Sg[j, 0] = 1, no other signal map), so that g_i(x, s) + g_j(x, s) = s at every state: a positive s is the
+    width of a slab, s = -1 leaves no z for the two rows, and y = e_i + e_j certifies that for any R."""
+    import test_loop_async as tla
+    i, j = rows or slab_rows(m)
+    p = tla.synthetic(n, m, nx, nu, packs=packs)
+    qp = p.qp
+    G, Pg, g0 = qp.G.copy(), p.Pg.copy(), np.array(p.g0, np.float64).reshape(m)
+    G[j], Pg[j], g0[j] = -G[i], -Pg[i], -g0[i]
+    Sg = np.zeros((m, 1))
+    Sg[j, 0] = 1.0
+    ML = np.linalg.inv(qp.H) @ G.T
+    nq = problems.QP(ML=ML, M=None, G=G, g=None, L=float(np.linalg.norm(G @ ML, "fro")), H=qp.H)
+    return SimpleNamespace(qp=nq, n=n, m=m, rows=(i, j), PM=p.PM, Pg=Pg, M0=np.array(p.M0, np.float64).reshape(n),
+                           g0=g0, Sg=Sg, A=p.A, B=p.B, nx=nx, nu=nu, ns=1, X0=p.X0)
+
+
+SLAB_BAD = {3: (2, 5), 10: (3, 5), 6: (0, 1)}  # pack: the steps [from, to) at which its signal is -1
+
+
+def slab_loop_inputs(width, batch_size=16, steps=5):
+    """The script of the slab plant's closed loop: S[t, b, 0] = width, a slab every pack can stay in, except
+    S = -1 where SLAB_BAD says so: packs 3 and 10 turn infeasible at steps 2 and 3 and stay so, pack 6 is
+    infeasible at step 0 only.  S [steps][batch][1], want [steps][batch]: the solves that must end 5."""
+    S = np.full((steps, batch_size, 1), float(width))
+    want = np.zeros((steps, batch_size), bool)
+    for b, (t0, t1) in SLAB_BAD.items():
+        if b < batch_size:
+            want[t0:t1, b] = True
+    S[want, 0] = -1.0
+    return SimpleNamespace(S=S, want=want, steps=steps, batch=batch_size)
+
+
+def slab_loop_reference(pl, L, X0, S, N=N, tol=TOL, R=SLAB_R, warm=False):
+    """The fp64 reference closed loop of every pack: loop_ref64's plant arithmetic around infeas_ref64.solve.
+    ``pl``: one slab_plant, or a list with every pack's own (a class fleet).
+    -> x, z, y [batch][.], xs, us [steps][batch][.], it, cd, nominated [steps][batch]."""
+    import loop_ref64 as lr
+    steps, batch = S.shape[:2]
+    plants = list(pl) if isinstance(pl, (list, tuple)) else [pl] * batch
+    pl = plants[0]
+    out = SimpleNamespace(x=np.zeros((batch, pl.nx)), z=np.zeros((batch, pl.n)), y=np.zeros((batch, pl.m)),
+                          xs=np.zeros((steps, batch, pl.nx)), us=np.zeros((steps, batch, pl.nu)),
+                          it=np.zeros((steps, batch), np.int32), cd=np.zeros((steps, batch), np.int32),
+                          nominated=np.zeros((steps, batch), np.int32))
+    for b in range(batch):
+        pl = plants[b]
+        x, z, y = np.asarray(X0[b], np.float64), None, None
+        for t in range(steps):
+            s = np.asarray(S[t, b], np.float64)
+            M = lr.affine(pl.PM, pl.M0, x, None, s)
+            g = lr.affine(pl.Pg, pl.g0, x, pl.Sg, s)
+            r = ref.solve(pl.qp.ML, M, pl.qp.G, g, L, N, tol, R, np.float64, z0=z if warm else None,
+                          y0=y if warm else None)
+            z, y = r.z, r.y
+            out.xs[t, b], out.us[t, b] = x, z[:pl.nu]
+            out.it[t, b], out.cd[t, b], out.nominated[t, b] = r.it, r.code, r.nominated
+            x = lr.plant_step(pl.A, pl.B, x, z[:pl.nu], None, s)
+        out.x[b], out.z[b], out.y[b] = x, z, y
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def slab_reference(n, m, batch, seed, dtype=np.float64):
+    """infeas_ref64.solve of every instance of slab_batch(n, m, batch, seed) with R = SLAB_R (computed once, shared
+    by the tests, never modified)."""
+    b = slab_batch(n, m, batch, seed)
+    return [ref.solve(b.qp.ML, b.M[k], b.qp.G, b.g[k], b.qp.L, N, TOL, SLAB_R, dtype) for k in range(batch)]
