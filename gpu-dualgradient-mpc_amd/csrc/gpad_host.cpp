@@ -223,6 +223,7 @@ int gpad_destroy(gpad_handle_t h) {
         h->work.release();
         h->counters.release();
         h->pwork.release();
+        h->lipwork.release();
         h->status.release();
         h->own_plant.release();
         h->state.release();

@@ -150,6 +150,7 @@ struct gpad_handle_s {
     DevBuf theta, beta;
     int sched_len = 0, sched_kind = -1, sched_dtype = -1;
     DevBuf work, counters, pwork;
+    DevBuf lipwork;      // gpad_lipschitz: the squaring buffers, norm slots and staged operands of one chunk
     std::vector<int> h_counts;
     // run status block on the device (RunStatus above): the error word the kernels report into and
     // the per-workgroup maxima of |g|, the certification floor's data term (include/gpad.h gpad_run)

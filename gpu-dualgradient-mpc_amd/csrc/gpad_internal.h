@@ -351,6 +351,25 @@ hipError_t launch_precompute(int n, int m, int nf, const double* H, long long sH
                              const double* f, long long sF, double* work, double* ML, double* gP, double* L, int b0,
                              int count, hipStream_t s);
 hipError_t launch_apply_inv(int n, int batch, const double* Hinv, const double* f, double* gP, hipStream_t s);
+// gpad_lipschitz (gpad_lipschitz.hip): C = (s A)(s B) in fp64 per instance, A K x P and B P x K row-major, f32 or
+// f64; s = 1 (in_slots null) or 1 / sqrt(sum of the instance's in_slots).  Writes C [count][K][K] and, per 64 x 64
+// tile of C, its sum of squares into out_slots [count][slot_stride]; grid lip_tiles(K)^2 x count workgroups.
+constexpr int kLipThreads = 256;  // four waves, a 32 x 32 quarter of the tile each
+constexpr int kLipTile = 64;
+constexpr int kLipKc = 16;        // values of k staged in LDS at a time
+struct LipGemmArgs {
+    const void* A;
+    const void* B;
+    long long sA, sB;             // elements between instances (0: shared)
+    long long lda, ldb, P;
+    int K;
+    const double* in_slots;
+    double* C;
+    double* out_slots;
+    int nslots, slot_stride;
+};
+int lip_tiles(int K);
+hipError_t launch_lip_gemm(const LipGemmArgs& a, bool f32_in, int count, hipStream_t s);
 hipError_t launch_accumulate_iters(const int* iters, long long count, long long* acc, hipStream_t s);
 // part[b] = max |g_i| over workgroup b's share, b < absmax_blocks(count), the remaining slots zeroed:
 // per-workgroup maxima, no atomics (the host reduces them when it reads the stats)

@@ -1,7 +1,7 @@
 // gpad_setup.cpp -- binding a problem to a handle: the packed device copies of the constant matrices
 // (k-major -ML and G/L, the MFMA fragment images), the Hessian, the flat battery form, the theta/beta
-// table and the one-time QP precompute.  Replaces the set-up half of the reference's host driver
-// (main.cu:79-203: file read, 9 cudaMallocs, H2D copies).
+// table, the one-time QP precompute and the step-bound estimate (gpad_lipschitz).  Replaces the set-up
+// half of the reference's host driver (main.cu:79-203: file read, 9 cudaMallocs, H2D copies).
 #include <algorithm>
 #include <cmath>
 
@@ -167,7 +167,193 @@ int ensure_schedule(gpad_handle_t h, int N, const void* theta_in, const void* be
     return GPAD_OK;
 }
 
+// ---- gpad_lipschitz: L >= rho(G ML) by repeated squaring (include/gpad.h; kernel in gpad_lipschitz.hip) ----
+namespace {
+
+constexpr size_t kLipWorkCap = (size_t)1 << 30;  // bytes of handle workspace one chunk of instances may take
+constexpr int kLipMaxChunk = 1024;               // ... and instances per launch (the grid's z extent)
+constexpr int kLipMaxK = 4096;
+constexpr int kLipMaxSquarings = 16;
+// L is rounded up by this relative margin.  The chain's fp64 rounding is of order (K + k) 2^-53 relative -- a norm
+// per squaring, each a sum of K^2 squares of sums of K products, and the k + 1 logarithms -- below 1e-12 for every
+// K <= 4096; the exact chain is >= rho(S), the computed one came out 2e-15 under it in one case.
+constexpr double kLipMargin = 1e-9;
+
+// smallest k with K^(1 / 2^(k+1)) <= 1 + rtol
+int lip_squarings(int K, double rtol) {
+    const double lim = std::log1p(rtol), lk = std::log((double)K);
+    int k = 0;
+    while (k < kLipMaxSquarings && std::ldexp(lk, -(k + 1)) > lim) ++k;
+    return k;
+}
+
+// the order of gpad_lipschitz.hip lip_slot_sum_dev: 256 strided partial sums, then the halving tree
+double lip_slot_sum(const double* slots, int count) {
+    double red[gpad::kLipThreads];
+    for (int t = 0; t < gpad::kLipThreads; ++t) {
+        double p = 0.0;
+        for (int i = t; i < count; i += gpad::kLipThreads) p += slots[i];
+        red[t] = p;
+    }
+    for (int s = gpad::kLipThreads / 2; s > 0; s >>= 1)
+        for (int t = 0; t < s; ++t) red[t] += red[t + s];
+    return red[0];
+}
+
+inline double lip_scale(double ssq) { return (ssq > 0.0 && std::isfinite(ssq)) ? 1.0 / std::sqrt(ssq) : 0.0; }
+
+// ssq[j] = |B_{j-1}^2|_F^2 (j = 0: |S|_F^2)  ->  L = exp(c_k / 2^k) (1 + margin), c_0 = log |S|_F, c_{j+1} = 2 c_j + log |.|_F
+int lip_finish(const char* fn, const double* ssq, int k, int inst, double* L) {
+    double c = 0.0;
+    for (int j = 0; j <= k; ++j) {
+        const double nj = std::sqrt(ssq[j]);
+        if (!std::isfinite(nj))
+            return fail(GPAD_ERR_INVALID, std::string(fn) + ": instance " + std::to_string(inst) +
+                                              ": a norm of the chain is not finite (NaN, infinity or overflow in ML, G)");
+        if (nj == 0.0) {
+            *L = 0.0;
+            return GPAD_OK;
+        }
+        c = 2.0 * c + std::log(nj);
+    }
+    *L = std::exp(std::ldexp(c, -k)) * (1.0 + kLipMargin);
+    return GPAD_OK;
+}
+
+int lip_validate(const char* fn, int n, int m, int batch, int dtype, const void* ML, const void* G, double* rtol,
+                 const double* L) {
+    if (n <= 0 || m <= 0 || batch <= 0 || !ML || !G || !L || (dtype != GPAD_DTYPE_F32 && dtype != GPAD_DTYPE_F64))
+        return fail(GPAD_ERR_INVALID, std::string(fn) + ": bad arguments");
+    if (!(*rtol >= 0.0) || *rtol > 1.0) return fail(GPAD_ERR_INVALID, std::string(fn) + ": rtol must be in [0, 1]");
+    if (*rtol == 0.0) *rtol = 0.01;
+    if (std::min(n, m) > kLipMaxK)
+        return fail(GPAD_ERR_UNSUPPORTED, std::string(fn) + ": min(n, m) > " + std::to_string(kLipMaxK));
+    return GPAD_OK;
+}
+
+// one pair on the host: plain fp64 loops, every sum ascending in k
+int lip_host_one(int n, int m, int dtype, const void* ML, const void* G, size_t off, int k, int inst, double* L) {
+    const bool f64 = dtype == GPAD_DTYPE_F64;
+    const size_t nm = (size_t)n * m;
+    std::vector<double> ml(nm), g(nm);
+    for (size_t i = 0; i < nm; ++i) {
+        ml[i] = f64 ? ((const double*)ML)[off + i] : (double)((const float*)ML)[off + i];
+        g[i] = f64 ? ((const double*)G)[off + i] : (double)((const float*)G)[off + i];
+    }
+    const bool small_n = n <= m;  // S = ML G (n x n), else G ML (m x m)
+    const double* A = small_n ? ml.data() : g.data();
+    const double* B = small_n ? g.data() : ml.data();
+    const size_t K = (size_t)std::min(n, m), P = (size_t)std::max(n, m);
+    std::vector<double> cur(K * K, 0.0), nxt(K * K), ssq((size_t)k + 1, 0.0);
+    auto gemm = [&](const double* a, const double* b, size_t p, double* c) {  // c = a b, a K x p, b p x K
+        std::fill(c, c + K * K, 0.0);
+        for (size_t i = 0; i < K; ++i)
+            for (size_t kk = 0; kk < p; ++kk) {
+                const double aik = a[i * p + kk];
+                for (size_t j = 0; j < K; ++j) c[i * K + j] += aik * b[kk * K + j];
+            }
+        double s = 0.0;
+        for (size_t i = 0; i < K * K; ++i) s += c[i] * c[i];
+        return s;
+    };
+    ssq[0] = gemm(A, B, P, cur.data());
+    for (int j = 1; j <= k; ++j) {
+        const double s = lip_scale(ssq[j - 1]);
+        for (double& v : cur) v *= s;
+        ssq[j] = gemm(cur.data(), cur.data(), K, nxt.data());
+        cur.swap(nxt);
+    }
+    return lip_finish("gpad_lipschitz_host", ssq.data(), k, inst, L);
+}
+
+}  // namespace
+
 extern "C" {
+
+int gpad_lipschitz(gpad_handle_t h, int n, int m, int batch, int shared, int dtype, int memory, const void* ML,
+                   const void* G, double rtol, double* L) {
+    return gpad::abi_guard("gpad_lipschitz", [&]() -> int {
+        if (!h) return fail(GPAD_ERR_INVALID, "gpad_lipschitz: null handle");
+        if (memory != GPAD_MEM_HOST && memory != GPAD_MEM_DEVICE)
+            return fail(GPAD_ERR_INVALID, "gpad_lipschitz: bad memory kind");
+        int rc = lip_validate("gpad_lipschitz", n, m, batch, dtype, ML, G, &rtol, L);
+        if (rc) return rc;
+        HIP_TRY(hipSetDevice(h->device));
+        const bool host = memory == GPAD_MEM_HOST, small_n = n <= m;
+        const int nmat = shared ? 1 : batch, K = std::min(n, m);
+        const int k = lip_squarings(K, rtol), nslots = gpad::lip_tiles(K) * gpad::lip_tiles(K);
+        const size_t es = esize(dtype), nm = (size_t)n * m, kk = (size_t)K * K;
+        // per instance: the two K x K buffers the squarings alternate between, a slot row per launch, and for host
+        // operands their staged copies
+        const size_t per = sizeof(double) * (2 * kk + (size_t)(k + 1) * nslots) + (host ? 2 * nm * es : 0);
+        const int chunk = (int)std::max<size_t>(1, std::min<size_t>({(size_t)nmat, (size_t)kLipMaxChunk, kLipWorkCap / per}));
+        if ((rc = h->lipwork.ensure(per * chunk))) return rc;
+        double* buf[2] = {(double*)h->lipwork.p, (double*)h->lipwork.p + kk * chunk};
+        double* slots = buf[1] + kk * chunk;  // [k + 1][chunk][nslots]
+        char* stML = (char*)(slots + (size_t)(k + 1) * chunk * nslots);
+        char* stG = stML + nm * es * chunk;
+        const size_t slot_row = (size_t)chunk * nslots;
+        std::vector<double> hs((size_t)(k + 1) * slot_row), ssq((size_t)k + 1), Lh((size_t)nmat);
+        for (int b0 = 0; b0 < nmat; b0 += chunk) {
+            const int cnt = std::min(chunk, nmat - b0);
+            const char* dML = (const char*)ML + (size_t)b0 * nm * es;
+            const char* dG = (const char*)G + (size_t)b0 * nm * es;
+            if (host) {
+                HIP_TRY(hipMemcpyAsync(stML, dML, nm * es * cnt, hipMemcpyHostToDevice, h->stream));
+                HIP_TRY(hipMemcpyAsync(stG, dG, nm * es * cnt, hipMemcpyHostToDevice, h->stream));
+                dML = stML;
+                dG = stG;
+            }
+            gpad::LipGemmArgs a{};
+            a.A = small_n ? dML : dG;
+            a.B = small_n ? dG : dML;
+            a.sA = a.sB = (long long)nm;
+            a.lda = small_n ? m : n;
+            a.ldb = small_n ? n : m;
+            a.P = std::max(n, m);
+            a.K = K;
+            a.in_slots = nullptr;
+            a.C = buf[0];
+            a.out_slots = slots;
+            a.nslots = a.slot_stride = nslots;
+            HIP_TRY(gpad::launch_lip_gemm(a, dtype == GPAD_DTYPE_F32, cnt, h->stream));
+            for (int j = 1; j <= k; ++j) {  // buf[(j-1) & 1] squared into buf[j & 1]
+                a.A = a.B = buf[(j - 1) & 1];
+                a.sA = a.sB = (long long)kk;
+                a.lda = a.ldb = a.P = K;
+                a.in_slots = slots + (size_t)(j - 1) * slot_row;
+                a.C = buf[j & 1];
+                a.out_slots = slots + (size_t)j * slot_row;
+                HIP_TRY(gpad::launch_lip_gemm(a, false, cnt, h->stream));
+            }
+            HIP_TRY(hipMemcpyAsync(hs.data(), slots, sizeof(double) * hs.size(), hipMemcpyDeviceToHost, h->stream));
+            HIP_TRY(hipStreamSynchronize(h->stream));
+            for (int i = 0; i < cnt; ++i) {
+                for (int j = 0; j <= k; ++j) ssq[j] = lip_slot_sum(hs.data() + (size_t)j * slot_row + (size_t)i * nslots, nslots);
+                if ((rc = lip_finish("gpad_lipschitz", ssq.data(), k, b0 + i, &Lh[b0 + i]))) return rc;
+            }
+        }
+        if (host) {
+            std::copy(Lh.begin(), Lh.end(), L);
+        } else {
+            HIP_TRY(hipMemcpyAsync(L, Lh.data(), sizeof(double) * nmat, hipMemcpyHostToDevice, h->stream));
+            HIP_TRY(hipStreamSynchronize(h->stream));
+        }
+        return GPAD_OK;
+    });
+}
+
+int gpad_lipschitz_host(int n, int m, int batch, int shared, int dtype, const void* ML, const void* G, double rtol,
+                        double* L) {
+    return gpad::abi_guard("gpad_lipschitz_host", [&]() -> int {
+        int rc = lip_validate("gpad_lipschitz_host", n, m, batch, dtype, ML, G, &rtol, L);
+        if (rc) return rc;
+        const int nmat = shared ? 1 : batch, k = lip_squarings(std::min(n, m), rtol);
+        for (int b = 0; b < nmat; ++b)
+            if ((rc = lip_host_one(n, m, dtype, ML, G, (size_t)b * n * m, k, b, &L[b]))) return rc;
+        return GPAD_OK;
+    });
+}
 
 int gpad_setup(gpad_handle_t h, const gpad_dims_t* d, const void* ML, const void* G, double L) {
     return gpad::abi_guard("gpad_setup", [&]() -> int {

@@ -50,6 +50,7 @@ EXPORTS = [
     "gpad_class_loop_fused", "gpad_class_loop_deal", "gpad_setup_class_signals",
     "gpad_setup_infeasibility", "gpad_farkas_margin", "gpad_infeasibility_resident",
     "gpad_infeasibility_loop_async",
+    "gpad_lipschitz", "gpad_lipschitz_host",
 ]
 GROUP_RCCL, GROUP_PEER = 1, 2
 
@@ -223,6 +224,11 @@ def load(path: str | None = None) -> C.CDLL:
     if hasattr(L, "gpad_infeasibility_loop_async"):  # (added within 0.6; absent from older builds under GPAD_LIB_TOLERANT)
         L.gpad_infeasibility_loop_async.argtypes = [vp, i]
         L.gpad_infeasibility_loop_async.restype = i
+    if hasattr(L, "gpad_lipschitz"):  # (added within 0.6; absent from older builds under GPAD_LIB_TOLERANT)
+        L.gpad_lipschitz.argtypes = [vp, i, i, i, i, i, i, cvp, cvp, d, vp]
+        L.gpad_lipschitz.restype = i
+        L.gpad_lipschitz_host.argtypes = [i, i, i, i, i, cvp, cvp, d, C.POINTER(d)]
+        L.gpad_lipschitz_host.restype = i
     L.gpad_datafile_read.argtypes = [C.c_char_p, i, C.POINTER(DataFile)]
     L.gpad_datafile_write.argtypes = [C.c_char_p, i, C.POINTER(DataFile)]
     L.gpad_datafile_free.argtypes = [C.POINTER(DataFile)]

@@ -355,6 +355,23 @@ class GpadSolver:
                                        _ptr(ML), opt(gP), _ptr(L)), "gpad_precompute")
         return ML, gP, (float(L[0]) if shared else L)
 
+    def lipschitz(self, ML, G, *, shared: bool = True, rtol: float = 0.01):
+        """gpad_lipschitz: an upper bound of lambda_max(G ML), the smallest L ``setup`` may be given, within a
+        factor 1 + rtol of it for ML = inv(H) G' (include/gpad.h), in fp64 on the device.  shared: ML (n, m),
+        G (m, n) -> float; else ML [batch][n][m], G [batch][m][n] -> L [batch] (a fleet on one setup passes
+        ``L.max()``).  float32 or float64, numpy in -> numpy out; torch device tensors in -> torch out."""
+        ML, G, n, m, batch = _lipschitz_operands(ML, G, shared)
+        if _is_torch(ML):
+            import torch
+            L = torch.empty(batch, dtype=torch.float64, device=ML.device)
+            mem = _lib.MEM_DEVICE
+        else:
+            L = np.empty(batch)
+            mem = _lib.MEM_HOST
+        check(self.lib.gpad_lipschitz(self.h, n, m, batch, 1 if shared else 0, _dtype_code(ML), mem, _ptr(ML), _ptr(G),
+                                      float(rtol), _ptr(L)), "gpad_lipschitz")
+        return float(L[0]) if shared else L
+
     def setup_plant(self, PM, Pg, *, M0=None, g0=None, A=None, B=None) -> None:
         """Bind M(x) = M0 + PM x, g(x) = g0 + Pg x and (optionally) x+ = A x + B u.
         Same dtype / memory kind as the preceding ``setup``.
@@ -587,6 +604,38 @@ def farkas_margin(G, g, y, zbound: float) -> float:
     check(lib.gpad_farkas_margin(n, m, _dtype_code(G), _ptr(G), _ptr(g), _ptr(y), float(zbound), C.byref(out)),
           "gpad_farkas_margin")
     return out.value
+
+
+def _lipschitz_operands(ML, G, shared: bool):
+    """ML, G as contiguous arrays of one dtype (float32 kept, anything else float64) and (n, m, batch)."""
+    if _is_torch(ML) != _is_torch(G):
+        raise TypeError("lipschitz: ML and G must both be numpy arrays or both torch tensors")
+    if _is_torch(ML):
+        import torch
+        dt = torch.float32 if ML.dtype == torch.float32 and G.dtype == torch.float32 else torch.float64
+        ML, G = ML.to(dt).contiguous(), G.to(dt).contiguous()
+    else:
+        ML, G = np.asarray(ML), np.asarray(G)
+        dt = np.float32 if ML.dtype == np.float32 and G.dtype == np.float32 else np.float64
+        ML, G = np.ascontiguousarray(ML, dt), np.ascontiguousarray(G, dt)
+    want = 2 if shared else 3
+    if ML.ndim != want or G.ndim != want:
+        raise ValueError(f"lipschitz: ML and G need {want} axes with shared={shared}")
+    n, m = int(ML.shape[-2]), int(ML.shape[-1])
+    if tuple(G.shape[-2:]) != (m, n) or (not shared and G.shape[0] != ML.shape[0]):
+        raise ValueError(f"lipschitz: ML is {tuple(ML.shape)}, so G must be {tuple(ML.shape[:-2]) + (m, n)}")
+    return ML, G, n, m, (1 if shared else int(ML.shape[0]))
+
+
+def lipschitz_host(ML, G, *, shared: bool = True, rtol: float = 0.01):
+    """gpad_lipschitz_host: ``GpadSolver.lipschitz`` in plain fp64 loops on host arrays -- no handle, no GPU.
+    The check of the device kernel, and the way to a tight L on a box without one."""
+    lib = _lib.load()
+    ML, G, n, m, batch = _lipschitz_operands(np.asarray(ML), np.asarray(G), shared)
+    L = np.empty(batch)
+    check(lib.gpad_lipschitz_host(n, m, batch, 1 if shared else 0, _dtype_code(ML), _ptr(ML), _ptr(G), float(rtol),
+                                  L.ctypes.data_as(C.POINTER(C.c_double))), "gpad_lipschitz_host")
+    return float(L[0]) if shared else L
 
 
 def schedule(N: int, kind: int = _lib.SCHEDULE_MATLAB):

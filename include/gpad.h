@@ -41,7 +41,7 @@ extern "C" {
                               * gpad_setup_infeasibility, gpad_farkas_margin and the termination code
                               * GPAD_CODE_INFEASIBLE (5), returned only with a bound in force;
                               * gpad_infeasibility_resident and gpad_infeasibility_loop_async (off by
-                              * default: no routing changes) */
+                              * default: no routing changes); gpad_lipschitz, gpad_lipschitz_host */
 
 /* status codes */
 #define GPAD_OK 0
@@ -319,6 +319,37 @@ int gpad_run_scaled(gpad_handle_t h, void* z0, void* y0, const void* gP, const v
  * Synchronous.  The outputs feed gpad_setup (ML, A as G, L) and gpad_run (gP as M). */
 int gpad_precompute(gpad_handle_t h, int n, int m, int batch, int shared, int memory, const double* H,
                     const double* A, const double* f, double* ML, double* gP, double* L);
+
+/* ---- a tight step bound ------------------------------------------------------------------
+ * GPAD converges for L >= lambda_max(G H^-1 G') = rho(G ML), and its iteration count grows like sqrt(L).
+ * gpad_precompute's L = ||H||_F^2 is the reference's choice (acceldualgrad.m:11), not a bound on that
+ * quantity.  gpad_lipschitz returns an upper bound of rho(G ML) within a factor 1 + rtol of it (for
+ * ML = H^-1 G', H symmetric positive definite), in fp64 on the device: with K = min(n, m) and S = ML G
+ * (n <= m) or G ML, both of which have G ML's non-zero eigenvalues,
+ *     rho(S) <= ||S^p||_F^(1/p) <= K^(1/(2p)) rho(S),      p = 2^k,
+ * the left inequality for every square S, the right one for S similar to a symmetric positive semi-definite
+ * matrix of rank <= K.  S^p is reached by k squarings, each normalised by its Frobenius norm, k the smallest
+ * count with K^(1/2^(k+1)) <= 1 + rtol (at most 16); the result is rounded up by a relative 1e-9, which
+ * covers the rounding of the chain.  It is an upper bound for any pair ML, G; only its tightness needs the
+ * structure above.
+ *   ML n x m, G m x n, row-major, dtype GPAD_DTYPE_F32 or _F64 (widened to fp64 on load);
+ *   shared = 1: one pair, L[1] (batch is not read beyond batch >= 1); shared = 0: ML [batch][n][m],
+ *   G [batch][m][n], L [batch] -- a fleet that shares one gpad_setup passes the maximum;
+ *   memory = GPAD_MEM_HOST or GPAD_MEM_DEVICE for ML, G and L (device: on the handle's stream);
+ *   rtol in [0, 1], 0 meaning 0.01; anything else (NaN included) GPAD_ERR_INVALID;
+ *   min(n, m) > 4096: GPAD_ERR_UNSUPPORTED.
+ * A pair whose S, or one of its squares, is zero gives L = 0 (gpad_setup rejects it).  A norm that is not
+ * finite (a NaN or infinity in ML or G, overflow) returns GPAD_ERR_INVALID, gpad_last_error naming the
+ * instance.  Synchronous.  Deterministic: no floating-point atomics, so L[b] has the same bits on every run,
+ * for host and device operands, and alone or at any position of a batch.  Instances are processed in chunks
+ * whose workspace (kept on the handle, freed by gpad_destroy) stays within 1 GiB and 1024 instances, a single
+ * instance excepted; k + 1 launches per chunk.
+ * gpad_lipschitz_host: the same recursion in plain fp64 loops on host arrays, every sum ascending -- no
+ * handle, no device.  It agrees with gpad_lipschitz to fp64 summation order (about 1e-13 relative). */
+int gpad_lipschitz(gpad_handle_t h, int n, int m, int batch, int shared, int dtype, int memory, const void* ML,
+                   const void* G, double rtol, double* L);
+int gpad_lipschitz_host(int n, int m, int batch, int shared, int dtype, const void* ML, const void* G, double rtol,
+                        double* L);
 
 /* ---- per-state QP data and closed-loop MPC -------------------
  * For an LTI plant the state-dependent QP data are affine in the state x (nx):
