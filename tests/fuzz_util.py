@@ -341,22 +341,31 @@ def run_value_case(cfg: dict, oracle, sample: int = 16) -> dict:
     return dict(ok=True, checked=checked, kernels=[st["kernel"]], codes=sorted(set(int(c) for c in codes)))
 
 
-def draw_loop_case(rng: np.random.Generator) -> dict:
+LOOP_ENGINES = ("lockstep", "loop_async", "loop_panel")
+
+
+def draw_loop_case(rng: np.random.Generator, engines=("lockstep",)) -> dict:
     """The closed-loop MPC runner (gpad_closed_loop, gpad.m:79-95): a battery plant of n_u cells over
-    a horizon N, a batch of packs from random states, several receding-horizon steps."""
+    a horizon N, a batch of packs from random states, several receding-horizon steps.  engines: the
+    loop engines to draw from (LOOP_ENGINES for all three), drawn after everything else, so a seed gives
+    the same case whatever the list and the default is the lockstep case it always was."""
     n_u = int(rng.integers(1, 5))
     Nh = int(rng.integers(2, 13))
     tol_mode = bool(rng.random() < 0.5)
     kernels = ["auto", "auto", "panel", "stream"] + (["resident"] if 4 * n_u * Nh + 2 * Nh <= 208 else [])
-    return dict(loop=True, n_u=n_u, Nh=Nh, batch=int(rng.choice([1, 3, 17, 64, 300, 1100, 4100])),
-                steps=int(rng.integers(1, 11)), N=(2000 if tol_mode else int(rng.integers(1, 121))),
-                tol=(float(rng.choice([1e-3, 1e-4])) if tol_mode else 0.0), warm=bool(rng.random() < 0.5),
-                kernel=str(rng.choice(kernels)), device=bool(rng.random() < 0.5), seed=int(rng.integers(1 << 30)))
+    cfg = dict(loop=True, n_u=n_u, Nh=Nh, batch=int(rng.choice([1, 3, 17, 64, 300, 1100, 4100])),
+               steps=int(rng.integers(1, 11)), N=(2000 if tol_mode else int(rng.integers(1, 121))),
+               tol=(float(rng.choice([1e-3, 1e-4])) if tol_mode else 0.0), warm=bool(rng.random() < 0.5),
+               kernel=str(rng.choice(kernels)), device=bool(rng.random() < 0.5), seed=int(rng.integers(1 << 30)))
+    cfg["engine"] = str(engines[int(rng.integers(len(engines)))])
+    return cfg
 
 
 def run_loop_case(cfg: dict, oracle, sample: int = 6) -> dict:
     """Every trajectory value, final state, z*, y* and per-step count of a sample of packs bit for
-    bit against the oracle's closed loop (orc_closed_loop_f32)."""
+    bit against the oracle's closed loop (orc_closed_loop_f32).  cfg["engine"] (absent: lockstep) sets the
+    loop_async or the loop_panel option; where the one-launch kernel does not apply, the library runs the
+    lockstep loop and the comparison is the same."""
     import torch
 
     import gpad_mpc
@@ -374,6 +383,8 @@ def run_loop_case(cfg: dict, oracle, sample: int = 6) -> dict:
     with gpad_mpc.GpadSolver(0) as s:
         s.setup(put(qp.ML), put(qp.G), float(L), n=qp.n, m=qp.m, batch=B, shared=True, kernel=kc)
         s.setup_plant(put(pl.PM), put(pl.Pg), g0=put(pl.g0), A=put(pl.A), B=put(pl.B))
+        if cfg.get("engine", "lockstep") != "lockstep":
+            s.set_option(cfg["engine"], 1)
         IT = np.zeros(S * B, np.int32)
         if cfg["device"]:
             X, Z, Y = put(X0), torch.zeros(B, qp.n, device=dev), torch.zeros(B, qp.m, device=dev)

@@ -34,12 +34,12 @@ def battery(n_u, Nh):
 
 
 @functools.lru_cache(maxsize=None)
-def synthetic(n, m, nx, nu, packs=6):
+def synthetic(n, m, nx, nu, packs=6, seed=11):
     """A generic plant on a synthetic QP: both affine maps with a constant term (M0, g0 bound),
-    nx != nu, a contracting A (0.9 x orthogonal)."""
+    nx != nu, a contracting A (0.9 x orthogonal).  seed: of the maps and X0 (the QP is seed 1's)."""
     from gpad_mpc import problems
     qp = problems.synthetic_qp(n, m, batch=1, seed=1)
-    rng = np.random.default_rng(11)
+    rng = np.random.default_rng(seed)
     PM = 0.1 * rng.standard_normal((n, nx))
     Pg = 0.05 * rng.standard_normal((m, nx))
     Q, _ = np.linalg.qr(rng.standard_normal((nx, nx)))

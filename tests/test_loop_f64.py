@@ -123,6 +123,10 @@ def config(name):
         import test_loop_async as T
         p = T.synthetic(70, 130, 5, 2)
         return _cfg(name, "plant", p.qp.ML, p.qp.G, p.qp.L, _maps(p), p.X0, 5)
+    if name == "B23":  # B's shape with nu = 3 > nx = 2 (run by tests/test_loop_shapes.py, with its own CPU checks)
+        import test_loop_async as T
+        p = T.synthetic(70, 130, 2, 3)
+        return _cfg(name, "plant", p.qp.ML, p.qp.G, p.qp.L, _maps(p), p.X0, 3)
     if name == "D":  # battery(3, 4) under load with references
         import test_signals as TS
         qp, pl = problems.battery_plant_signals(3, 4)
