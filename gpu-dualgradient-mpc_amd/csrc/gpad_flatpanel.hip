@@ -19,16 +19,13 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cmath>
-#include <cstdlib>
 
 #include "gpad_internal.h"
 #include "gpad_panel.h"  // (f32x4, as_float4, pi16; the Algorithm-1 test of gpad_panel_test.h)
 
 namespace gpad {
 
-constexpr int kFlatPanelWaves = 16;
-constexpr int kFlatPanelWavesMax = 16;
+constexpr int kFlatPanelWaves = 16;  // waves of the largest workgroup: a phase has at most 4 units per wave
 
 struct FlatGeom {  // sizes in tiles / k-blocks of 16 rows; image offsets in float4s
     int n_u, Nh, n, m, mc, E;
@@ -42,8 +39,8 @@ struct FlatGeom {  // sizes in tiles / k-blocks of 16 rows; image offsets in flo
     int PB;                  // LDS blocks per panel
     int P;                   // panels per workgroup (set by the launcher)
     // unit descriptors (set by the launcher): pp << 16 | (cell + 1) << 8 | t
-    int d1[4 * kFlatPanelWavesMax];
-    int d2[4 * kFlatPanelWavesMax];
+    int d1[4 * kFlatPanelWaves];
+    int d2[4 * kFlatPanelWaves];
 };
 
 __host__ __device__ inline int fp_ceil16(int x) { return (x + 15) / 16; }
@@ -153,51 +150,6 @@ hipError_t launch_pack_flatpanel(const float* MGf, const float* GLT, int n, int 
     return hipGetLastError();
 }
 
-// one unit's chain over nkb k-blocks (the last only its kq 4-steps): A by buffer loads at byte
-// offset voff + b * stride, two k-blocks in flight; B block b from Ba (b < kbs) or Bb (b >= kbs)
-__device__ __forceinline__ f32x4 fp_gemm(__amdgpu_buffer_rsrc_t PA, int voff, int stride, int nkb, int kq,
-                                          const float4* Ba, int kbs, const float4* Bb, int lane) {
-    f32x4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
-    float4 a0 = as_float4(__builtin_amdgcn_raw_buffer_load_b128(PA, voff, 0, 0));
-    float4 a1 = nkb > 1 ? as_float4(__builtin_amdgcn_raw_buffer_load_b128(PA, voff, stride, 0)) : a0;
-    float4 b0 = kbs > 0 ? Ba[lane] : Bb[lane];
-    for (int kb = 0; kb < nkb; ++kb) {
-        const float4 ak = a0, bk = b0;
-        a0 = a1;
-        if (kb + 2 < nkb) a1 = as_float4(__builtin_amdgcn_raw_buffer_load_b128(PA, voff, (kb + 2) * stride, 0));
-        if (kb + 1 < nkb) b0 = kb + 1 < kbs ? Ba[(kb + 1) * 64 + lane] : Bb[(kb + 1 - kbs) * 64 + lane];
-        const int steps = kb + 1 < nkb ? 4 : kq;
-        __builtin_amdgcn_sched_barrier(0);
-        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(ak.x, bk.x, acc, 0, 0, 0);
-        if (steps > 1) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(ak.y, bk.y, acc, 0, 0, 0);
-        if (steps > 2) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(ak.z, bk.z, acc, 0, 0, 0);
-        if (steps > 3) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(ak.w, bk.w, acc, 0, 0, 0);
-        asm volatile("" : "+v"(acc)::"memory");
-    }
-    return acc;
-}
-
-// a phase-2 unit: the coupling tile t (u < KBe) or tile t of cell c's constraint rows
-struct FpUnit2 {
-    int cell, t;
-};
-__device__ __forceinline__ FpUnit2 fp_unit2(const FlatGeom& g, int u) {
-    FpUnit2 x;
-    if (u < g.KBe) {
-        x.cell = -1;
-        x.t = u;
-    } else {
-        x.cell = (u - g.KBe) / g.KBc;
-        x.t = (u - g.KBe) - x.cell * g.KBc;
-    }
-    return x;
-}
-// constraint row of output row rr of a phase-2 unit (-1: padding)
-__device__ __forceinline__ int fp_row2(const FlatGeom& g, FpUnit2 x, int rr) {
-    if (x.cell < 0) return rr < g.E ? g.mc + rr : -1;
-    return rr < 4 * g.Nh ? x.cell + g.n_u * rr : -1;
-}
-
 // A fragment prefetch of a unit's first two k-blocks (issued before the barrier that precedes
 // its chain: the L2 latency overlaps the barrier and the epilogue)
 struct FpPre {
@@ -277,45 +229,53 @@ __device__ __forceinline__ int fp_opq(int x) {
     asm volatile("" : "+s"(x));
     return x;
 }
-struct FpU1 {
-    int pp, j, t;
-};
-__device__ __forceinline__ FpU1 fp_u1(const FlatGeom& g, int un) {
-    const int d = g.d1[fp_opq(un)];
-    FpU1 x;
-    x.pp = d >> 16;
-    x.j = ((d >> 8) & 0xFF) - 1;
-    x.t = d & 0xFF;
-    return x;
-}
-struct FpU2 {
+// Unit un of a phase (d = g.d1 or g.d2): row tile t of panel pp.  Phase 1: of cell `cell`'s 8b
+// rows.  Phase 2: of cell `cell`'s constraint rows, or (cell < 0) of the coupling rows.
+struct FpUnit {
     int pp, cell, t;
 };
-__device__ __forceinline__ FpU2 fp_u2(const FlatGeom& g, int un) {
-    const int d = g.d2[fp_opq(un)];
-    FpU2 x;
-    x.pp = d >> 16;
-    x.cell = ((d >> 8) & 0xFF) - 1;
-    x.t = d & 0xFF;
+__device__ __forceinline__ FpUnit fp_unit(const int* d, int un) {
+    const int w = d[fp_opq(un)];
+    FpUnit x;
+    x.pp = w >> 16;
+    x.cell = ((w >> 8) & 0xFF) - 1;
+    x.t = w & 0xFF;
     return x;
 }
-__device__ __forceinline__ int fp_voff1(const FlatGeom& g, FpU1 x, int lane) {
-    return (x.j * g.KBc * g.T1 + x.t) * 1024 + lane * 16;
+// constraint row of output row rr of a phase-2 unit (-1: padding)
+__device__ __forceinline__ int fp_row2(const FlatGeom& g, FpUnit x, int rr) {
+    if (x.cell < 0) return rr < g.E ? g.mc + rr : -1;
+    return rr < 4 * g.Nh ? x.cell + g.n_u * rr : -1;
 }
-__device__ __forceinline__ int fp_ajump1(const FlatGeom& g, FpU1 x) {  // cell image -> coupling image
-    return g.off1c * 16 - (x.j + 1) * g.KBc * g.T1 * 1024;
+__device__ __forceinline__ int fp_voff1(const FlatGeom& g, FpUnit x, int lane) {
+    return (x.cell * g.KBc * g.T1 + x.t) * 1024 + lane * 16;
 }
-__device__ __forceinline__ int fp_voff2(const FlatGeom& g, FpU2 x, int lane) {
+__device__ __forceinline__ int fp_ajump1(const FlatGeom& g, FpUnit x) {  // cell image -> coupling image
+    return g.off1c * 16 - (x.cell + 1) * g.KBc * g.T1 * 1024;
+}
+__device__ __forceinline__ int fp_voff2(const FlatGeom& g, FpUnit x, int lane) {
     return (x.cell < 0 ? g.off3 + x.t * 64 : g.off2 + (x.cell * g.T1 * g.KBc + x.t) * 64) * 16 + lane * 16;
 }
 
+// A panel's arrays in LDS, offsets in float4s from its base: Wc [n_u][KBc] at 0 | We [KBe] |
+// Zc [n_u][T1] | Zn [KB3]; PB = the panel's size
+struct FpLds {
+    int We, Zc, Zn, PB;
+};
+__device__ __forceinline__ FpLds fp_lds_map(const FlatGeom& g) {
+    FpLds o;
+    o.We = g.n_u * g.KBc * 64;
+    o.Zc = o.We + g.KBe * 64;
+    o.Zn = o.Zc + g.n_u * g.T1 * 64;
+    o.PB = g.PB * 64;
+    return o;
+}
 template <int NU1, int NU2, bool ALDS, int W>
 __global__ __launch_bounds__(64 * W, 4) void gpad_flatpanel_kernel(SolveArgs<float> a, FlatGeom g) {
     extern __shared__ __attribute__((aligned(16))) float4 fp_lds[];
     const int P = g.P;
-    // per panel pp at fp_lds + pp * PB * 64:  Wc [n_u][KBc] | We [KBe] | Zc [n_u][T1] | Zn [KB3]
-    const int oWe = g.n_u * g.KBc * 64, oZc = oWe + g.KBe * 64, oZn = oZc + g.n_u * g.T1 * 64;
-    const int PBf = g.PB * 64;
+    const FpLds o = fp_lds_map(g);  // panel pp at fp_lds + pp * PBf
+    const int PBf = o.PB;
     TestSlot<float>* slots = reinterpret_cast<TestSlot<float>*>(fp_lds + P * PBf);  // [P * U2]
     float4* As = fp_lds + P * PBf + (P * g.U2 * (int)sizeof(TestSlot<float>)) / 16;  // ALDS: the A image
 
@@ -340,7 +300,7 @@ __global__ __launch_bounds__(64 * W, 4) void gpad_flatpanel_kernel(SolveArgs<flo
     // Zn's rows past n are read by the last k-block of the coupling chains: zero once
     for (int pp = 0; pp < P; ++pp)
         for (int e = threadIdx.x; e < g.KB3 * 64; e += 64 * W)
-            fp_lds[pp * PBf + oZn + e] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            fp_lds[pp * PBf + o.Zn + e] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
 
     for (int grp = blockIdx.x; grp < groups; grp += gridDim.x) {
         const int k0 = 16 * P * grp;  // first column of the group; column (pp, c) = k0 + 16 pp + c
@@ -361,7 +321,7 @@ __global__ __launch_bounds__(64 * W, 4) void gpad_flatpanel_kernel(SolveArgs<flo
 #pragma unroll
         for (int q = 0; q < NU1; ++q) {
             const int un = w + W * q;
-            const FpU1 x = fp_u1(g, un < nu1 ? un : 0);
+            const FpUnit x = fp_unit(g.d1, un < nu1 ? un : 0);
             const int col = k0 + 16 * x.pp + c;
             const bool act = un < nu1 && col < count;
             const size_t bi = act ? inst_of(16 * x.pp + c) : 0;
@@ -369,31 +329,31 @@ __global__ __launch_bounds__(64 * W, 4) void gpad_flatpanel_kernel(SolveArgs<flo
             for (int r = 0; r < 4; ++r) {
                 const int i = 16 * x.t + 4 * r + jl;
                 const bool ok = act && i < g.Nh;
-                z[q][r] = ok ? a.z[bi * n + i * g.n_u + x.j] : 0.0f;
-                gp[q][r] = ok ? a.gP[bi * a.ld_gP + i * g.n_u + x.j] : 0.0f;
+                z[q][r] = ok ? a.z[bi * n + i * g.n_u + x.cell] : 0.0f;
+                gp[q][r] = ok ? a.gP[bi * a.ld_gP + i * g.n_u + x.cell] : 0.0f;
             }
             if (un < nu1 && use_tol && fresh) {  // z_{-1} as the B operand of u = G_L z_{-1}
                 float4* L = fp_lds + x.pp * PBf;
-                L[oZc + (x.j * g.T1 + x.t) * 64 + lane] = make_float4(z[q][0], z[q][1], z[q][2], z[q][3]);
+                L[o.Zc + (x.cell * g.T1 + x.t) * 64 + lane] = make_float4(z[q][0], z[q][1], z[q][2], z[q][3]);
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
-                    const int i = 16 * x.t + 4 * r + jl, kk = i * g.n_u + x.j;
+                    const int i = 16 * x.t + 4 * r + jl, kk = i * g.n_u + x.cell;
                     if (i < g.Nh)
-                        reinterpret_cast<float*>(&L[oZn + (kk >> 4) * 64 + (kk & 3) * 16 + c])[(kk >> 2) & 3] = z[q][r];
+                        reinterpret_cast<float*>(&L[o.Zn + (kk >> 4) * 64 + (kk & 3) * 16 + c])[(kk >> 2) & 3] = z[q][r];
                 }
             }
         }
 #pragma unroll
         for (int q = 0; q < NU2; ++q) {
             const int un = w + W * q;
-            const FpU2 x = fp_u2(g, un < nu2 ? un : 0);
+            const FpUnit x = fp_unit(g.d2, un < nu2 ? un : 0);
             const int col = k0 + 16 * x.pp + c;
             const bool act = un < nu2 && col < count;
             const size_t bi = act ? inst_of(16 * x.pp + c) : 0;
             float wv[4];
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                const int row = fp_row2(g, FpUnit2{x.cell, x.t}, 16 * x.t + 4 * r + jl);
+                const int row = fp_row2(g, x, 16 * x.t + 4 * r + jl);
                 const bool ok = row >= 0 && act;
                 y[q][r] = ok ? a.y[bi * m + row] : 0.0f;
                 pd[q][r] = ok ? (float)(a.gscale * (double)a.g[bi * a.ld_g + row]) : 0.0f;
@@ -407,7 +367,7 @@ __global__ __launch_bounds__(64 * W, 4) void gpad_flatpanel_kernel(SolveArgs<flo
             }
             if (un < nu2) {
                 float4* L = fp_lds + x.pp * PBf;
-                L[(x.cell < 0 ? oWe + x.t * 64 : (x.cell * g.KBc + x.t) * 64) + lane] =
+                L[(x.cell < 0 ? o.We + x.t * 64 : (x.cell * g.KBc + x.t) * 64) + lane] =
                     make_float4(wv[0], wv[1], wv[2], wv[3]);
             }
         }
@@ -417,14 +377,14 @@ __global__ __launch_bounds__(64 * W, 4) void gpad_flatpanel_kernel(SolveArgs<flo
             for (int q = 0; q < NU2; ++q) {
                 const int un = w + W * q;
                 if (un < nu2) {
-                    const FpU2 x = fp_u2(g, un);
+                    const FpUnit x = fp_unit(g.d2, un);
                     const bool cp = x.cell < 0;
                     const float4* L = fp_lds + x.pp * PBf;
                     const int voff = fp_voff2(g, x, lane), stride = (cp ? g.KBe : g.KBc) * 1024;
                     const int nkb = cp ? g.KB3 : g.T1;
                     const f32x4 cz = fp_chain<ALDS>(PA, As, fp_pre<ALDS>(PA, As, voff, stride, nkb), voff, stride, nkb,
-                                               cp ? g.kq3 : g.kq2, cp ? L + oZn : L + oZc + x.cell * g.T1 * 64,
-                                               nkb, L + oZn, lane);
+                                               cp ? g.kq3 : g.kq2, cp ? L + o.Zn : L + o.Zc + x.cell * g.T1 * 64,
+                                               nkb, L + o.Zn, lane);
 #pragma unroll
                     for (int r = 0; r < 4; ++r) u[q][r] = cz[r];
                 }
@@ -435,7 +395,7 @@ __global__ __launch_bounds__(64 * W, 4) void gpad_flatpanel_kernel(SolveArgs<flo
         // first units' A fragments, one barrier ahead
         FpPre pre1{}, pre2{};
         if (w < nu1) {
-            const FpU1 x = fp_u1(g, w);
+            const FpUnit x = fp_unit(g.d1, w);
             pre1 = fp_pre<ALDS>(PA, As, fp_voff1(g, x, lane), g.T1 * 1024, g.KB1, g.KBc, fp_ajump1(g, x));
         }
         int v = a.v_begin;
@@ -450,14 +410,14 @@ __global__ __launch_bounds__(64 * W, 4) void gpad_flatpanel_kernel(SolveArgs<flo
             for (int q = 0; q < NU1; ++q) {
                 const int un = w + W * q;
                 if (un < nu1) {
-                    const FpU1 x = fp_u1(g, un);
+                    const FpUnit x = fp_unit(g.d1, un);
                     const bool act = (live >> (16 * x.pp + c)) & 1ull;
                     float4* L = fp_lds + x.pp * PBf;
                     const int voff = fp_voff1(g, x, lane);
                     const int ajump = fp_ajump1(g, x);
                     const FpPre f = q == 0 ? pre1 : fp_pre<ALDS>(PA, As, voff, g.T1 * 1024, g.KB1, g.KBc, ajump);
-                    const f32x4 acc = fp_chain<ALDS>(PA, As, f, voff, g.T1 * 1024, g.KB1, g.kq1, L + x.j * g.KBc * 64, g.KBc,
-                                                      L + oWe, lane, g.KBc, ajump);
+                    const f32x4 acc = fp_chain<ALDS>(PA, As, f, voff, g.T1 * 1024, g.KB1, g.kq1, L + x.cell * g.KBc * 64, g.KBc,
+                                                      L + o.We, lane, g.KBc, ajump);
                     float zh[4];
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
@@ -465,18 +425,18 @@ __global__ __launch_bounds__(64 * W, 4) void gpad_flatpanel_kernel(SolveArgs<flo
                         const float zn = __builtin_fmaf(omt, z[q][r], th * zh[r]);
                         if (act) z[q][r] = zn;
                     }
-                    L[oZc + (x.j * g.T1 + x.t) * 64 + lane] = make_float4(zh[0], zh[1], zh[2], zh[3]);
+                    L[o.Zc + (x.cell * g.T1 + x.t) * 64 + lane] = make_float4(zh[0], zh[1], zh[2], zh[3]);
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
-                        const int i = 16 * x.t + 4 * r + jl, kk = i * g.n_u + x.j;
+                        const int i = 16 * x.t + 4 * r + jl, kk = i * g.n_u + x.cell;
                         if (i < g.Nh)
-                            reinterpret_cast<float*>(&L[oZn + (kk >> 4) * 64 + (kk & 3) * 16 + c])[(kk >> 2) & 3] =
+                            reinterpret_cast<float*>(&L[o.Zn + (kk >> 4) * 64 + (kk & 3) * 16 + c])[(kk >> 2) & 3] =
                                 zh[r];
                     }
                 }
             }
             if (w < nu2) {
-                const FpU2 x = fp_u2(g, w);
+                const FpUnit x = fp_unit(g.d2, w);
                 pre2 = fp_pre<ALDS>(PA, As, fp_voff2(g, x, lane), (x.cell < 0 ? g.KBe : g.KBc) * 1024,
                               x.cell < 0 ? g.KB3 : g.T1);
             }
@@ -486,7 +446,7 @@ __global__ __launch_bounds__(64 * W, 4) void gpad_flatpanel_kernel(SolveArgs<flo
             for (int q = 0; q < NU2; ++q) {
                 const int un = w + W * q;
                 if (un < nu2) {
-                    const FpU2 x = fp_u2(g, un);
+                    const FpUnit x = fp_unit(g.d2, un);
                     const bool act = (live >> (16 * x.pp + c)) & 1ull;
                     const bool cp = x.cell < 0;
                     float4* L = fp_lds + x.pp * PBf;
@@ -494,8 +454,8 @@ __global__ __launch_bounds__(64 * W, 4) void gpad_flatpanel_kernel(SolveArgs<flo
                     const int nkb = cp ? g.KB3 : g.T1;
                     const FpPre f = q == 0 ? pre2 : fp_pre<ALDS>(PA, As, voff, stride, nkb);
                     const f32x4 acc = fp_chain<ALDS>(PA, As, f, voff, stride, nkb, cp ? g.kq3 : g.kq2,
-                                                cp ? L + oZn : L + oZc + x.cell * g.T1 * 64, nkb, L + oZn, lane);
-                    float4* wp = L + (cp ? oWe + x.t * 64 : (x.cell * g.KBc + x.t) * 64) + lane;
+                                                cp ? L + o.Zn : L + o.Zc + x.cell * g.T1 * 64, nkb, L + o.Zn, lane);
+                    float4* wp = L + (cp ? o.We + x.t * 64 : (x.cell * g.KBc + x.t) * 64) + lane;
                     const float4 w4 = *wp;
                     const float wv[4] = {w4.x, w4.y, w4.z, w4.w};
                     const int lim = cp ? g.E : 4 * g.Nh;
@@ -522,7 +482,7 @@ __global__ __launch_bounds__(64 * W, 4) void gpad_flatpanel_kernel(SolveArgs<flo
                 }
             }
             if (w < nu1) {
-                const FpU1 x = fp_u1(g, w);
+                const FpUnit x = fp_unit(g.d1, w);
                 pre1 = fp_pre<ALDS>(PA, As, fp_voff1(g, x, lane), g.T1 * 1024, g.KB1, g.KBc, fp_ajump1(g, x));
             }
             th = th_next;
@@ -545,10 +505,10 @@ __global__ __launch_bounds__(64 * W, 4) void gpad_flatpanel_kernel(SolveArgs<flo
                     for (int q = 0; q < NU1; ++q) {
                         const int un = w + W * q;
                         if (un < nu1) {
-                            const FpU1 x = fp_u1(g, un);
+                            const FpUnit x = fp_unit(g.d1, un);
                             const int bit = 16 * x.pp + c;
                             float4* L = fp_lds + x.pp * PBf;
-                            float4* zc = &L[oZc + (x.j * g.T1 + x.t) * 64 + lane];
+                            float4* zc = &L[o.Zc + (x.cell * g.T1 + x.t) * 64 + lane];
                             if ((m2 >> bit) & 1ull) {  // test (B)'s zhat out before z replaces it
                                 const float4 zh4 = *zc;
                                 const float zhv[4] = {zh4.x, zh4.y, zh4.z, zh4.w};
@@ -556,15 +516,15 @@ __global__ __launch_bounds__(64 * W, 4) void gpad_flatpanel_kernel(SolveArgs<flo
 #pragma unroll
                                 for (int r = 0; r < 4; ++r) {
                                     const int i = 16 * x.t + 4 * r + jl;
-                                    if (i < g.Nh) a.z[bi * n + i * g.n_u + x.j] = zhv[r];
+                                    if (i < g.Nh) a.z[bi * n + i * g.n_u + x.cell] = zhv[r];
                                 }
                             }
                             *zc = make_float4(z[q][0], z[q][1], z[q][2], z[q][3]);
 #pragma unroll
                             for (int r = 0; r < 4; ++r) {
-                                const int i = 16 * x.t + 4 * r + jl, kk = i * g.n_u + x.j;
+                                const int i = 16 * x.t + 4 * r + jl, kk = i * g.n_u + x.cell;
                                 if (i < g.Nh)
-                                    reinterpret_cast<float*>(&L[oZn + (kk >> 4) * 64 + (kk & 3) * 16 + c])[(kk >> 2) & 3] =
+                                    reinterpret_cast<float*>(&L[o.Zn + (kk >> 4) * 64 + (kk & 3) * 16 + c])[(kk >> 2) & 3] =
                                         z[q][r];
                             }
                         }
@@ -574,7 +534,7 @@ __global__ __launch_bounds__(64 * W, 4) void gpad_flatpanel_kernel(SolveArgs<flo
                     for (int q = 0; q < NU2; ++q) {
                         const int un = w + W * q;
                         if (un < nu2) {
-                            const FpU2 x = fp_u2(g, un);
+                            const FpUnit x = fp_unit(g.d2, un);
                             const bool nom = (mA >> (16 * x.pp + c)) & 1ull;
                             const bool cp = x.cell < 0;
                             const float4* L = fp_lds + x.pp * PBf;
@@ -582,8 +542,8 @@ __global__ __launch_bounds__(64 * W, 4) void gpad_flatpanel_kernel(SolveArgs<flo
                             const int nkb = cp ? g.KB3 : g.T1;
                             const f32x4 cz = fp_chain<ALDS>(PA, As, fp_pre<ALDS>(PA, As, voff, stride, nkb), voff,
                                                              stride, nkb, cp ? g.kq3 : g.kq2,
-                                                             cp ? L + oZn : L + oZc + x.cell * g.T1 * 64, nkb,
-                                                             L + oZn, lane);
+                                                             cp ? L + o.Zn : L + o.Zc + x.cell * g.T1 * 64, nkb,
+                                                             L + o.Zn, lane);
                             const int lim = cp ? g.E : 4 * g.Nh;
                             VerPart<float> vp;
 #pragma unroll
@@ -608,17 +568,17 @@ __global__ __launch_bounds__(64 * W, 4) void gpad_flatpanel_kernel(SolveArgs<flo
                 for (int q = 0; q < NU1; ++q) {
                     const int un = w + W * q;
                     if (un < nu1) {
-                        const FpU1 x = fp_u1(g, un);
+                        const FpUnit x = fp_unit(g.d1, un);
                         const int bit = 16 * x.pp + c;
                         const bool tb = (m2 >> bit) & 1ull;  // test (B): zhat (pre-written when verified over)
                         if (((fin >> bit) & 1ull) && (!tb || zh_out)) {
                             const size_t bi = inst_of(bit);
-                            const float4 zh4 = fp_lds[x.pp * PBf + oZc + (x.j * g.T1 + x.t) * 64 + lane];
+                            const float4 zh4 = fp_lds[x.pp * PBf + o.Zc + (x.cell * g.T1 + x.t) * 64 + lane];
                             const float zhv[4] = {zh4.x, zh4.y, zh4.z, zh4.w};
 #pragma unroll
                             for (int r = 0; r < 4; ++r) {
                                 const int i = 16 * x.t + 4 * r + jl;
-                                if (i < g.Nh) a.z[bi * n + i * g.n_u + x.j] = tb ? zhv[r] : z[q][r];
+                                if (i < g.Nh) a.z[bi * n + i * g.n_u + x.cell] = tb ? zhv[r] : z[q][r];
                             }
                         }
                     }
@@ -627,13 +587,13 @@ __global__ __launch_bounds__(64 * W, 4) void gpad_flatpanel_kernel(SolveArgs<flo
                 for (int q = 0; q < NU2; ++q) {
                     const int un = w + W * q;
                     if (un < nu2) {
-                        const FpU2 x = fp_u2(g, un);
+                        const FpUnit x = fp_unit(g.d2, un);
                         const int bit = 16 * x.pp + c;
                         if ((fin >> bit) & 1ull) {
                             const size_t bi = inst_of(bit);
 #pragma unroll
                             for (int r = 0; r < 4; ++r) {
-                                const int row = fp_row2(g, FpUnit2{x.cell, x.t}, 16 * x.t + 4 * r + jl);
+                                const int row = fp_row2(g, x, 16 * x.t + 4 * r + jl);
                                 if (row >= 0) a.y[bi * m + row] = y[q][r];
                             }
                         }
@@ -654,14 +614,14 @@ __global__ __launch_bounds__(64 * W, 4) void gpad_flatpanel_kernel(SolveArgs<flo
             for (int q = 0; q < NU1; ++q) {
                 const int un = w + W * q;
                 if (un < nu1) {
-                    const FpU1 x = fp_u1(g, un);
+                    const FpUnit x = fp_unit(g.d1, un);
                     const int bit = 16 * x.pp + c;
                     if ((live >> bit) & 1ull) {
                         const size_t bi = inst_of(bit);
 #pragma unroll
                         for (int r = 0; r < 4; ++r) {
                             const int i = 16 * x.t + 4 * r + jl;
-                            if (i < g.Nh) a.z[bi * n + i * g.n_u + x.j] = z[q][r];
+                            if (i < g.Nh) a.z[bi * n + i * g.n_u + x.cell] = z[q][r];
                         }
                     }
                 }
@@ -670,16 +630,16 @@ __global__ __launch_bounds__(64 * W, 4) void gpad_flatpanel_kernel(SolveArgs<flo
             for (int q = 0; q < NU2; ++q) {
                 const int un = w + W * q;
                 if (un < nu2) {
-                    const FpU2 x = fp_u2(g, un);
+                    const FpUnit x = fp_unit(g.d2, un);
                     const int bit = 16 * x.pp + c;
                     if ((live >> bit) & 1ull) {
                         const size_t bi = inst_of(bit);
-                        const float4 w4 = fp_lds[x.pp * PBf + (x.cell < 0 ? oWe + x.t * 64 : (x.cell * g.KBc + x.t) * 64) +
+                        const float4 w4 = fp_lds[x.pp * PBf + (x.cell < 0 ? o.We + x.t * 64 : (x.cell * g.KBc + x.t) * 64) +
                                                  lane];  // w of iteration v (this unit's own rows)
                         const float wv[4] = {w4.x, w4.y, w4.z, w4.w};
 #pragma unroll
                         for (int r = 0; r < 4; ++r) {
-                            const int row = fp_row2(g, FpUnit2{x.cell, x.t}, 16 * x.t + 4 * r + jl);
+                            const int row = fp_row2(g, x, 16 * x.t + 4 * r + jl);
                             if (row >= 0) {
                                 a.y[bi * m + row] = y[q][r];
                                 a.wc[bi * m + row] = wv[r];
@@ -701,6 +661,82 @@ __global__ __launch_bounds__(64 * W, 4) void gpad_flatpanel_kernel(SolveArgs<flo
     }
 }
 
+// the unit descriptor tables for P panels per workgroup.  A panel's phase-1 units: cell by cell,
+// its T1 row tiles; its phase-2 units: the KBe coupling tiles (cell -1), then cell by cell its
+// KBc row tiles
+static void fp_fill_units(FlatGeom& g, int P) {
+    g.P = P;
+    for (int un = 0; un < 4 * kFlatPanelWaves; ++un) {
+        const int pp = un / g.U1, uu = un % g.U1;
+        g.d1[un] = un < P * g.U1 ? (pp << 16) | ((uu / g.T1 + 1) << 8) | (uu % g.T1) : 0;
+        const int qq = un / g.U2, vv = un % g.U2;
+        const int cell = vv < g.KBe ? -1 : (vv - g.KBe) / g.KBc;
+        const int t = vv < g.KBe ? vv : (vv - g.KBe) % g.KBc;
+        g.d2[un] = un < P * g.U2 ? (qq << 16) | ((cell + 1) << 8) | t : 0;
+    }
+}
+
+// units per wave of a phase, rounded up to an instantiated count
+static int fp_nt(int units, int W) {
+    const int q = (units + W - 1) / W;
+    return q <= 1 ? 1 : (q <= 2 ? 2 : 4);
+}
+
+struct FlatPlan {
+    int W, P;    // waves per workgroup, panels per workgroup
+    bool alds;   // the A image in LDS
+    size_t lds;  // dynamic LDS bytes of a workgroup
+    int grid;
+    int NU1, NU2;  // units per wave of the two phases (the kernel's template arguments)
+};
+
+// The launch of `panels` panels of 16 instances on num_cus CUs (no device calls).
+// P panels per workgroup: as many as keep every CU busy (groups >= CUs), the phase-1 units within
+// one per wave and the phase-2 units within 4 per wave, and the LDS within 160 KiB.
+static FlatPlan flatpanel_plan(const FlatGeom& g, int panels, int num_cus, const Tuning& tn) {
+    FlatPlan p{};
+    // 8-wave workgroups, two per CU: the same waves per CU as one 16-wave workgroup, but two
+    // independent barrier domains, so one workgroup's barrier waits overlap the other's chains.
+    // Only for shapes whose units fit (phase 1 one per wave, phase 2 at most four per wave) with
+    // the LDS of two workgroups; forced with GPAD_FLAT_WAVES=8 (then also at one panel each, and
+    // falling through to 16 waves when nothing fits) or by the default rule.
+    // default: two 8-wave workgroups per CU when each can hold two panels (C1 packs from 16384:
+    // 5.41 -> 5.23 us per batch-iteration); at one panel each they lose to one 16-wave
+    // workgroup of two panels (8192: 3.03 vs 3.28 us)
+    if (tn.flat_waves == 8 || tn.flat_waves == 0) {
+        const bool force = tn.flat_waves == 8;
+        for (int q = 2; q >= 1 && !p.P; --q)
+            if (q * g.U1 <= 8 && q * g.U2 <= 32 && 2 * flatpanel_lds_bytes(g, q) <= 160 * 1024 &&
+                (force ? q == 1 || (panels + q - 1) / q >= 2 * num_cus : q == 2 && (panels + q - 1) / q >= 2 * num_cus))
+                p.P = q;
+    }
+    p.W = p.P ? 8 : kFlatPanelWaves;
+    if (!p.P) {  // 16-wave workgroups
+        p.P = 1;
+        for (int q = 4; q > 1; --q) {
+            if (q * g.U1 <= kFlatPanelWaves && q * g.U2 <= 4 * kFlatPanelWaves &&
+                flatpanel_lds_bytes(g, q) <= 160 * 1024 && (panels + q - 1) / q >= num_cus) {
+                p.P = q;
+                break;
+            }
+        }
+        if (tn.flat_panels > 0) p.P = std::min(4, tn.flat_panels);
+        while (p.P > 1 && (p.P * g.U1 > 4 * kFlatPanelWaves || p.P * g.U2 > 4 * kFlatPanelWaves ||
+                           flatpanel_lds_bytes(g, p.P) > 160 * 1024))
+            --p.P;
+    }
+    // the A image in LDS when it fits beside the panels' vectors (of both workgroups of a CU at 8 waves)
+    p.lds = flatpanel_lds_bytes(g, p.P);
+    const size_t abytes = (size_t)g.total * 16;
+    p.alds = (p.W == 8 ? 2 : 1) * (p.lds + abytes) <= 160 * 1024 && tn.flat_a_lds;
+    if (p.alds) p.lds += abytes;
+    // two workgroups per CU where their LDS allows it (at 8 waves always), no more than there are groups
+    p.grid = std::min((panels + p.P - 1) / p.P, num_cus * (2 * p.lds <= 160 * 1024 ? 2 : 1));
+    p.NU1 = fp_nt(p.P * g.U1, p.W);
+    p.NU2 = fp_nt(p.P * g.U2, p.W);
+    return p;
+}
+
 template <int NU1, int NU2, bool ALDS, int W>
 static hipError_t launch_fp_k(const SolveArgs<float>& a, const FlatGeom& g, size_t lds, int grid, hipStream_t s) {
     if (lds > 64 * 1024) {
@@ -711,112 +747,27 @@ static hipError_t launch_fp_k(const SolveArgs<float>& a, const FlatGeom& g, size
     hipLaunchKernelGGL((gpad_flatpanel_kernel<NU1, NU2, ALDS, W>), dim3(grid), dim3(64 * W), lds, s, a, g);
     return hipGetLastError();
 }
-template <int NU1, int NU2, int W = kFlatPanelWaves>
-static hipError_t launch_fp_nt(const SolveArgs<float>& a, const FlatGeom& g, size_t lds, bool alds, int grid,
-                               hipStream_t s) {
-    return alds ? launch_fp_k<NU1, NU2, true, W>(a, g, lds, grid, s)
-                : launch_fp_k<NU1, NU2, false, W>(a, g, lds, grid, s);
-}
-
-static int fp_nt(int units, int W = kFlatPanelWaves) {
-    const int q = (units + W - 1) / W;
-    return q <= 1 ? 1 : (q <= 2 ? 2 : 4);
-}
-
-// 8-wave workgroups, two per CU: the same waves per CU as one 16-wave workgroup, but two
-// independent barrier domains, so one workgroup's barrier waits overlap the other's chains.
-// Only for shapes whose units fit (phase 1 one per wave, phase 2 at most four per wave) with
-// the LDS of two workgroups; chosen with GPAD_FLAT_WAVES=8 or by the default rule below.
-static hipError_t launch_flatpanel_w8(const SolveArgs<float>& a, FlatGeom g, int panels, hipStream_t s,
-                                      bool force, bool* taken) {
-    *taken = false;
-    int P = 0;
-    for (int q = 2; q >= 1 && !P; --q)
-        if (q * g.U1 <= 8 && q * g.U2 <= 32 && 2 * flatpanel_lds_bytes(g, q) <= 160 * 1024 &&
-            (force ? q == 1 || (panels + q - 1) / q >= 2 * a.num_cus : q == 2 && (panels + q - 1) / q >= 2 * a.num_cus))
-            P = q;
-    if (!P) return hipSuccess;
-    g.P = P;
-    for (int un = 0; un < 4 * kFlatPanelWavesMax; ++un) {
-        const int pp = un / g.U1, uu = un % g.U1;
-        g.d1[un] = un < P * g.U1 ? (pp << 16) | ((uu / g.T1 + 1) << 8) | (uu % g.T1) : 0;
-        const int qq = un / g.U2, vv = un % g.U2;
-        const int cell = vv < g.KBe ? -1 : (vv - g.KBe) / g.KBc;
-        const int t = vv < g.KBe ? vv : (vv - g.KBe) % g.KBc;
-        g.d2[un] = un < P * g.U2 ? (qq << 16) | ((cell + 1) << 8) | t : 0;
-    }
-    size_t lds = flatpanel_lds_bytes(g, P);
-    const size_t abytes = (size_t)g.total * 16;
-    const bool alds = 2 * (lds + abytes) <= 160 * 1024 && (!a.tune || a.tune->flat_a_lds);
-    if (alds) lds += abytes;
-    const int groups = (panels + P - 1) / P;
-    const int grid = std::min(groups, 2 * a.num_cus);
-    *taken = true;
-    switch (fp_nt(P * g.U2, 8)) {
-        case 1: return launch_fp_nt<1, 1, 8>(a, g, lds, alds, grid, s);
-        case 2: return launch_fp_nt<1, 2, 8>(a, g, lds, alds, grid, s);
-        default: return launch_fp_nt<1, 4, 8>(a, g, lds, alds, grid, s);
-    }
-}
 
 // one launch over a.batch instances, or over the phase's list (a.count_in; the geometry and grid
 // are sized for a.batch, extra workgroups find no group); a.frag = the flat fragment images.
-// P panels per workgroup: as many as keep every CU busy (groups >= CUs), the phase-1 units within
-// one per wave and the phase-2 units within 4 per wave, and the LDS within 160 KiB.
 // (the phase loop over such launches is gpad_phases.cpp launch_flatpanel)
 hipError_t launch_flatpanel_once(const SolveArgs<float>& a, hipStream_t s) {
     if (!flatpanel_supported(a.n, a.m, a.n_u) || !a.frag) return hipErrorInvalidValue;
     FlatGeom g = flat_geom(a.n, a.m, a.n_u);
-    const int panels = (a.batch + 15) / 16;
-    const Tuning tn = a.tune ? *a.tune : Tuning{};
-    if (tn.flat_waves == 8) {  // forced 8-wave workgroups
-        bool taken = false;
-        const hipError_t e = launch_flatpanel_w8(a, g, panels, s, true, &taken);
-        if (taken || e != hipSuccess) return e;
-    } else if (tn.flat_waves == 0) {
-        // default: two 8-wave workgroups per CU when each can hold two panels (C1 packs from 16384:
-        // 5.41 -> 5.23 us per batch-iteration); at one panel each they lose to one 16-wave
-        // workgroup of two panels (8192: 3.03 vs 3.28 us)
-        bool taken = false;
-        const hipError_t e = launch_flatpanel_w8(a, g, panels, s, false, &taken);
-        if (taken || e != hipSuccess) return e;
-    }
-    int P = 1;
-    for (int q = 4; q > 1; --q) {
-        if (q * g.U1 <= kFlatPanelWaves && q * g.U2 <= 4 * kFlatPanelWaves &&
-            flatpanel_lds_bytes(g, q) <= 160 * 1024 && (panels + q - 1) / q >= a.num_cus) {
-            P = q;
-            break;
-        }
-    }
-    if (tn.flat_panels > 0) P = std::min(4, tn.flat_panels);
-    while (P > 1 && (P * g.U1 > 4 * kFlatPanelWaves || P * g.U2 > 4 * kFlatPanelWaves ||
-                     flatpanel_lds_bytes(g, P) > 160 * 1024))
-        --P;
-    g.P = P;
-    for (int un = 0; un < 4 * kFlatPanelWavesMax; ++un) {
-        const int pp = un / g.U1, uu = un % g.U1;
-        g.d1[un] = un < P * g.U1 ? (pp << 16) | ((uu / g.T1 + 1) << 8) | (uu % g.T1) : 0;
-        const int qq = un / g.U2, vv = un % g.U2;
-        const int cell = vv < g.KBe ? -1 : (vv - g.KBe) / g.KBc;
-        const int t = vv < g.KBe ? vv : (vv - g.KBe) % g.KBc;
-        g.d2[un] = un < P * g.U2 ? (qq << 16) | ((cell + 1) << 8) | t : 0;
-    }
-    size_t lds = flatpanel_lds_bytes(g, P);
-    const size_t abytes = (size_t)g.total * 16;
-    const bool alds = lds + abytes <= 160 * 1024 && tn.flat_a_lds;  // A image in LDS
-    if (alds) lds += abytes;
-    const int groups = (panels + P - 1) / P;
-    int grid = a.num_cus * (lds * 2 <= 160 * 1024 ? 2 : 1);
-    if (grid > groups) grid = groups;
-    const int q1 = fp_nt(P * g.U1), q2 = fp_nt(P * g.U2);
-#define FP_CASE(A, B) \
-    case A * 8 + B: return launch_fp_nt<A, B>(a, g, lds, alds, grid, s);
-    switch (q1 * 8 + q2) {
-        FP_CASE(1, 1) FP_CASE(1, 2) FP_CASE(1, 4)
-        FP_CASE(2, 1) FP_CASE(2, 2) FP_CASE(2, 4)
-        FP_CASE(4, 1) FP_CASE(4, 2)
-        default: return launch_fp_nt<4, 4>(a, g, lds, alds, grid, s);
+    const FlatPlan p = flatpanel_plan(g, (a.batch + 15) / 16, a.num_cus, a.tune ? *a.tune : Tuning{});
+    fp_fill_units(g, p.P);
+    // NU2 >= NU1 for every supported shape: U2 = KBe + n_u KBc and U1 = n_u T1, where
+    // KBc = ceil(4 Nh / 16) >= T1 = ceil(Nh / 16) and KBe >= 1 (flatpanel_supported: m > 4 n), so
+    // P U2 > P U1, and fp_nt is monotone.  At 8 waves the plan keeps phase 1 at one unit per wave.
+#define FP_CASE(W, N1, N2)                                                            \
+    case W * 100 + N1 * 10 + N2:                                                      \
+        return p.alds ? launch_fp_k<N1, N2, true, W>(a, g, p.lds, p.grid, s)          \
+                      : launch_fp_k<N1, N2, false, W>(a, g, p.lds, p.grid, s);
+    switch (p.W * 100 + p.NU1 * 10 + p.NU2) {
+        FP_CASE(16, 1, 1) FP_CASE(16, 1, 2) FP_CASE(16, 1, 4)
+        FP_CASE(16, 2, 2) FP_CASE(16, 2, 4) FP_CASE(16, 4, 4)
+        FP_CASE(8, 1, 1) FP_CASE(8, 1, 2) FP_CASE(8, 1, 4)
+        default: return hipErrorInvalidValue;
     }
 #undef FP_CASE
 }

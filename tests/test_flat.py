@@ -162,17 +162,32 @@ def test_flat_batch_bitexact(gpu, oracle, tol, N, kernel, cells):
         np.testing.assert_array_equal(Y[b], y, err_msg=f"y[{b}]")
 
 
+PANEL_CASES = [((4, 10), 40, 1), ((3, 17), 33, 1), ((5, 6), 16 * 3 + 1, 1),
+               ((4, 50), 24, 1), ((2, 30), 20, 1), ((4, 10), 16 * 5 + 3, 4),
+               ((4, 10), 16 * 3 + 7, 2), ((3, 17), 16 * 4 + 9, 3), ((5, 6), 16 * 2 + 1, 4),
+               ((4, 50), 1, 1), ((3, 17), 5, 1), ((4, 10), 16 * 3 + 5, 8),
+               ((3, 17), 16 * 2 + 3, 8), ((5, 6), 16 * 4 + 1, 8)]
+# (cells, B, P, flat_a_lds) -> the kernel instantiation <NU1, NU2, ALDS, waves> the launcher picks.
+# (9, 4): n = 36, m = 152, 9 phase-1 and 10 phase-2 units per panel; a group of 4 panels has 64
+# columns, so B = 67 leaves a 3-column ragged group.
+PANEL_VARIANT_CASES = [((9, 4), 16 * 4 + 3, 2, 1), ((9, 4), 16 * 4 + 3, 2, 0),  # <2,2,*,16>
+                       ((9, 4), 16 * 4 + 3, 4, 1), ((9, 4), 16 * 4 + 3, 4, 0),  # <4,4,*,16>
+                       ((6, 4), 19, 8, 1),                                      # <1,1,true,8>
+                       ((4, 10), 40, 1, 0),                                     # <1,1,false,16>
+                       ((3, 17), 16 * 4 + 9, 3, 0)]                             # <2,4,false,16>
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("tol,N", [(0.0, 120), (1e-4, 4000)])
-@pytest.mark.parametrize("cells,B,P", [((4, 10), 40, 1), ((3, 17), 33, 1), ((5, 6), 16 * 3 + 1, 1),
-                                       ((4, 50), 24, 1), ((2, 30), 20, 1), ((4, 10), 16 * 5 + 3, 4),
-                                       ((4, 10), 16 * 3 + 7, 2), ((3, 17), 16 * 4 + 9, 3), ((5, 6), 16 * 2 + 1, 4),
-                                       ((4, 50), 1, 1), ((3, 17), 5, 1), ((4, 10), 16 * 3 + 5, 8),
-                                       ((3, 17), 16 * 2 + 3, 8), ((5, 6), 16 * 4 + 1, 8)])
-def test_flat_panel_bitexact(gpu, oracle, tol, N, cells, B, P):
+@pytest.mark.parametrize(
+    "cells,B,P,a_lds",
+    [pytest.param(c, b, p, 1, id=f"cells{i}-{b}-{p}") for i, (c, b, p) in enumerate(PANEL_CASES)] +
+    [pytest.param(c, b, p, al, id=f"{c[0]}x{c[1]}-{b}-{p}-alds{al}") for c, b, p, al in PANEL_VARIANT_CASES])
+def test_flat_panel_bitexact(gpu, oracle, tol, N, cells, B, P, a_lds):
     """The flat MFMA panel kernel (gpad_flatpanel.hip, forced with KERNEL_PANEL): per-cell
     skinny GEMMs over 16-instance panels, P panels per workgroup (ragged last panel, partly
-    empty last group), vs the oracle's flat solve."""
+    empty last group), with the fragment image in LDS (flat_a_lds, the default) or read from
+    global memory, vs the oracle's flat solve."""
     from gpad_mpc import problems
     import gpad_mpc
     n_u, Nh = cells
@@ -189,6 +204,7 @@ def test_flat_panel_bitexact(gpu, oracle, tol, N, cells, B, P):
         s.set_option("flat_waves", 8)
     else:
         s.set_option("flat_panels", P)
+    s.set_option("flat_a_lds", a_lds)
     Z = np.zeros((B, qp.n), np.float32)
     Y = np.zeros((B, qp.m), np.float32)
     it = np.zeros(B, np.int32)
@@ -205,13 +221,15 @@ def test_flat_panel_bitexact(gpu, oracle, tol, N, cells, B, P):
 @pytest.mark.gpu
 @pytest.mark.parametrize("phase_len,phased,P", [(10, 2, 1), (30, 2, 2), (0, 2, 4), (0, 0, 1), (10, 2, 8),
                                                  (20, 2, 3)])
-@pytest.mark.parametrize("cells,B", [((4, 10), 16 * 6 + 5), ((3, 17), 16 * 4 + 9)])
+@pytest.mark.parametrize("cells,B", [((4, 10), 16 * 6 + 5), ((3, 17), 16 * 4 + 9), ((9, 4), 16 * 6 + 5)])
 def test_flat_panel_phased_bitexact(gpu, oracle, phase_len, phased, P, cells, B):
     """Phased compaction on the flat panels (tol mode): survivors of each phase are parked
     (z, y in place; w, u carried) and re-packed into new groups (other columns, panels and
     workgroups) for the next phase; warm-started y.  Every instance must equal its own oracle
     flat solve, iteration count included.  phased=2 forces phases at this small batch (the
-    default starts at 4 panels per CU); phased=0: one launch, groups run to their last column."""
+    default starts at 4 panels per CU); phased=0: one launch, groups run to their last column.
+    Cells (9, 4) park and re-pack with two (P = 2, 3) and four (P = 4) units per wave in both
+    phases; its 8-wave request does not fit and falls through to 16 waves."""
     from gpad_mpc import problems
     import gpad_mpc
     n_u, Nh = cells
