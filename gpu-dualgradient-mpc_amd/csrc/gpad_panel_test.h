@@ -21,7 +21,8 @@
 // 16-column panel of the reference -- is exercised by:
 //   gpad_panel_kernel       tests/test_schedule_tables.py test_seed[37x53-panel]
 //   gpad_loop_panel_kernel  tests/test_loop_panel.py test_both_codes_in_one_panel
-//   gpad_bigpanel_kernel    tests/test_schedule_tables.py test_seed[300x280-bigpanel]
+//   gpad_bigpanel_kernel    tests/test_schedule_tables.py test_seed[300x280-bigpanel]; at every <NT1, NT2>,
+//                           with a code-1 and a code-2 finish at one test: tests/test_bigpanel.py test_algorithm1
 //   gpad_flatpanel_kernel   tests/test_schedule_tables.py test_flat_seed[4x10-panels]
 //   gpad_panel64_kernel     tests/test_schedule_tables.py test_seed_f64_both_codes_in_one_panel
 #pragma once
