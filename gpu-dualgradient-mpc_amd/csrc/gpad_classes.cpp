@@ -429,6 +429,27 @@ int classes_last_stats(ClassBinding* cb, gpad_stats_t* st) {
     return GPAD_OK;
 }
 
+// gpad_last_restarts: every child's counts of the last run, placed in the caller's order as the iteration counts
+// are (a fused loop never runs with the restart on: its whole-batch handle reports zeros)
+int classes_last_restarts(ClassBinding* cb, int* restarts, int cap) {
+    const int batch = cb->dims.batch, steps = std::max(cb->last_steps, 1);
+    const size_t entries = (size_t)steps * batch;
+    std::vector<int> all(entries, 0);
+    for (int k = 0; k < cb->K && cb->last_steps > 0 && !cb->last_fused; ++k) {
+        const gpad_handle_t c = cb->child[k];
+        if (!c) continue;
+        const int cnt = cb->count(k), off = cb->offsets[k];
+        cb->it.resize((size_t)steps * cnt);
+        const int rc = gpad_last_restarts(c, cb->it.data(), steps * cnt);
+        if (rc < 0) return rc;
+        for (int t = 0; t < steps; ++t)
+            for (int i = 0; i < cnt; ++i) all[(size_t)t * batch + cb->perm[(size_t)off + i]] = cb->it[(size_t)t * cnt + i];
+    }
+    const int k = (int)std::min<size_t>(entries, (size_t)cap);
+    std::copy(all.begin(), all.begin() + k, restarts);
+    return k;
+}
+
 // (the handles that ran last report: the children, or after a fused loop the whole-batch handle)
 int classes_sync(ClassBinding* cb) {
     int first_err = GPAD_OK;
@@ -587,7 +608,9 @@ static int state_typed(ClassBinding* cb, T* x, T* z, T* y, const T* sg, int step
     const bool loop = steps > 0, host = d.memory == GPAD_MEM_HOST;
     // gpad_class_loop_fused: a loop of a shape the panel loop takes runs as one launch over every class; any
     // other call runs class by class as if it were off (as the loop options do)
+    // (GPAD_OPT_RESTART on: class by class too, on the lockstep loop -- the panel loop does not carry the restart)
     const bool fused = loop && cb->fused_on && cb->fused && sizeof(T) == sizeof(float) &&
+                       cb->fused->tune.restart == 0 &&
                        loop_panel_shape(cb->fused, N, tol, nx + ns);  // (the state and the signals share a row)
     const bool zy_in = !loop || warm;  // a cold loop starts every step from z = y = 0: nothing to bring in
     const size_t batch = (size_t)d.batch, zn = batch * d.n, yn = batch * d.m, xn = batch * nx;

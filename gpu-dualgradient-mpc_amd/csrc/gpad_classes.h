@@ -104,6 +104,8 @@ int classes_infeasibility_resident(ClassBinding* cb, int on);
 // gpad_infeasibility_loop_async likewise
 int classes_infeasibility_loop_async(ClassBinding* cb, int on);
 int classes_last_stats(ClassBinding* cb, gpad_stats_t* st);
+// gpad_last_restarts of the binding: [steps][batch] in the caller's order; returns the entries written
+int classes_last_restarts(ClassBinding* cb, int* restarts, int cap);
 int classes_accumulate(ClassBinding* cb, long long* acc);
 int classes_sync(ClassBinding* cb);
 

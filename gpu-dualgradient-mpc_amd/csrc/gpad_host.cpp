@@ -126,7 +126,7 @@ int collect_stats(gpad_handle_t h, gpad_stats_t* st) {
     }
     // (a run with an infeasibility bound in force plans nothing: its phases have no pairs and no finisher, which
     // the planner models, and its counts are cut short by code 5)
-    if (h->last_phased && h->last_steps == 1 && !(h->zbound > 0.0 && h->last_tol > 0.0)) {
+    if (h->last_phased && h->last_steps == 1 && !(h->zbound > 0.0 && h->last_tol > 0.0) && !h->last_restart) {
         update_plan(h, h->h_counts.data(), batch, h->last_N);
         h->plan_pending = false;  // these counts are at least as recent as any copy in flight
     }
@@ -222,6 +222,8 @@ int gpad_destroy(gpad_handle_t h) {
         h->beta.release();
         h->work.release();
         h->counters.release();
+        h->restarts.release();
+        h->rs_pos.release();
         h->pwork.release();
         h->lipwork.release();
         h->status.release();
@@ -297,6 +299,27 @@ int gpad_last_stats(gpad_handle_t h, gpad_stats_t* st) {
         if (h->last_batch <= 0) return fail(GPAD_ERR_NOT_SETUP, "gpad_last_stats: no run yet");
         HIP_TRY(hipSetDevice(h->device));
         return collect_stats(h, st);
+    });
+}
+
+int gpad_last_restarts(gpad_handle_t h, int* restarts, int cap) {
+    return gpad::abi_guard("gpad_last_restarts", [&]() -> int {
+        if (!h || !restarts || cap < 0) return fail(GPAD_ERR_INVALID, "gpad_last_restarts: bad argument");
+        if (h->cls) {
+            HIP_TRY(hipSetDevice(h->device));
+            return gpad::classes_last_restarts(h->cls, restarts, cap);
+        }
+        // (no run yet: the zeros of one solve of the bound batch)
+        const size_t entries = h->last_batch > 0 ? (size_t)h->last_batch * h->last_steps : (size_t)h->dims.batch;
+        const int k = (int)std::min(entries, (size_t)cap);
+        if (h->last_batch <= 0 || !h->last_restart || !h->restarts.p) {
+            std::fill(restarts, restarts + k, 0);
+            return k;
+        }
+        HIP_TRY(hipSetDevice(h->device));
+        HIP_TRY(hipMemcpyAsync(restarts, h->restarts.p, sizeof(int) * (size_t)k, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        return k;
     });
 }
 

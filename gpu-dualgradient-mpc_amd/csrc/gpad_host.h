@@ -88,6 +88,7 @@ inline constexpr OptionSpec kOptions[] = {
     {GPAD_OPT_P64_REFILL, &gpad::Tuning::p64_no_refill, 0, 1, true},
     {GPAD_OPT_LOOP_ASYNC, &gpad::Tuning::loop_async, 0, 1, false},
     {GPAD_OPT_LOOP_PANEL, &gpad::Tuning::loop_panel, 0, 1, false},
+    {GPAD_OPT_RESTART, &gpad::Tuning::restart, 0, kOptBig, false},  // (changes results: include/gpad.h)
 };
 
 // Run status block (gpad_handle_s::status): the device error word, then the per-workgroup maxima
@@ -152,6 +153,9 @@ struct gpad_handle_s {
     DevBuf work, counters, pwork;
     DevBuf lipwork;      // gpad_lipschitz: the squaring buffers, norm slots and staged operands of one chunk
     std::vector<int> h_counts;
+    DevBuf restarts;           // GPAD_OPT_RESTART: restarts per solve of the last run, [steps][batch]
+    DevBuf rs_pos;             // ... on the panels: a parked instance's position in the schedule, [batch]
+    bool last_restart = false;  // ... which ran with the option on (else gpad_last_restarts reports zeros)
     // run status block on the device (RunStatus above): the error word the kernels report into and
     // the per-workgroup maxima of |g|, the certification floor's data term (include/gpad.h gpad_run)
     DevBuf status;             // RunStatus
@@ -234,7 +238,11 @@ void build_p64_order(gpad_handle_t h, const int* counts, int batch);
 template <typename T>
 void fill_solve_args(gpad_handle_t h, int N, double tol, gpad::SolveArgs<T>* a);
 // Enqueue one fused solve on device buffers (no staging, no sync).  Counters: iters/conv
-// [batch] each.  *kernel_out = the family that ran.
+// [batch] each.  *kernel_out = the family that ran.  restarts: with GPAD_OPT_RESTART on, [batch] of
+// Handle::restarts for this solve's restart counts (restart_counts below sizes the buffer for the run).
 template <typename T>
 int launch_solve(gpad_handle_t h, T* dz, T* dy, const T* dM, const T* dg, int N, double tol, bool scaled_vec,
-                 int* iters, int* conv, int* kernel_out);
+                 int* iters, int* conv, int* kernel_out, int* restarts = nullptr);
+// Before a run of nsolve solves: notes whether GPAD_OPT_RESTART is on (Handle::last_restart) and, when it is,
+// sizes Handle::restarts; *out (out nullable) = its base, or null with the option off
+int restart_counts(gpad_handle_t h, int nsolve, int** out);

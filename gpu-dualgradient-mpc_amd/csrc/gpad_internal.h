@@ -41,6 +41,8 @@ struct Tuning {
                               // the resident kernel carries the certificate where unbound runs take that kernel
     int fk_loop_async = 0;    // gpad_infeasibility_loop_async (likewise): with a bound in force GPAD_OPT_LOOP_ASYNC
                               // runs the asynchronous loop's certificate kernels instead of the lockstep loop
+    int restart = 0;          // GPAD_OPT_RESTART: adaptive restart of the momentum, a decision every `restart`
+                              // iterations (0: off).  The one option that changes results (include/gpad.h)
 };
 
 // Device error word of a run (SolveArgs::err): kernels OR these bits in with a vector atomic;
@@ -150,8 +152,17 @@ struct SolveArgs {
 // launchers (return hipError_t of the launch)
 // fk: the infeasibility certificate of the run (gpad_farkas.h), or null: the kernel without it
 struct FarkasArgs;
+// The adaptive restart of a run (GPAD_OPT_RESTART): a decision after every iteration whose count in the
+// instance's own solve is a multiple of R
+struct RestartArgs {
+    int R;       // >= 1
+    int* count;  // [batch] restarts of each instance's solve (panels: also a parked instance's count so far)
+    int* pos;    // panels: [batch] a parked instance's position in the schedule (stream kernel: unused)
+};
+// rs: the kernel's variant with the adaptive restart, or null
 template <typename T>
-hipError_t launch_stream(const SolveArgs<T>& a, hipStream_t s, const FarkasArgs* fk = nullptr);
+hipError_t launch_stream(const SolveArgs<T>& a, hipStream_t s, const FarkasArgs* fk = nullptr,
+                         const RestartArgs* rs = nullptr);
 // fk: the non-flat kernel's variant with the infeasibility certificate (gpad_resident_farkas.hip), or null
 hipError_t launch_resident(const SolveArgs<float>& a, hipStream_t s, bool* supported, const FarkasArgs* fk = nullptr);
 // two-instance ping-pong kernel over a work list (shared matrices; gpad_duo.hip): the
@@ -268,7 +279,9 @@ __device__ __forceinline__ void list_survivors(const Args& a, int P, bool park, 
 // this geometry
 // fk: the infeasibility certificate of the run (gpad_farkas.h) -- the T-wave kernel's variant for every
 // T <= 16 (n, m <= 256), no pair layout and no finisher; *supported false beyond -- or null
-hipError_t launch_panel(const SolveArgs<float>& a, hipStream_t s, bool* supported, const FarkasArgs* fk = nullptr);
+// rs (without fk): the adaptive restart of the run -- the T-wave kernel's restart variant under the same rules
+hipError_t launch_panel(const SolveArgs<float>& a, hipStream_t s, bool* supported, const FarkasArgs* fk = nullptr,
+                        const RestartArgs* rs = nullptr);
 // launch_panel at (n, m) runs the panel pairs, which fold max |g| into their loads (gmax_part)
 bool panel_folds_gmax(int n, int m);
 size_t panel_work_bytes(int m, int batch);
@@ -292,7 +305,7 @@ int panel_tiles(int n, int m, int batch);
 hipError_t launch_pack_panel(const float* ML, const float* G, int n, int m, int batch, float mg_sign,
                              double g_scale, void* frag, hipStream_t s);
 hipError_t launch_panel_single(int T, const SolveArgs<float>& a, int grid, hipStream_t s,
-                               const FarkasArgs* fk = nullptr);
+                               const FarkasArgs* fk = nullptr, const RestartArgs* rs = nullptr);
 // gpad_pairs.hip: one phase launch of the pair / relay kernel, T = 9..16 (picks the KQ / DROP instantiation)
 hipError_t launch_panel_pairs(int T, const SolveArgs<float>& a, int grid, hipStream_t s);
 // gpad_compact.hip: the boundary before phase ph >= 1: the survivors phase ph - 1 listed per panel

@@ -73,16 +73,37 @@ hipError_t launch_pack_panel(const float* ML, const float* G, int n, int m, int 
 // slowest instance of their static panel finishes.  Columns are independent in the MFMA, so an
 // instance's arithmetic does not depend on its column, panel or phase (bit-exact either way).
 // A workgroup walks panels grid-stride, so any batch size runs on a resident-sized grid.
+#define GPAD_PANEL_RS 0
 #define GPAD_PANEL_FK 0
 #include "gpad_panel_solve.inc"
 #undef GPAD_PANEL_FK
 #define GPAD_PANEL_FK 1
 #include "gpad_panel_solve.inc"
 #undef GPAD_PANEL_FK
+#undef GPAD_PANEL_RS
+#define GPAD_PANEL_RS 1
+#define GPAD_PANEL_FK 0
+#include "gpad_panel_solve.inc"
+#undef GPAD_PANEL_FK
+#undef GPAD_PANEL_RS
 
 // one phase launch of gpad_panel_kernel<T>, T = 1..8 (the phase loop is gpad_phases.cpp's); with fk the
-// variant with the infeasibility certificate, T = 1..16
-hipError_t launch_panel_single(int T, const SolveArgs<float>& a, int grid, hipStream_t s, const FarkasArgs* fk) {
+// variant with the infeasibility certificate, with rs (and no fk) the one with the adaptive restart, T = 1..16
+hipError_t launch_panel_single(int T, const SolveArgs<float>& a, int grid, hipStream_t s, const FarkasArgs* fk,
+                               const RestartArgs* rs) {
+    if (rs) {
+        if (fk || rs->R < 1 || !rs->count || !rs->pos) return hipErrorInvalidValue;
+#define PANEL_CASE(TT) \
+    case TT: hipLaunchKernelGGL((gpad_panel_restart_kernel<TT>), dim3(grid), dim3(64 * TT), 0, s, a, *rs); break;
+        switch (T) {
+            PANEL_CASE(1) PANEL_CASE(2) PANEL_CASE(3) PANEL_CASE(4) PANEL_CASE(5) PANEL_CASE(6) PANEL_CASE(7)
+            PANEL_CASE(8) PANEL_CASE(9) PANEL_CASE(10) PANEL_CASE(11) PANEL_CASE(12) PANEL_CASE(13) PANEL_CASE(14)
+            PANEL_CASE(15) PANEL_CASE(16)
+            default: return hipErrorInvalidValue;
+        }
+#undef PANEL_CASE
+        return hipGetLastError();
+    }
     if (fk) {
 #define PANEL_CASE(TT) \
     case TT: hipLaunchKernelGGL((gpad_panel_farkas_kernel<TT>), dim3(grid), dim3(64 * TT), 0, s, a, *fk); break;

@@ -5,8 +5,20 @@
 // column leaves the panel like a converged one (code 5, z* = z, y* = y+).  Two inclusions rather than one
 // device function inlined into two kernels: through such a function gpad_panel_kernel's code is not the one
 // it has as a kernel of its own (tools/isa_diff.py), and with nothing bound it must be.
+// GPAD_PANEL_RS 1 (with GPAD_PANEL_FK 0): gpad_panel_restart_kernel<T>, the same solve with the adaptive restart
+// of the momentum (GPAD_OPT_RESTART, include/gpad.h).  Every column carries its own position `pos` in the
+// theta / beta tables (read per lane from global memory) and its restart count.  On a decision iteration -- v a
+// multiple of rs.R below N; v is every column's own count, also in a carried phase -- a lane sums
+// (double)(w - y+) * (double)(y+ - y) over its four rows, the lane groups j are folded by two butterflies and
+// the T row tiles meet through one LDS word per (tile, column), read after the iteration's closing barrier.
+// Algorithm 1 comes first; a column with q > 0 that goes on then writes w = y+ over its slot and returns to
+// position 0, and one more barrier follows, on decision iterations only.  A parked column keeps pos and count
+// in rs.pos / rs.count.  The additions are preprocessor blocks: the other variants keep their text.
 template <int T>
-#if GPAD_PANEL_FK
+#if GPAD_PANEL_RS
+__global__ __launch_bounds__(64 * T) void gpad_panel_restart_kernel(SolveArgs<float> a, RestartArgs rs) {
+    constexpr bool FK = false;
+#elif GPAD_PANEL_FK
 __global__ __launch_bounds__(64 * T) void gpad_panel_farkas_kernel(SolveArgs<float> a, FarkasArgs fk) {
     constexpr bool FK = true;
 #else
@@ -22,6 +34,9 @@ __global__ __launch_bounds__(64 * T) void gpad_panel_kernel(SolveArgs<float> a) 
     __shared__ TestSlot<float> slots[T];
 #if GPAD_PANEL_FK
     __shared__ double fqs[T][16];  // the nomination partials q of (row tile, column)
+#endif
+#if GPAD_PANEL_RS
+    __shared__ double rqs[T][16];  // the restart partials q of (row tile, column)
 #endif
 
     const int lane = threadIdx.x & 63;
@@ -85,11 +100,31 @@ __global__ __launch_bounds__(64 * T) void gpad_panel_kernel(SolveArgs<float> a) 
         __syncthreads();
 
         int v = a.v_begin;
+#if GPAD_PANEL_RS
+        int pos = 0, nrs = 0;  // the column's position in the schedule and its restarts (the same in every lane of it)
+        if (!fresh && active) {
+            pos = rs.pos[inst];
+            nrs = rs.count[inst];
+        }
+        while (true) {
+            const float th = a.theta[pos], bn = a.beta[pos + 1];
+            ++pos;
+            ++v;
+            const bool dec = v < N && (v % rs.R) == 0;  // uniform: a restart decision follows this iteration
+            float4 wo4 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            float yo[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+            if (dec) {  // this iteration's w (own slot) and y, which panel_dual overwrites
+                wo4 = Wl4[slot];
+#pragma unroll
+                for (int r = 0; r < 4; ++r) yo[r] = y[r];
+            }
+#else
         float th = a.theta[v], bn = a.beta[v + 1];
         while (true) {
             // schedule prefetched one iteration ahead (tables hold N + 2 entries)
             const float th_next = a.theta[v + 1], bn_next = a.beta[v + 2];
             ++v;
+#endif
             const bool chk = use_tol && (v % K) == 0;  // uniform: every column is at iteration v
             const bool cert = FK && chk && (v % (4 * K)) == 0;  // a certificate event
             FarkasPart fq;
@@ -100,10 +135,41 @@ __global__ __launch_bounds__(64 * T) void gpad_panel_kernel(SolveArgs<float> a) 
             // ---- GEMM 2 + epilogue: y+ = [w + G_L zhat + p_D]+ (8d), next w (8a) ----------
             TestPart<float> part = panel_dual<FK>(panel_gemm<T>(PA2, Zh, voff, lane), Wl4, Pd4, slot, omt, th, bn,
                                                   use_tol, chk, active, 16 * t + j, m, y, u, cert, &fq);
+#if GPAD_PANEL_RS
+            if (dec) {
+                const float wo[4] = {wo4.x, wo4.y, wo4.z, wo4.w};
+                double q = 0.0;
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+                    if (active && (16 * t + 4 * r + j) < m) q += (double)(wo[r] - y[r]) * (double)(y[r] - yo[r]);
+                q += __shfl_xor(q, 16, 64);
+                q += __shfl_xor(q, 32, 64);
+                if (j == 0) rqs[t][c] = q;
+            }
+            __syncthreads();
+            bool rhit = false;  // the column restarts, unless this iteration ends its solve
+            if (dec) {
+                double q = 0.0;
+                for (int s = 0; s < T; ++s) q += rqs[s][c];
+                rhit = q > 0.0;
+            }
+            if (!chk && v < a.v_end) {
+                if (dec) {
+                    if (rhit && active) {
+                        Wl4[slot] = make_float4(y[0], y[1], y[2], y[3]);
+                        pos = 0;
+                        ++nrs;
+                    }
+                    __syncthreads();
+                }
+                continue;
+            }
+#else
             th = th_next;
             bn = bn_next;
             __syncthreads();
             if (!chk && v < a.v_end) continue;
+#endif
 
             // ---- Algorithm 1 test, per column: lane groups j, then row tiles through LDS ----
             int code = 0;
@@ -166,9 +232,22 @@ __global__ __launch_bounds__(64 * T) void gpad_panel_kernel(SolveArgs<float> a) 
                 if (t == 0 && j == 0) {
                     a.iters[inst] = v;
                     a.conv[inst] = code;
+#if GPAD_PANEL_RS
+                    rs.count[inst] = nrs;
+#endif
                 }
                 active = false;
             }
+#if GPAD_PANEL_RS
+            if (dec) {  // Algorithm 1 came first: the columns that go on (also into the next phase)
+                if (rhit && active) {
+                    Wl4[slot] = make_float4(y[0], y[1], y[2], y[3]);
+                    pos = 0;
+                    ++nrs;
+                }
+                __syncthreads();
+            }
+#endif
 #if GPAD_PANEL_FK
             if (cert) {
                 // nomination, per column and the same in every wave: q = the slots' partials in order
@@ -230,6 +309,12 @@ __global__ __launch_bounds__(64 * T) void gpad_panel_kernel(SolveArgs<float> a) 
                         if (use_tol) a.uc[(size_t)inst * m + i] = u[r];
                     }
                 }
+#if GPAD_PANEL_RS
+                if (t == 0 && j == 0) {
+                    rs.pos[inst] = pos;
+                    rs.count[inst] = nrs;
+                }
+#endif
             }
             if (t == 0) list_survivors(a, p, park, inst, lane, j);  // lanes 0..15 speak for the columns
         }

@@ -267,8 +267,8 @@ size_t panel_work_bytes(int m, int batch) { return phase_work(nullptr, m, batch)
 // decides the resident grid, who zeroes the counters, and which kernel a phase launches.
 // ---------------------------------------------------------------------------------------------
 static hipError_t launch_panel_phase(int T, const SolveArgs<float>& a, int grid, hipStream_t s,
-                                     const FarkasArgs* fk) {
-    if (fk) return launch_panel_single(T, a, grid, s, fk);  // the T-wave kernel at every T it has
+                                     const FarkasArgs* fk, const RestartArgs* rs) {
+    if (fk || rs) return launch_panel_single(T, a, grid, s, fk, rs);  // the T-wave kernel at every T it has
     if (T == 0) {  // (its status was never looked at: the launch's own error is what counts)
         (void)launch_bigpanel(a, grid, s);
         return hipGetLastError();
@@ -276,22 +276,25 @@ static hipError_t launch_panel_phase(int T, const SolveArgs<float>& a, int grid,
     return T > 8 ? launch_panel_pairs(T, a, grid, s) : launch_panel_single(T, a, grid, s);
 }
 
-// fk: the infeasibility certificate (launch_panel): the T-wave kernel's variant, no finisher
-static hipError_t launch_panel_phases(int T, SolveArgs<float> a, hipStream_t s, const FarkasArgs* fk) {
+// fk: the infeasibility certificate (launch_panel): the T-wave kernel's variant, no finisher; rs: the adaptive
+// restart, likewise (`tw`: either)
+static hipError_t launch_panel_phases(int T, SolveArgs<float> a, hipStream_t s, const FarkasArgs* fk,
+                                      const RestartArgs* rs) {
+    const bool tw = fk || rs;
     // Grid = resident workgroups (panel_resident_grid).  Workgroups walk their panels grid-stride.
     const int panels = (a.batch + 15) / 16;
-    const int resident = fk && T > 8 ? 2 * a.num_cus : panel_resident_grid(T, a.num_cus);
+    const int resident = tw && T > 8 ? 2 * a.num_cus : panel_resident_grid(T, a.num_cus);
     int grid = panels < resident ? panels : resident;
     const Tuning tn = a.tune ? *a.tune : Tuning{};
     if (tn.panel_max_grid > 0 && tn.panel_max_grid < grid) grid = tn.panel_max_grid;  // grid-stride panels
     const bool phased = a.tol > 0.0 && a.pwork != nullptr && tn.phased;
-    a.fin_thresh = phased && !fk ? panel_fin_thresh(a.n, a.m, a.num_cus, &tn) : 0;
+    a.fin_thresh = phased && !tw ? panel_fin_thresh(a.n, a.m, a.num_cus, &tn) : 0;
     if (!phased) {  // fixed N (or no workspace): one phase, nothing carried
         a.v_begin = 0;
         a.v_end = a.N;
         a.idx_in = nullptr;
         a.count_in = nullptr;
-        return launch_panel_phase(T, a, grid, s, fk);
+        return launch_panel_phase(T, a, grid, s, fk, rs);
     }
     // survivors listed per panel, densified at each boundary by phase_compact_kernel (one idx
     // list suffices: phase ph reads idx0 while it lists into seg_idx)
@@ -305,7 +308,7 @@ static hipError_t launch_panel_phases(int T, SolveArgs<float> a, hipStream_t s, 
     // the phase counters and the finisher's queue counters: zeroed by the first launch's workgroup 0
     // (panel pairs), else one memset
     hipError_t e = hipSuccess;
-    if (T > 8 && !fk) {
+    if (T > 8 && !tw) {
         a.zero_w = w.counts;
         a.zero_n = 2 * kPanelMaxPhases;
     } else if ((e = hipMemsetAsync(w.counts, 0, sizeof(int) * 2 * kPanelMaxPhases, s)) != hipSuccess) {
@@ -357,7 +360,7 @@ static hipError_t launch_panel_phases(int T, SolveArgs<float> a, hipStream_t s, 
             if (tn.duo_max_grid > 0 && tn.duo_max_grid < g) g = tn.duo_max_grid;  // more claims
             if ((e = launch_duo(a, g, s)) != hipSuccess) return e;
         }
-        if ((e = launch_panel_phase(T, a, grid, s, fk)) != hipSuccess) return e;
+        if ((e = launch_panel_phase(T, a, grid, s, fk, rs)) != hipSuccess) return e;
         a.zero_w = nullptr;
         v0 = v1;
     }
@@ -366,9 +369,10 @@ static hipError_t launch_panel_phases(int T, SolveArgs<float> a, hipStream_t s, 
 
 bool panel_folds_gmax(int n, int m) { return panel_tiles_for(n, m) > 8; }
 
-hipError_t launch_panel(const SolveArgs<float>& a, hipStream_t s, bool* supported, const FarkasArgs* fk) {
+hipError_t launch_panel(const SolveArgs<float>& a, hipStream_t s, bool* supported, const FarkasArgs* fk,
+                        const RestartArgs* rs) {
     const int T = panel_tiles_for(a.n, a.m);  // 0: big panels
-    if (fk && T < 1) {  // (the big panels do not carry it)
+    if ((fk || rs) && T < 1) {  // (the big panels do not carry it)
         *supported = false;
         return hipSuccess;
     }
@@ -376,7 +380,7 @@ hipError_t launch_panel(const SolveArgs<float>& a, hipStream_t s, bool* supporte
     *supported = a.frag != nullptr && a.strideA == 0 && a.strideB == 0 &&
                  (T ? a.frag_tiles == T
                     : bigpanel_supported(a.n, a.m) && a.frag_tiles == panel_tiles(a.n, a.m, a.batch));
-    return *supported ? launch_panel_phases(T, a, s, fk) : hipSuccess;
+    return *supported ? launch_panel_phases(T, a, s, fk, rs) : hipSuccess;
 }
 
 // ---------------------------------------------------------------------------------------------

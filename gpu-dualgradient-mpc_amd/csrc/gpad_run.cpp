@@ -107,9 +107,33 @@ void fill_solve_args(gpad_handle_t h, int N, double tol, gpad::SolveArgs<T>* a) 
 template void fill_solve_args<float>(gpad_handle_t, int, double, gpad::SolveArgs<float>*);
 template void fill_solve_args<double>(gpad_handle_t, int, double, gpad::SolveArgs<double>*);
 
+int restart_counts(gpad_handle_t h, int nsolve, int** out) {
+    if (out) *out = nullptr;
+    h->last_restart = h->tune.restart > 0;
+    if (!h->last_restart) return GPAD_OK;
+    if (int rc = h->restarts.ensure(sizeof(int) * (size_t)h->dims.batch * nsolve)) return rc;
+    if (out) *out = (int*)h->restarts.p;
+    return GPAD_OK;
+}
+
+// GPAD_OPT_RESTART on: what the restart kernels do not carry (the follow-ups of include/gpad.h), refused by
+// name rather than run without the restart
+static int restart_refusal(gpad_handle_t h, double tol) {
+    const char* what = h->flat                                   ? "flat setups (gpad_setup_flat)"
+                       : h->hess_ok                              ? "a bound Hessian (gpad_setup_hessian)"
+                       : h->zbound > 0.0 && tol > 0.0            ? "an infeasibility bound in force with tol > 0"
+                       : h->dims.kernel == GPAD_KERNEL_RESIDENT ? "a forced resident kernel"
+                       : h->dims.kernel == GPAD_KERNEL_PANEL && h->dims.dtype == GPAD_DTYPE_F64
+                           ? "the f64 panels (f64 runs the stream kernel)"
+                           : nullptr;
+    if (!what) return GPAD_OK;
+    return fail(GPAD_ERR_UNSUPPORTED, std::string("adaptive restart (GPAD_OPT_RESTART) runs on the stream kernel and the "
+                                                  "f32 T-wave panels: not with ") + what);
+}
+
 template <typename T>
 int launch_solve(gpad_handle_t h, T* dz, T* dy, const T* dM, const T* dg, int N, double tol,
-                 bool scaled_vec, int* iters, int* conv, int* kernel_out) {
+                 bool scaled_vec, int* iters, int* conv, int* kernel_out, int* restarts) {
     const gpad_dims_t& d = h->dims;
     const int n = d.n, m = d.m, batch = d.batch;
     gpad::SolveArgs<T> a{};
@@ -147,10 +171,56 @@ int launch_solve(gpad_handle_t h, T* dz, T* dy, const T* dM, const T* dg, int N,
     h->last_N = N;
     hipError_t e = hipSuccess;
     bool ok = false;
+    if (h->tune.restart > 0) {
+        if (int rc = restart_refusal(h, tol)) {
+            h->last_restart = false;  // (nothing ran: gpad_last_restarts reports zeros)
+            return rc;
+        }
+        if (!restarts) return fail(GPAD_ERR_INVALID, "launch_solve: no restart counters");
+    }
     if (N == 0) {  // nothing to iterate: outputs are the inputs, zero counts
         HIP_TRY(hipMemsetAsync(a.iters, 0, sizeof(int) * (size_t)batch, h->stream));
         HIP_TRY(hipMemsetAsync(a.conv, 0, sizeof(int) * (size_t)batch, h->stream));
+        if (h->tune.restart > 0) HIP_TRY(hipMemsetAsync(restarts, 0, sizeof(int) * (size_t)batch, h->stream));
         *kernel_out = d.kernel == GPAD_KERNEL_AUTO ? GPAD_KERNEL_STREAM : d.kernel;
+        return finish(GPAD_OK);
+    }
+    // Adaptive restart (GPAD_OPT_RESTART): the position in the schedule is per instance.  A forced PANEL, and AUTO
+    // where unbound AUTO runs panels, run the T-wave panels' restart variant where it applies (shared f32 matrices,
+    // n, m <= 256: T <= 16) -- no pair layout, no finisher, as with a certificate bound; AUTO otherwise and a
+    // forced STREAM the stream kernel's, f32 and f64, every shape.  The engines that share one position per
+    // launch (pairs, finisher, resident, the f64 and big panels) are not entered
+    if (h->tune.restart > 0) {
+        gpad::RestartArgs rs{h->tune.restart, restarts, nullptr};
+        if constexpr (sizeof(T) == sizeof(float)) {
+            const int panel_min = gpad::resident_supported(n, m) ? 4 * h->num_cus : 64;
+            const bool want = kernel == GPAD_KERNEL_PANEL || (kernel == GPAD_KERNEL_AUTO && batch > panel_min);
+            bool pok = false;
+            if (want && d.shared && h->frag_ok) {
+                int rc = h->pwork.ensure(gpad::panel_work_bytes(m, batch));
+                if (!rc) rc = h->rs_pos.ensure(sizeof(int) * (size_t)batch);
+                if (rc) return rc;
+                rs.pos = (int*)h->rs_pos.p;
+                a.pwork = h->pwork.p;
+                a.used = &h->last_phases;  // (no plan: the planner models the pairs and the finisher)
+                e = gpad::launch_panel(a, h->stream, &pok, nullptr, &rs);
+                if (e != hipSuccess) return fail(GPAD_ERR_HIP, std::string("panel: ") + hipGetErrorString(e));
+                if (!pok) a.pwork = nullptr, a.used = nullptr;
+            }
+            if (!pok && kernel == GPAD_KERNEL_PANEL)
+                return fail(GPAD_ERR_UNSUPPORTED, "adaptive restart (GPAD_OPT_RESTART) on the panels needs shared f32 "
+                                                  "matrices with n, m <= 256");
+            if (pok) {
+                *kernel_out = GPAD_KERNEL_PANEL;
+                h->last_phased = tol > 0.0 && h->tune.phased;  // (else one launch: no phases to report)
+                return finish(GPAD_OK);
+            }
+        }
+        e = gpad::launch_stream<T>(a, h->stream, nullptr, &rs);
+        if (e != hipSuccess)
+            return fail(e == hipErrorInvalidValue ? GPAD_ERR_UNSUPPORTED : GPAD_ERR_HIP,
+                        std::string("stream kernel: ") + hipGetErrorString(e) + " (n+m beyond the LDS budget?)");
+        *kernel_out = GPAD_KERNEL_STREAM;
         return finish(GPAD_OK);
     }
     // The infeasibility certificate (gpad_setup_infeasibility) is carried by the stream kernel and by the f32
@@ -314,9 +384,9 @@ int launch_solve(gpad_handle_t h, T* dz, T* dy, const T* dM, const T* dg, int N,
     return finish(GPAD_OK);
 }
 template int launch_solve<float>(gpad_handle_t, float*, float*, const float*, const float*, int, double, bool, int*,
-                                 int*, int*);
+                                 int*, int*, int*);
 template int launch_solve<double>(gpad_handle_t, double*, double*, const double*, const double*, int, double, bool,
-                                  int*, int*, int*);
+                                  int*, int*, int*, int*);
 
 template <typename T>
 static int run_typed(gpad_handle_t h, T* z, T* y, const T* M, const T* g, int N, double tol,
@@ -327,6 +397,8 @@ static int run_typed(gpad_handle_t h, T* z, T* y, const T* M, const T* g, int N,
     if (rc) return rc;
     // [iters | conv]
     if ((rc = h->counters.ensure(sizeof(int) * 2 * (size_t)batch))) return rc;
+    int* restarts = nullptr;
+    if ((rc = restart_counts(h, 1, &restarts))) return rc;
     T *dz = z, *dy = y;
     const T *dM = M, *dg = g;
     const size_t zb = sizeof(T) * (size_t)batch * n, yb = sizeof(T) * (size_t)batch * m;
@@ -356,14 +428,14 @@ static int run_typed(gpad_handle_t h, T* z, T* y, const T* M, const T* g, int N,
         h->plan_pending = false;
     }
     HIP_TRY(hipEventRecord(h->ev0, h->stream));
-    if ((rc = launch_solve<T>(h, dz, dy, dM, dg, N, tol, scaled_vec, iters, iters + batch, &kernel)))
+    if ((rc = launch_solve<T>(h, dz, dy, dM, dg, N, tol, scaled_vec, iters, iters + batch, &kernel, restarts)))
         return rc;
     HIP_TRY(hipEventRecord(h->ev1, h->stream));
     h->timed = true;
     h->last_kernel = kernel;
     h->last_batch = batch;
     h->last_steps = 1;
-    const bool bound_run = h->zbound > 0.0 && tol > 0.0;  // (plans nothing: collect_stats)
+    const bool bound_run = (h->zbound > 0.0 && tol > 0.0) || h->last_restart;  // (plans nothing: collect_stats)
     if (!st && ((h->last_phased && h->tune.plan && !bound_run) || (h->last_p64 && h->tune.lpt))) {  // asynchronous run: counts
         // to the host behind it
         const size_t want = sizeof(int) * (size_t)batch;
@@ -410,6 +482,9 @@ static int run_impl(gpad_handle_t h, void* z0, void* y0, const void* M, const vo
     if ((theta || beta) && h->zbound > 0.0 && tol > 0.0)  // (the certificate's events follow the library's schedule)
         return fail(GPAD_ERR_UNSUPPORTED, "gpad_run_scaled: caller theta / beta tables with an infeasibility bound "
                                           "in force (gpad_setup_infeasibility)");
+    if ((theta || beta) && h->tune.restart > 0)  // (a restart returns to position 0 of the library's schedule)
+        return fail(GPAD_ERR_UNSUPPORTED, "gpad_run_scaled: caller theta / beta tables with adaptive restart on "
+                                          "(GPAD_OPT_RESTART)");
     HIP_TRY(hipSetDevice(h->device));
     if (h->dims.dtype == GPAD_DTYPE_F64)
         return run_typed<double>(h, (double*)z0, (double*)y0, (const double*)M, (const double*)g, N,

@@ -219,6 +219,7 @@ bool loop_panel_shape(gpad_handle_t h, int N, double tol, int nxa) {
 // gpad_classes.cpp attaches them only to a loop that meets loop_panel_shape.
 static int one_launch_engine(gpad_handle_t h, bool loop, int N, double tol, int nxa) {
     if (h->cloop) return GPAD_KERNEL_LOOP_CLASSES;
+    if (h->tune.restart > 0) return 0;  // GPAD_OPT_RESTART: the one-launch loops do not carry the restart
     const gpad_dims_t& d = h->dims;
     const int n = d.n, m = d.m, nu = h->plant->nu;
     const bool lpanel = loop && h->tune.loop_panel && loop_panel_shape(h, N, tol, nxa);
@@ -331,7 +332,8 @@ static int run_loop_lockstep(gpad_handle_t h, const StateWork<T>& w, bool loop, 
             HIP_TRY(hipMemsetAsync(w.dy, 0, sizeof(T) * w.yn, h->stream));
         }
         int* it = counters + 2 * (size_t)batch * t;
-        if (int rc = launch_solve<T>(h, w.dz, w.dy, w.Mx, w.gx, N, tol, false, it, it + batch, kernel)) return rc;
+        int* rst = h->last_restart ? (int*)h->restarts.p + (size_t)batch * t : nullptr;  // (restart_counts)
+        if (int rc = launch_solve<T>(h, w.dz, w.dy, w.Mx, w.gx, N, tol, false, it, it + batch, kernel, rst)) return rc;
         if (nsolve > 1 && tol > 0.0) {  // this step's max |g| slots -> the run's (RunStatus::acc)
             char* sp = (char*)h->status.p;
             HIP_TRY(gpad::launch_absmax_fold(reinterpret_cast<const double*>(sp + offsetof(RunStatus, part)),
@@ -359,6 +361,7 @@ static int state_typed(gpad_handle_t h, T* x, T* z, T* y, const T* sg, int steps
     int rc = ensure_schedule(h, N, nullptr, nullptr);
     if (rc) return rc;
     if ((rc = h->counters.ensure(sizeof(int) * 2 * (size_t)d.batch * nsolve))) return rc;
+    if ((rc = restart_counts(h, nsolve, nullptr))) return rc;
     StateWork<T> w{};
     if ((rc = state_work<T>(h, z, y, sg, steps, xs, us, &w))) return rc;
     if (w.S_up) HIP_TRY(hipMemcpyAsync(w.S_up, sg, sizeof(T) * w.sn, hipMemcpyHostToDevice, h->stream));

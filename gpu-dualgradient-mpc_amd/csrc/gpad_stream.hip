@@ -51,11 +51,13 @@ __device__ __forceinline__ StreamLds<T> stream_lds(unsigned char* smem, int ldn,
 }
 
 // LDS bytes of the stream kernel: the vectors, the test slots and (value branches, or the infeasibility
-// certificate) the block-sum partials and z(y+)
+// certificate) the block-sum partials and z(y+); the restart variant: the partials alone (red = the wave
+// partials of its q)
 template <typename T>
-size_t stream_lds_bytes(int ldn, int ldm, bool value) {
+size_t stream_lds_bytes(int ldn, int ldm, bool value, bool restart = false) {
     return sizeof(T) * (size_t)(3 * ldn + 4 * ldm) + sizeof(CheckSlot) * 2 * (kStreamBlock / 64) +
-           (value ? sizeof(double) * (size_t)(kStreamBlock / 64 + ldn) : 0);
+           (value ? sizeof(double) * (size_t)(kStreamBlock / 64 + ldn)
+                  : (restart ? sizeof(double) * (size_t)(kStreamBlock / 64) : 0));
 }
 
 // acc[r] = sum_k Mt[k*ld + r0 + r] * v[k], sequential in k, 4 rows per lane.
@@ -163,32 +165,46 @@ __device__ int stream_value_branch(const SolveArgs<T>& a, const StreamLds<T>& s,
     return V - D <= eV * (D > 1.0 ? D : 1.0) ? 4 : 0;  // :76
 }
 
-// the two variants of the kernel (gpad_stream_solve.inc)
+// the three variants of the kernel (gpad_stream_solve.inc)
+#define GPAD_STREAM_RS 0
 #define GPAD_STREAM_FK 0
 #include "gpad_stream_solve.inc"
 #undef GPAD_STREAM_FK
 #define GPAD_STREAM_FK 1
 #include "gpad_stream_solve.inc"
 #undef GPAD_STREAM_FK
+#undef GPAD_STREAM_RS
+#define GPAD_STREAM_RS 1
+#define GPAD_STREAM_FK 0
+#include "gpad_stream_solve.inc"
+#undef GPAD_STREAM_FK
+#undef GPAD_STREAM_RS
 
-// fk: the infeasibility certificate of this run, or null (the kernel without it)
+// fk: the infeasibility certificate of this run, or null (the kernel without it); rs: its adaptive restart
+// (rs->R >= 1, rs->count [batch]), or null -- not both, and neither with the value-function branches
 template <typename T>
-hipError_t launch_stream(const SolveArgs<T>& a, hipStream_t st, const FarkasArgs* fk) {
-    const size_t lds = stream_lds_bytes<T>(a.ldn, a.ldm, a.Hq != nullptr || fk != nullptr);
-    if (lds > 160 * 1024 || (fk && a.Hq)) return hipErrorInvalidValue;
-    const void* fn = fk ? (const void*)gpad_stream_farkas_kernel<T> : (const void*)gpad_stream_kernel<T>;
+hipError_t launch_stream(const SolveArgs<T>& a, hipStream_t st, const FarkasArgs* fk, const RestartArgs* rs) {
+    const size_t lds = stream_lds_bytes<T>(a.ldn, a.ldm, a.Hq != nullptr || fk != nullptr, rs != nullptr);
+    if (lds > 160 * 1024 || (fk && a.Hq) || (rs && (fk || a.Hq || rs->R < 1 || !rs->count)))
+        return hipErrorInvalidValue;
+    const void* fn = rs   ? (const void*)gpad_stream_restart_kernel<T>
+                     : fk ? (const void*)gpad_stream_farkas_kernel<T>
+                          : (const void*)gpad_stream_kernel<T>;
     if (lds > 64 * 1024) {
         hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
     }
-    if (fk)
+    if (rs)
+        hipLaunchKernelGGL(gpad_stream_restart_kernel<T>, dim3(a.batch), dim3(kStreamBlock), lds, st, a, *rs);
+    else if (fk)
         hipLaunchKernelGGL(gpad_stream_farkas_kernel<T>, dim3(a.batch), dim3(kStreamBlock), lds, st, a, *fk);
     else
         hipLaunchKernelGGL(gpad_stream_kernel<T>, dim3(a.batch), dim3(kStreamBlock), lds, st, a);
     return hipGetLastError();
 }
-template hipError_t launch_stream<float>(const SolveArgs<float>&, hipStream_t, const FarkasArgs*);
-template hipError_t launch_stream<double>(const SolveArgs<double>&, hipStream_t, const FarkasArgs*);
+template hipError_t launch_stream<float>(const SolveArgs<float>&, hipStream_t, const FarkasArgs*, const RestartArgs*);
+template hipError_t launch_stream<double>(const SolveArgs<double>&, hipStream_t, const FarkasArgs*,
+                                          const RestartArgs*);
 
 // r_i = sum_k |G_L[i][k]| of every bound image, fp64, k ascending (the certificate's s term)
 template <typename T>

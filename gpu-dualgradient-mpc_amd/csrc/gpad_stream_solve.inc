@@ -3,8 +3,25 @@
 // infeasibility certificate (gpad_farkas.h) at every fourth test.  Two inclusions rather than one device
 // function inlined into two kernels: through such a function gpad_stream_kernel's code is not the one it
 // has as a kernel of its own (tools/isa_diff.py), and with nothing bound it must be.
+// GPAD_STREAM_RS 1 (with GPAD_STREAM_FK 0): gpad_stream_restart_kernel<T>, the same solve with the adaptive
+// restart of the momentum (GPAD_OPT_RESTART, include/gpad.h): the workgroup's instance reads theta / beta at
+// its own position `pos` of the schedule, and a decision iteration -- one whose count is a multiple of rs.R
+// and which neither ends the solve nor is its last -- sums q = sum_i (w_i - y+_i)(y+_i - y_i) over its rows
+// (the differences rounded in T, products and sum in fp64: per lane in row order, the wave butterfly, the
+// waves' partials in order).  q > 0: w = y+ is written over the extrapolated w and pos returns to 0.
+// Its additions are preprocessor blocks, not `if constexpr`: the other two variants must preprocess to the text
+// they had without it -- dead declarations alone moved their register allocation (tools/isa_diff.py).
+#if GPAD_STREAM_RS
+#define GPAD_STREAM_POS pos
+#else
+#define GPAD_STREAM_POS v
+#endif
 template <typename T>
-#if GPAD_STREAM_FK
+#if GPAD_STREAM_RS
+__global__ __launch_bounds__(kStreamBlock) void gpad_stream_restart_kernel(SolveArgs<T> a, RestartArgs rs) {
+    constexpr bool FK = false;
+    const FarkasArgs fk{};  // (never read)
+#elif GPAD_STREAM_FK
 __global__ __launch_bounds__(kStreamBlock) void gpad_stream_farkas_kernel(SolveArgs<T> a, FarkasArgs fk) {
     constexpr bool FK = true;
 #else
@@ -51,10 +68,13 @@ __global__ __launch_bounds__(kStreamBlock) void gpad_stream_kernel(SolveArgs<T> 
     const int nwaves = kStreamBlock / 64;
     int it = 0;
     int done = 0;
+#if GPAD_STREAM_RS
+    int pos = 0, nrs = 0;  // the instance's position in the schedule, its restarts so far
+#endif
     for (int v = 0; v < a.N; ++v) {
-        const T th = a.theta[v];
+        const T th = a.theta[GPAD_STREAM_POS];
         const T omt = T(1) - th;
-        const T bnext = a.beta[v + 1];
+        const T bnext = a.beta[GPAD_STREAM_POS + 1];
         // ---- phase 1: 8b + 8c, rows of -ML ----------------------------------------------
         for (int r0 = 4 * tid; r0 < n; r0 += 4 * kStreamBlock) {
             T acc[4] = {T(0), T(0), T(0), T(0)};
@@ -78,6 +98,11 @@ __global__ __launch_bounds__(kStreamBlock) void gpad_stream_kernel(SolveArgs<T> 
         if constexpr (FK) cert = chk && ((v + 1) % (4 * a.check_every)) == 0;
         T violz = neg_inf<T>(), violh = neg_inf<T>(), wmin = -neg_inf<T>(), magh = T(0);
         double gap = 0.0;
+#if GPAD_STREAM_RS
+        // a restart decision follows this iteration, unless it ends the solve, on q = sum (w - y+)(y+ - y)
+        const bool dec = v + 1 < a.N && ((v + 1) % rs.R) == 0;
+        double rq = 0.0;
+#endif
         for (int r0 = 4 * tid; r0 < m; r0 += 4 * kStreamBlock) {
             T c[4] = {T(0), T(0), T(0), T(0)};
             chain4<T>(GLt, ldm, r0, s.zh, n, c);
@@ -102,6 +127,9 @@ __global__ __launch_bounds__(kStreamBlock) void gpad_stream_kernel(SolveArgs<T> 
                                 if (cert) fq += (double)yp * (double)pdi;
                         }
                     }
+#if GPAD_STREAM_RS
+                    if (dec) rq += (double)(wi - yp) * (double)(yp - yi);
+#endif
                     s.w[i] = fmad(bnext, yp - yi, yp);               // next 8a
                     s.ys[i] = yp;
                 }
@@ -114,6 +142,12 @@ __global__ __launch_bounds__(kStreamBlock) void gpad_stream_kernel(SolveArgs<T> 
                 if ((tid & 63) == 0) s.red[tid >> 6] = fq;
             }
         }
+#if GPAD_STREAM_RS
+        if (dec) {  // reduced as gap is: the wave butterfly, then the waves' partials in order
+            rq = wave_sum(rq);
+            if ((tid & 63) == 0) s.red[tid >> 6] = rq;
+        }
+#endif
         __syncthreads();
         it = v + 1;
         if (chk) {
@@ -162,6 +196,19 @@ __global__ __launch_bounds__(kStreamBlock) void gpad_stream_kernel(SolveArgs<T> 
             }
         }
         if (done) break;
+#if GPAD_STREAM_RS
+        ++pos;
+        if (dec) {  // Algorithm 1 came first: this iteration did not end the solve
+            double q = 0.0;
+            for (int i = 0; i < nwaves; ++i) q += s.red[i];
+            if (q > 0.0) {  // (uniform) the momentum points uphill: drop it, the schedule starts again
+                for (int i = tid; i < m; i += kStreamBlock) s.w[i] = s.ys[i];
+                pos = 0;
+                ++nrs;
+                __syncthreads();
+            }
+        }
+#endif
     }
     const T* zout = done >= 2 && !(FK && done == kCodeInfeasible) ? s.zh : s.zs;  // tests (B), (B'), (B'') certify zhat
     for (int i = tid; i < n; i += kStreamBlock) zg[i] = zout[i];
@@ -169,6 +216,10 @@ __global__ __launch_bounds__(kStreamBlock) void gpad_stream_kernel(SolveArgs<T> 
     if (tid == 0) {
         a.iters[b] = it;
         a.conv[b] = done;
+#if GPAD_STREAM_RS
+        rs.count[b] = nrs;
+#endif
     }
 }
+#undef GPAD_STREAM_POS
 

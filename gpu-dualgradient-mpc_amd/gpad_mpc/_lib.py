@@ -51,6 +51,7 @@ EXPORTS = [
     "gpad_setup_infeasibility", "gpad_farkas_margin", "gpad_infeasibility_resident",
     "gpad_infeasibility_loop_async",
     "gpad_lipschitz", "gpad_lipschitz_host",
+    "gpad_last_restarts",
 ]
 GROUP_RCCL, GROUP_PEER = 1, 2
 
@@ -76,6 +77,10 @@ OPTIONS = {"phase_len": OPT_PHASE_LEN, "finish_thresh": OPT_FINISH_THRESH, "plan
            "debug_drop_handoff": OPT_DEBUG_DROP_HANDOFF, "p64_relay": OPT_P64_RELAY,
            "p64_refill": OPT_P64_REFILL, "loop_async": OPT_LOOP_ASYNC,
            "loop_panel": OPT_LOOP_PANEL}
+# Set through gpad_set_option as well, but not tuning: adaptive restart of the momentum changes results
+# (include/gpad.h GPAD_OPT_RESTART: a decision every R iterations, 0 = off, the default)
+OPT_RESTART = 24
+SOLVE_OPTIONS = {"restart": OPT_RESTART}
 
 FILE_ROWMAJOR, FILE_FLIPPED, FILE_FLAT = 0, 1, 2
 
@@ -229,6 +234,9 @@ def load(path: str | None = None) -> C.CDLL:
         L.gpad_lipschitz.restype = i
         L.gpad_lipschitz_host.argtypes = [i, i, i, i, i, cvp, cvp, d, C.POINTER(d)]
         L.gpad_lipschitz_host.restype = i
+    if hasattr(L, "gpad_last_restarts"):  # (added within 0.6; absent from older builds under GPAD_LIB_TOLERANT)
+        L.gpad_last_restarts.argtypes = [vp, C.POINTER(i), i]
+        L.gpad_last_restarts.restype = i
     L.gpad_datafile_read.argtypes = [C.c_char_p, i, C.POINTER(DataFile)]
     L.gpad_datafile_write.argtypes = [C.c_char_p, i, C.POINTER(DataFile)]
     L.gpad_datafile_free.argtypes = [C.POINTER(DataFile)]

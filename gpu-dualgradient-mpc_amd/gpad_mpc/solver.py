@@ -68,6 +68,7 @@ class GpadSolver:
         self._device = device
         self.dims = None
         self._classes = 0  # K of a class binding (setup_classes), 0: none
+        self._last_steps = 0  # steps of the last closed_loop, 0 after any other run (last_restarts' shape)
 
     def last_phases(self) -> dict:
         """The phases the last phased panel solve launched (include/gpad.h gpad_last_phases): ends,
@@ -114,8 +115,15 @@ class GpadSolver:
 
     def set_option(self, name, value: int = _lib.OPT_DEFAULT) -> None:
         """gpad_set_option: schedule / launch tuning (``name`` in _lib.OPTIONS or a GPAD_OPT_*
-        code); never changes results.  ``value`` -1 restores the default."""
-        code = _lib.OPTIONS[name] if isinstance(name, str) else int(name)
+        code); never changes results.  ``value`` -1 restores the default.
+
+        ``"restart"`` (_lib.SOLVE_OPTIONS) is set here too and does change results: R >= 1 turns on the
+        adaptive restart of the momentum with a decision every R iterations (include/gpad.h
+        GPAD_OPT_RESTART; 0, the default, is off), see ``last_restarts``."""
+        if isinstance(name, str):
+            code = _lib.SOLVE_OPTIONS[name] if name in _lib.SOLVE_OPTIONS else _lib.OPTIONS[name]
+        else:
+            code = int(name)
         check(self.lib.gpad_set_option(self.h, code, int(value)), f"gpad_set_option({name})")
 
     def set_options(self, **kw) -> None:
@@ -238,6 +246,7 @@ class GpadSolver:
         if codes is not None:  # per-instance termination codes 0..5 (host int32 [batch])
             st.codes = _count_array(codes, "codes", nb)
         want = stats or not _is_torch(z)
+        self._last_steps = 0
         for tab in (theta, beta):  # host tables whatever the memory kind (include/gpad.h)
             if tab is not None and (_is_torch(tab) or not isinstance(tab, np.ndarray)):
                 raise TypeError("theta/beta must be host numpy arrays (include/gpad.h gpad_run_scaled)")
@@ -262,6 +271,18 @@ class GpadSolver:
             st.codes = _count_array(codes, "codes", max(1, self.dims.batch if self.dims else 1))
         check(self.lib.gpad_last_stats(self.h, C.byref(st)), "gpad_last_stats")
         return self._stats_dict(st)
+
+    def last_restarts(self):
+        """Restarts of every solve of the last run (gpad_last_restarts): int32 [batch], or [steps][batch]
+        after ``closed_loop``; zeros when that run had ``restart`` off or before any run."""
+        batch = max(1, self.dims.batch if self.dims else 1)
+        steps = self._last_steps
+        buf = (C.c_int * (batch * max(1, steps)))()
+        n = self.lib.gpad_last_restarts(self.h, buf, len(buf))
+        check(min(n, 0), "gpad_last_restarts")
+        out = np.zeros(len(buf), np.int32)
+        out[:n] = buf[:n]
+        return out.reshape(steps, batch) if steps else out
 
     def phase_plan(self) -> dict:
         """The phase plan the next phased panel solve follows (include/gpad.h gpad_phase_plan):
@@ -449,6 +470,7 @@ class GpadSolver:
         """GPAD for every instance's state x [batch][nx] (M(x), g(x) formed on the device); with
         signals bound (``setup_signals``), ``s`` [batch][ns] is required."""
         st = Stats()
+        self._last_steps = 0
         want = stats or not _is_torch(z)
         if s is not None:
             check(self.lib.gpad_run_state_signals(self.h, _ptr(x), _ptr(s), _ptr(z), _ptr(y), int(N), float(tol),
@@ -484,6 +506,7 @@ class GpadSolver:
         uses signals[t] for its QP data and for the update from x_t to x_{t+1}.  The one-launch loop
         then needs nx + ns <= 64."""
         st = Stats()
+        self._last_steps = int(steps)
         for arr, field in ((iters, "iters"), (codes, "codes")):
             if arr is not None:
                 setattr(st, field, _count_array(arr, field, steps * max(1, self.dims.batch if self.dims else 1)))

@@ -41,7 +41,8 @@ extern "C" {
                               * gpad_setup_infeasibility, gpad_farkas_margin and the termination code
                               * GPAD_CODE_INFEASIBLE (5), returned only with a bound in force;
                               * gpad_infeasibility_resident and gpad_infeasibility_loop_async (off by
-                              * default: no routing changes); gpad_lipschitz, gpad_lipschitz_host */
+                              * default: no routing changes); gpad_lipschitz, gpad_lipschitz_host;
+                              * GPAD_OPT_RESTART (option 24, off by default) and gpad_last_restarts */
 
 /* status codes */
 #define GPAD_OK 0
@@ -748,6 +749,47 @@ int gpad_schedule(int N, int kind, double* theta, double* beta);
                                     * gpad_closed_loop), where that kernel applies, else as without
                                     * the option; 0 (default): off */
 int gpad_set_option(gpad_handle_t h, int option, int value);
+
+/* ---- adaptive restart of the momentum (O'Donoghue & Candes; no reference counterpart) ------------
+ * gpad_set_option(h, GPAD_OPT_RESTART, R), option 24 -- set through gpad_set_option and kept, like every
+ * option, across gpad_setup*, but unlike the tuning options above it CHANGES RESULTS (fewer iterations to
+ * the same tolerance; other z*, y* bits), which is why it is defined apart from them.
+ *   R = 0 (default): off -- every kernel and every result as without the option.
+ *   R >= 1: after every iteration k of an instance's own solve (counted from 1) with k % R == 0 and k < the
+ *     solve's final count, the instance decides on a restart.  Algorithm 1 and the iteration cap come first:
+ *     an iteration that ends the solve decides nothing.  With tol > 0 and at fixed N alike.
+ *   GPAD_OPT_DEFAULT (-1) restores 0, as for every option; any other R < 0 is GPAD_ERR_INVALID.
+ * The decision uses iteration k's own vectors: q = sum_i (double)(w_i - y+_i) * (double)(y+_i - y_i), the two
+ * differences each rounded once in the handle's dtype, the products and the sum in fp64 (f32 products are
+ * exact there), summed in the engine's own order.  The instance restarts iff q > 0: its next iteration runs
+ * with w = y+ exactly and reads theta / beta from position 0 of the schedule, the one after from position 1,
+ * and so on -- each instance has its own position.  z, y and the recursions of Algorithm 1 go on untouched
+ * (theta_0 = 1 makes the average forget z_{-1} by itself).  While the iterates are finite this is, bit for
+ * bit, the plain solve with the per-instance tables theta'[k + 1 + i] = theta[i], beta'[k + 1] = 0,
+ * beta'[k + 1 + i] = beta[i] (i >= 1) spliced in at every restart after the iteration of index k
+ * (tests/restart_ref.py).
+ * Routing with R > 0.  A forced GPAD_KERNEL_PANEL, and GPAD_KERNEL_AUTO where it runs panels without the
+ * option (shared matrices, more instances than the latency kernel serves), run the f32 T-wave MFMA panels'
+ * restart variant where the plain T-wave panels apply -- shared f32 matrices, n, m <= 256; every column has
+ * its own position in the schedule; no pair layout and no finisher, as with a certificate bound; phased
+ * compaction stays, a parked instance keeps its position and count (stats kernel = GPAD_KERNEL_PANEL).
+ * GPAD_KERNEL_AUTO otherwise (f64, per-instance matrices, n or m > 256, small batches) and a forced
+ * GPAD_KERNEL_STREAM run the stream kernel's restart variant (GPAD_KERNEL_STREAM), f32 and f64.  Both give
+ * the same bits.  gpad_run_state and the lockstep gpad_closed_loop (with signals or without) reach them solve
+ * by solve; GPAD_OPT_LOOP_ASYNC, GPAD_OPT_LOOP_PANEL and gpad_class_loop_fused fall back to the lockstep loop
+ * while R > 0, and a class binding forwards the option to its classes.  GPAD_ERR_UNSUPPORTED, with a message
+ * that names the restart, from the run (the handle then still runs with R = 0): a forced
+ * GPAD_KERNEL_RESIDENT, a forced GPAD_KERNEL_PANEL on f64 or with n or m > 256 (the f64 and the big panels),
+ * flat setups, a bound Hessian, caller theta / beta tables in gpad_run_scaled, an infeasibility bound in
+ * force together with tol > 0.  Follow-ups, not built: the restart on the resident kernel, in the panel
+ * loops, on the pairs and the finisher, together with the certificate, and in groups (gpad_group_* take no
+ * options, so a group never runs with the restart on). */
+#define GPAD_OPT_RESTART (24)
+/* The restarts of every solve of the last run, as the iteration counts are laid out: [batch], after
+ * gpad_closed_loop [steps][batch]; a class-bound handle reports them in the caller's order.  Zeros when
+ * that run had the restart off, or before any run.  Writes up to cap entries (synchronises the stream) and
+ * returns the number written, or GPAD_ERR_INVALID (NULL, cap < 0). */
+int gpad_last_restarts(gpad_handle_t h, int* restarts, int cap);
 
 /* Synchronise the handle's stream (for callers using device memory + async runs). */
 int gpad_sync(gpad_handle_t h);
